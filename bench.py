@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on BASELINE.json's config 2 (default), or --config 3 | 4 | 5.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, dtype, the roofline
+of the timed launches). --full adds everything else the line used to carry: the timed output checked against the CPU oracle
+(`accuracy`; a failed gate nulls `value`), the real-binary CPU baseline and, at N = 1 on config 2, the PCIe-inclusive and
+file-to-file figures and configs 3-5. --dump-outputs DIR writes what the last timed step computed to DIR/<name>.npy
+(float32; a fixed seeded sample of whole utterances where the output exceeds 64 MB; the inputs are seeded, so two builds
+can be compared file for file).
 
 --config 3: IS09_emotion LLD (16 + 16 delta) on 10 000 x 10 s; --config 4: the whole ComParE_2016 LLD level (130 columns) on
 12 500 x 10 s (the per-GPU share of 100 000 utterances over 8 GPUs); --config 5: eGeMAPSv02 LLD + the 88 functionals on
@@ -22,7 +29,7 @@ rank runs its own 1000 x 10 s batch ("weak" scaling, no data-path collective); t
 collective in the path -- the gather of the feature matrices to rank 0 -- is
 opensmile_amd/gather.py and is reported next to `value` (gather_ms, value_incl_gather), never in it.
 
-The default N = 1 line also carries (a) "configs": BASELINE.json's configs 3, 4 and 5 at their
+The --full N = 1 line also carries (a) "configs": BASELINE.json's configs 3, 4 and 5 at their
 per-GPU sizes, 2-3 timed steps each, each with its own roofline and real-binary CPU baseline
 (--no-configs skips them), (b) "h2d_inclusive" / "to_host": the same chain with the PCM starting
 in pinned host memory / the features ending there (SURVEY 8d's GPU timing protocol).
@@ -294,6 +301,32 @@ def measured_accuracy(config, host_rows, frame_offsets, pcm, sample_offsets, fun
     return res
 
 
+DUMP_BYTES = 60 * 2 ** 20       # --dump-outputs: whole utterances up to this many bytes (at most 64 MB in all with the .npy headers)
+
+
+def dump_outputs(path, outs, seed=0):
+    """--dump-outputs: what the last timed step handed its caller, as <path>/<name>.npy (float32). `outs` maps a name to (device
+    tensor, its row offsets per utterance). Utterances are taken whole, in one fixed seeded order, until DUMP_BYTES are spent (all
+    of them when everything fits), the same utterances for every array, in batch order; their indices go to
+    <path>/utterances.npy (float64), so that two builds' files compare row for row."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    offs = {name: np.asarray(o, np.int64) for name, (_, o) in outs.items()}
+    n_utt = len(next(iter(offs.values()))) - 1
+    per_utt = sum(np.diff(offs[name]) * t.shape[1] * 4 for name, (t, _) in outs.items())
+    order = np.random.default_rng(seed).permutation(n_utt)
+    keep = np.sort(order[:int(np.searchsorted(np.cumsum(per_utt[order]), DUMP_BYTES, side="right"))])
+    files = []
+    for name, (t, _) in outs.items():
+        o = offs[name]
+        rows = np.concatenate([np.arange(o[u], o[u + 1]) for u in keep]) if keep.size else np.zeros(0, np.int64)
+        a = t[torch.from_numpy(rows).to(t.device)].float().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        files.append(name + ".npy")
+    np.save(os.path.join(path, "utterances.npy"), keep.astype(np.float64))
+    return {"dir": path, "files": files + ["utterances.npy"], "utterances": int(keep.size), "of": n_utt, "seed": seed}
+
+
 def _free_port():
     import socket
     with socket.socket() as sk:
@@ -418,6 +451,11 @@ def main():
                     help="NO kernel is launched and nothing is measured: only the rank plumbing runs (launcher, rendezvous, barrier, "
                          "max-over-ranks, frame sum, gather, JSON) on the gloo backend with CPU tensors -- what the CPU test of the "
                          "N > 1 path uses; the line's metric says so and its value is null")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: accuracy against the CPU oracle, the CPU baseline, and at N = 1 "
+                         "on config 2 the PCIe-inclusive / file-to-file figures and configs 3-5 (the --no-* flags trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
@@ -426,7 +464,7 @@ def main():
     if args.plumbing_only:
         return main_plumbing(args)
     if args.config != 2:
-        res = run_config(args, args.config, init_ranks(args), with_cpu=not args.no_cpu_baseline)
+        res = run_config(args, args.config, init_ranks(args), with_cpu=args.full and not args.no_cpu_baseline)
         if res is not None:
             print(json.dumps(res), flush=True)
         return finish_ranks()
@@ -493,6 +531,9 @@ def main():
     dt = time.perf_counter() - t0
     ms_main, ms_delta = plan.last_timing()
     plan.set_timing(False)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {"lld": (d_out, batch.frame_offsets)})
 
     dts = [dt]
     if world > 1:
@@ -524,13 +565,15 @@ def main():
 
     if rank == 0:
         value = total_frames * args.steps / dt
-        # BASELINE.json's metric: "...; max abs err vs CPU ref" -- measured on the timed run's own output, after the timed region
-        try:
-            accuracy = measured_accuracy(2, lambda a, b: d_out[a:b].cpu().numpy(), batch.frame_offsets, pcm, off)
-        except Exception as e:
-            accuracy = {"pass": False, "error": f"{type(e).__name__}: {e}"}
-        if not accuracy.get("pass"):
-            value = None                          # a fast kernel whose results differ from the reference's is not a measurement
+        accuracy = None
+        if args.full:
+            # BASELINE.json's metric: "...; max abs err vs CPU ref" -- measured on the timed run's own output, after the timed region
+            try:
+                accuracy = measured_accuracy(2, lambda a, b: d_out[a:b].cpu().numpy(), batch.frame_offsets, pcm, off)
+            except Exception as e:
+                accuracy = {"pass": False, "error": f"{type(e).__name__}: {e}"}
+            if not accuracy.get("pass"):
+                value = None                      # a fast kernel whose results differ from the reference's is not a measurement
         # the frame kernel computes the two regression stages itself (smilehip_batch_delta_fused): its launch then reads the hop and
         # writes all 39 columns -- 476 B per frame -- and the window-chain kernel is gone from the step
         fused = bool(getattr(batch, "delta_fused", False)) and ms_delta < 0.2 * ms_main
@@ -580,15 +623,18 @@ def main():
                          "alg_bytes_per_frame": alg_per_frame,
                          "alg_flop_note": "SURVEY 8d's count for R0-R7; the two regression stages add ~2e2 per frame, not counted",
                          "kernel_ms": ms_main, "delta_kernel_ms": ms_delta},
-            "accuracy": accuracy, "max_abs_err": accuracy.get("max_abs_err"), "frame_scaled_err": accuracy.get("frame_scaled_err"),
             "ranks": ranks,
         }
+        if accuracy is not None:
+            res.update(accuracy=accuracy, max_abs_err=accuracy.get("max_abs_err"), frame_scaled_err=accuracy.get("frame_scaled_err"))
+        if dumped is not None:
+            res["outputs_dumped"] = dumped
         if gather_ms is not None:
             res["gather_ms"] = gather_ms
             res["value_incl_gather"] = total_frames * args.steps / (dt + args.steps * gather_ms * 1e-3)
             res["gather_note"] = "every step's feature matrices (frames x 39 f32 per rank) gathered to rank 0, not overlapped"
             res["gather_via"] = gather_via
-        if world == 1 and not args.no_h2d:
+        if world == 1 and args.full and not args.no_h2d:
             try:
                 del d_out, d_pcm
                 res["h2d_inclusive"], res["to_host"] = pcie_figures()
@@ -598,17 +644,17 @@ def main():
                 res["file_to_file"] = file_to_file_figure()
             except Exception as e:
                 res["file_to_file"] = {"value": None, "note": f"failed: {type(e).__name__}: {e}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline()
             except Exception as e:  # the baseline must never take the bench line down
                 res["cpu_baseline"] = {"value": None, "unit": "frames/s", "cores": 0, "kind": "reference",
                                        "sample": f"failed: {e}"}
-        if world == 1 and not args.no_configs:
+        if world == 1 and args.full and not args.no_configs:
             # BASELINE.json's configs 3-5 at their per-GPU sizes, the same protocol, their own short step counts
             res["configs"] = {}
             sub = argparse.Namespace(**vars(args))
-            sub.steps = sub.warmup = sub.utts = None
+            sub.steps = sub.warmup = sub.utts = sub.dump_outputs = None
             for k in (3, 4, 5):
                 try:
                     torch.cuda.empty_cache()
@@ -794,6 +840,12 @@ def run_config(args, config, ranks, with_cpu=True, nested=False):
     by_kernel = capi.kernel_timing_report()      # {name: (launches, summed ms)} over the timed region
     capi.kernel_timing(False)
     plan.set_timing(False)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        outs = {"lld": (d_out, batch.frame_offsets)}
+        if config == 5:
+            outs["functionals"] = (d_func, np.arange(utts + 1))
+        dumped = dump_outputs(args.dump_outputs, outs)
     dts = [dt]
     total_frames = frames
     if world > 1:
@@ -871,17 +923,18 @@ def run_config(args, config, ranks, with_cpu=True, nested=False):
         achieved = dom_alg * frames / (dom_ms * 1e-3) / 1e9
         achieved_step = CHAIN_ALG_BYTES[config] * frames / (dt / steps) / 1e9
         cf = _counter_fields(config, [dom] if dom else c["pmc_kernels"])
-        try:
-            accuracy = measured_accuracy(config, lambda a, b: d_out[a:b].cpu().numpy(), batch.frame_offsets, pcm, off,
-                                         func_rows=(lambda u: d_func[u].cpu().numpy()) if config == 5 else None)
-        except Exception as e:
-            accuracy = {"pass": False, "error": f"{type(e).__name__}: {e}"}
+        accuracy = None
+        if args.full:
+            try:
+                accuracy = measured_accuracy(config, lambda a, b: d_out[a:b].cpu().numpy(), batch.frame_offsets, pcm, off,
+                                             func_rows=(lambda u: d_func[u].cpu().numpy()) if config == 5 else None)
+            except Exception as e:
+                accuracy = {"pass": False, "error": f"{type(e).__name__}: {e}"}
         res = {
             "metric": {3: "IS09_emotion LLD frames/sec (16kHz, 25ms/10ms)", 4: "ComParE_2016 LLD frames/sec (16kHz, 20ms+60ms/10ms)",
                        5: "eGeMAPSv02 LLD+functionals frames/sec (16kHz, 20ms+60ms/10ms)"}[config],
-            "value": (total_frames * steps / dt) if accuracy.get("pass") else None, "unit": "frames/s", "n_gpus": world, "steps": steps, "warmup": warmup,
-            "accuracy": accuracy, "max_abs_err": accuracy.get("max_abs_err"), "cells_bit_identical": accuracy.get("cells_bit_identical"),
-            "cells_checked": accuracy.get("cells"),
+            "value": (total_frames * steps / dt) if accuracy is None or accuracy.get("pass") else None, "unit": "frames/s",
+            "n_gpus": world, "steps": steps, "warmup": warmup,
             "ms_per_step": dt / steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
             "data": "synthetic",
             "config": {"workload": c["workload"], "baseline_config": config, "utterances_per_gpu": utts,
@@ -906,6 +959,11 @@ def run_config(args, config, ranks, with_cpu=True, nested=False):
                          "issue": _issue_roofline(config, dom, dom_ms, by_kernel[dom][0] / steps if dom else 1),
                          "kernels_ms_per_step": {k: round(v[1] / steps, 4) for k, v in sorted(by_kernel.items(), key=lambda kv: -kv[1][1])}},
         }
+        if accuracy is not None:
+            res.update(accuracy=accuracy, max_abs_err=accuracy.get("max_abs_err"), cells_bit_identical=accuracy.get("cells_bit_identical"),
+                       cells_checked=accuracy.get("cells"))
+        if dumped is not None:
+            res["outputs_dumped"] = dumped
         if gather_via is not None:
             res["gathered"], res["gather_via"] = gathered, gather_via
         if gather_ms is not None:

@@ -8,7 +8,7 @@ for lib in "$@"; do
   name=$(basename $lib .so); [ "$lib" = - ] && name=product
   if [ "$lib" = - ]; then unset SMILEHIP_LIB; else export SMILEHIP_LIB=$R/$lib; fi
   if [ $C = 2 ]; then X="--no-configs --no-h2d"; else X="--config $C"; fi
-  timeout 900 python bench.py $X --no-cpu-baseline > $O/ab_c${C}_$name.json 2> $O/ab_c${C}_$name.err || tail -3 $O/ab_c${C}_$name.err
+  timeout 900 python bench.py $X --full --no-cpu-baseline > $O/ab_c${C}_$name.json 2> $O/ab_c${C}_$name.err || tail -3 $O/ab_c${C}_$name.err
   python - $O/ab_c${C}_$name.json $name <<'PY'
 import json, sys
 try:

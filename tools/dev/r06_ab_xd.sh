@@ -1,6 +1,6 @@
 R=$GRAFT_REPO_ROOT; cd $R
 for c in 4 5; do for x in 0 1; do
-  SMILEHIP_JITTER_XD=$x timeout 900 python bench.py --config $c --no-cpu-baseline > /tmp/o.json 2>/tmp/o.err || tail -2 /tmp/o.err
+  SMILEHIP_JITTER_XD=$x timeout 900 python bench.py --config $c --full --no-cpu-baseline > /tmp/o.json 2>/tmp/o.err || tail -2 /tmp/o.err
   python - $c $x <<'PY'
 import json,sys
 d=json.loads(open('/tmp/o.json').read().strip().splitlines()[-1])

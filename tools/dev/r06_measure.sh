@@ -34,14 +34,14 @@ for sec in "$@"; do
       ( time timeout 1200 python -m pytest ${sec#tests:} -m gpu -q -x ) > $O/pytest_sub_$n.log 2>&1; echo "pytest rc=$?" >> $O/pytest_sub_$n.log
       grep -n "^FAILED\|^ERROR\|^E  \|passed\|failed\|pytest rc" $O/pytest_sub_$n.log | cut -c1-400 | head -20 ;;
     bench)
-      ( time timeout 1500 python bench.py ) > $O/bench_default.json 2> $O/bench_default.err; tail -3 $O/bench_default.err
+      ( time timeout 1500 python bench.py --full ) > $O/bench_default.json 2> $O/bench_default.err; tail -3 $O/bench_default.err
       cut -c1-300 $O/bench_default.json
       timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-configs --no-h2d > $O/bench_c2_short.json 2>> $O/bench_default.err
       cut -c1-300 $O/bench_c2_short.json ;;
     benchc:*)
       c=${sec#benchc:}
       if [ $c = 2 ]; then X="--no-configs --no-h2d"; else X="--config $c"; fi
-      timeout 900 python bench.py $X --no-cpu-baseline > $O/bench_c$c.json 2> $O/bench_c$c.err; tail -2 $O/bench_c$c.err
+      timeout 900 python bench.py $X --full --no-cpu-baseline > $O/bench_c$c.json 2> $O/bench_c$c.err; tail -2 $O/bench_c$c.err
       python - $O/bench_c$c.json <<'PY'
 import json, sys
 try:

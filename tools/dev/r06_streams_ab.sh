@@ -5,7 +5,7 @@ set -u
 R=$GRAFT_REPO_ROOT; T=$1; O=$R/gpurun_out/$T; mkdir -p $O; cd $R
 for C in 4 5; do for S in default 0; do
   if [ $S = default ]; then unset SMILEHIP_SERIAL; else export SMILEHIP_SERIAL=$S; fi
-  timeout 900 python bench.py --config $C --no-cpu-baseline > $O/streams_c${C}_$S.json 2> $O/streams_c${C}_$S.err || tail -3 $O/streams_c${C}_$S.err
+  timeout 900 python bench.py --config $C --full --no-cpu-baseline > $O/streams_c${C}_$S.json 2> $O/streams_c${C}_$S.err || tail -3 $O/streams_c${C}_$S.err
   python - $O/streams_c${C}_$S.json $C $S <<'PY'
 import json, sys
 try:

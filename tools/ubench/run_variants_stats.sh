@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 for v in "$@"; do
   if [ $v = default ]; then unset SMILEHIP_LIB; else export SMILEHIP_LIB=$R/tools/ubench/build/libsmilehip_$v.so; fi
   rm -rf /tmp/vs_$v
-  SMILEHIP_SERIAL=1 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/vs_$v -- python $R/bench.py $X --utts $U --steps 2 --warmup 1 --no-cpu-baseline > /tmp/vs_$v.json 2>/dev/null
+  SMILEHIP_SERIAL=1 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/vs_$v -- python $R/bench.py $X --utts $U --steps 2 --warmup 1 --full --no-cpu-baseline > /tmp/vs_$v.json 2>/dev/null
   echo "== $v  $(python -c "import json; r=json.loads(open('/tmp/vs_$v.json').read().strip().splitlines()[-1]); print('step_ms', round(r['ms_per_step'],3), 'accuracy', r['accuracy'].get('pass'))")"
   python - $(find /tmp/vs_$v -name '*kernel_stats.csv' | head -1) <<'PY'
 import csv, sys
