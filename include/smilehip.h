@@ -912,9 +912,17 @@ int smilehip_pitch_smoother_rows(smilehip_context *ctx, int32_t n_cand, float vo
                                  int64_t *d_written, void *stream);
 /* cFormantLpc::processVector (src/lld/formantLpc.cpp:192-290): nFormants = 5, saveFormants = saveBandwidths = 1, minF 50,
  * maxF 5450, no median filter / octave correction; roots of the LP polynomial by the reference's balanced companion-matrix
- * QR iteration (src/smileutil/zerosolve.cpp): 11 coefficients -> [5 frequencies | 5 bandwidths] */
+ * QR iteration (src/smileutil/zerosolve.cpp): 11 coefficients -> [5 frequencies | 5 bandwidths]. A row whose QR iteration gives
+ * up (70 iterations, e.g. on a NaN coefficient) keeps the previous row's folded roots wherever it found none, as the reference's
+ * roots member does; the first row has zeros before it. */
 int smilehip_formantlpc_frames(smilehip_plan *plan, const float *d_lpc, int64_t ld_src, float *d_dst, int64_t ld_dst,
                                int64_t n_frames, void *stream);
+/* The same with the carried roots across calls (frame-by-frame callers): d_state (optional, SMILEHIP_FORMANT_STATE_BYTES) holds
+ * the folded roots after a call's last row; with resume != 0 they are what the call's first row carries over. A call with rows
+ * writes it; the plan keeps a scratch of 16 bytes per 64 rows for the call (calls on one plan go one after the other). */
+#define SMILEHIP_FORMANT_STATE_BYTES 176
+int smilehip_formantlpc_rows(smilehip_plan *plan, const float *d_lpc, int64_t ld_src, float *d_dst, int64_t ld_dst,
+                             int64_t n_frames, void *d_state, int32_t resume, void *stream);
 /* cHarmonics::processVector (src/lld/harmonics.cpp:743-1031) with [gemapsv01b_harmonics]'s options: per row F0 (Hz; 0 =
  * unvoiced), the 10 values of level gemapsv01b_formants and the 513 magnitudes of the 60 ms frame -> 6 values
  * [HarmonicsToNoiseRatioACFLogdB, HarmonicDifferenceLogRelH1-H2, ..H1-A3, FormantAmplitudeByMaxHarmonicLogRelF0[1..3]] */

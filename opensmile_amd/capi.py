@@ -161,6 +161,7 @@ SYMBOLS = {
     "smilehip_specresample_frames": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp]),
     "smilehip_lpc_frames": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp]),
     "smilehip_formantlpc_frames": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp]),
+    "smilehip_formantlpc_rows": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _i32, _vp]),
     "smilehip_harmonics_frames": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp]),
     "smilehip_valbased_select_frames": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _i32, _f32, _i32, _i32, _i32, _i32, _f32, _vp, _i64, _vp, _vp]),
     "smilehip_jitter_stream_create": (C.c_int, [_vp, _dbl, _i64, _i64, _dbl, _dbl, _i32, C.POINTER(_vp)]),
@@ -392,8 +393,39 @@ def lpc_host(plan, x):
     return rows_op_host(plan.ctx, load().smilehip_lpc_frames, plan._h, [x], 11)
 
 
-def formantlpc_host(plan, lpc):
-    return rows_op_host(plan.ctx, load().smilehip_formantlpc_frames, plan._h, [lpc], 10)
+FORMANT_STATE_BYTES = 176     # SMILEHIP_FORMANT_STATE_BYTES: the folded roots carried from one call to the next
+
+
+def formantlpc_host(plan, lpc, cuts=None):
+    """cFormantLpc on the rows of lpc (n x 11) -> n x 10. cuts (optional): row indices at which the rows are split into
+    consecutive calls of smilehip_formantlpc_rows that carry the roots through a state buffer, as a frame-by-frame caller
+    does; the result is the one of a single call."""
+    if cuts is None:
+        return rows_op_host(plan.ctx, load().smilehip_formantlpc_frames, plan._h, [lpc], 10)
+    L = load()
+    ctx = plan.ctx
+    lpc = np.ascontiguousarray(lpc, dtype=np.float32)
+    n = lpc.shape[0]
+    out = np.zeros((n, 10), np.float32)
+    bounds = [0] + sorted(int(c) for c in cuts) + [n]
+    d_in, d_out, d_st = _vp(), _vp(), _vp()
+    _check(L.smilehip_alloc(ctx._h, max(lpc.nbytes, 4), C.byref(d_in)))
+    _check(L.smilehip_alloc(ctx._h, max(out.nbytes, 4), C.byref(d_out)))
+    _check(L.smilehip_alloc(ctx._h, FORMANT_STATE_BYTES, C.byref(d_st)))
+    try:
+        if lpc.nbytes:
+            _check(L.smilehip_copy_to_device(ctx._h, d_in, lpc.ctypes.data, lpc.nbytes, None))
+        for k in range(len(bounds) - 1):
+            a, b = bounds[k], bounds[k + 1]
+            _check(L.smilehip_formantlpc_rows(plan._h, d_in.value + a * lpc.shape[1] * 4, lpc.shape[1], d_out.value + a * 40, 10,
+                                              b - a, d_st, 1 if a > 0 else 0, None))
+        _check(L.smilehip_stream_synchronize(ctx._h, None))
+        if out.nbytes:
+            _check(L.smilehip_copy_to_host(ctx._h, out.ctypes.data, d_out, out.nbytes, None))
+    finally:
+        for d in (d_in, d_out, d_st):
+            L.smilehip_free(ctx._h, d)
+    return out
 
 
 def harmonics_host(plan, f0, formants, mag):

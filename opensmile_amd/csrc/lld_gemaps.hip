@@ -515,8 +515,10 @@ __device__ __forceinline__ void zs_balance_reg(ZsMat &m) {   // zerosolveBalance
   }
 }
 
-// zerosolveQRhelper, zerosolve.cpp:100-283. root: the lane's (re, im) pairs in LDS, element e at root[e * 64]
-__device__ __forceinline__ void zs_qr_reg(ZsMat &h, double *root) {
+// zerosolveQRhelper, zerosolve.cpp:100-283. root: the lane's (re, im) pairs in LDS, element e at root[e * 64]. Returns the
+// number of roots not found: 0 when the iteration converged; after giving up (70 iterations without a deflation), the slots
+// of the roots found so far (indices N .. kNC-1) hold them and the others what they held before, as in the reference.
+__device__ __forceinline__ int zs_qr_reg(ZsMat &h, double *root) {
   int N = kNC, nit = 0;
   double t = 0.0;
   bool live = true;                                        // false: all roots found, or given up after 70 iterations
@@ -658,20 +660,11 @@ __device__ __forceinline__ void zs_qr_reg(ZsMat &h, double *root) {
       }
     }
   }
+  return N;
 }
-}  // namespace
 
-// cFormantLpc::processVector (formantLpc.cpp:192-290), nFormants = 5, saveFormants = saveBandwidths = 1, no median filter /
-// octave correction. One thread per frame. When the QR iteration does not converge the reference goes on with what its
-// roots member held before (the previous frame's values); a frame here starts from zeros instead (not observed on speech).
-__global__ void __launch_bounds__(64) lld_gemaps_formants(GemapsParams G) {
-  const int64_t g = (int64_t)blockIdx.x * 64 + threadIdx.x;
-  if (g >= (G.op_mode ? G.op_rows : G.total_frames20)) return;
-  const float *lp = G.lpc + g * G.lpc_ld;
-  __shared__ double fm_roots[2 * kNC * 64];                              // the lanes' roots, element-major
-  double *roots = fm_roots + threadIdx.x;
-  double fc[5], bc[5];
-  for (int i = 0; i < 2 * kNC; ++i) GM_ROOT(roots, i) = 0.0;
+// One frame's LP coefficients -> roots (zerosolveSetCmatrix, balancing, QR); the return value is zs_qr_reg's
+__device__ __forceinline__ int fm_solve(const float *lp, double *roots) {
   ZsMat mat;
 #pragma unroll
   for (int i = 0; i < kNC; i++)
@@ -682,7 +675,13 @@ __global__ void __launch_bounds__(64) lld_gemaps_formants(GemapsParams G) {
 #pragma unroll
   for (int i = 0; i < kNC; i++) mat.a[i][kNC - 1] = -(double)(-lp[kNC - i - 1]) / 1.0;   // a[i] = -lpc[n-1-i], a[n] = 1
   zs_balance_reg(mat);
-  zs_qr_reg(mat, roots);
+  return zs_qr_reg(mat, roots);
+}
+
+// The roots folded into the unit circle in place (the reference's roots member keeps them folded), then the frame's
+// 5 frequencies | 5 bandwidths to o
+__device__ __forceinline__ void fm_fold_and_write(const GemapsParams &G, double *roots, float *o) {
+  double fc[5], bc[5];
   for (int i = 0; i < kNC; i++) {                                            // smileMath_complexIntoUnitCircle, smileUtil.c:992-1003
     const double re = GM_ROOT(roots, 2 * i), im = GM_ROOT(roots, 2 * i + 1);
     if (sqrt(re * re + im * im) > 1.0) {
@@ -696,6 +695,7 @@ __global__ void __launch_bounds__(64) lld_gemaps_formants(GemapsParams G) {
       GM_ROOT(roots, 2 * i) = R; GM_ROOT(roots, 2 * i + 1) = I;
     }
   }
+  if (!o) return;
   int n_found = 0;                                                           // smileDsp_lpcrootsToFormants, smileUtil.c:2019-2053
   {
     const double spPi = G.fm_T * M_PI, spPi2 = spPi * 2.0;
@@ -727,8 +727,74 @@ __global__ void __launch_bounds__(64) lld_gemaps_formants(GemapsParams G) {
         double t = fc[j]; fc[j] = fc[i]; fc[i] = t;
         t = bc[j]; bc[j] = bc[i]; bc[i] = t;
       }
-  float *o = G.formants + g * G.fm_ld;
   for (int i = 0; i < 5; i++) { o[i] = (float)fc[i]; o[5 + i] = (float)bc[i]; }
+}
+}  // namespace
+
+// cFormantLpc::processVector (formantLpc.cpp:192-290), nFormants = 5, saveFormants = saveBandwidths = 1, no median filter /
+// octave correction. One thread per frame.
+// When the QR iteration gives up (zerosolve.cpp:166-168; a NaN LP coefficient does, tests/test_gpu_formant_carry.py), the
+// reference writes only the roots it found into its roots member (zerosolve.cpp:337-341) and goes on with what that member
+// held: the previous frame's roots, already folded into the unit circle. Here every wave records which of its frames gave up
+// (G.fm_flags word 2w) and which of those had found some roots first (word 2w + 1); lld_gemaps_formants_fix then redoes the
+// flagged frames in stream order. The carry runs within an utterance (batch) or a call, and across calls through the optional
+// state of smilehip_formantlpc_rows; a frame that gives up with nothing before it starts from zeros.
+__global__ void __launch_bounds__(64) lld_gemaps_formants(GemapsParams G) {
+  const int64_t g = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (g >= (G.op_mode ? G.op_rows : G.total_frames20)) return;
+  const float *lp = G.lpc + g * G.lpc_ld;
+  __shared__ double fm_roots[2 * kNC * 64];                              // the lanes' roots, element-major
+  double *roots = fm_roots + threadIdx.x;
+  for (int i = 0; i < 2 * kNC; ++i) GM_ROOT(roots, i) = 0.0;
+  const int left = fm_solve(lp, roots);
+  const uint64_t gave_up = __ballot(left > 0), partial = __ballot(left > 0 && left < kNC);
+  if (threadIdx.x == 0) { G.fm_flags[2 * blockIdx.x] = gave_up; G.fm_flags[2 * blockIdx.x + 1] = partial; }
+  fm_fold_and_write(G, roots, G.formants + g * G.fm_ld);
+}
+
+// The frames lld_gemaps_formants flagged, redone in order. Thread w looks at the frames of word w; the first frame of each run
+// of flagged frames (a stream's first frame, or one whose predecessor converged) carries the run: it solves the predecessor again
+// (or takes the state / zeros at a stream's start), then for each frame of the run re-solves it on top of the carried roots if it
+// had found roots before giving up, folds them and writes the row. A run that crosses a word is its first frame's thread's.
+// state_pass (op mode, one thread): the folded roots of the last row to G.fm_state, for the next call (no rows written).
+namespace {
+__device__ __forceinline__ bool fm_bit(const uint64_t *flags, int64_t f, int which) {
+  return (flags[2 * (f >> 6) + which] >> (f & 63)) & 1;
+}
+}  // namespace
+__global__ void __launch_bounds__(64) lld_gemaps_formants_fix(GemapsParams G, int state_pass) {
+  const int64_t rows = G.op_mode ? G.op_rows : G.total_frames20;
+  const int64_t w = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (state_pass ? w != 0 : w >= (rows + 63) / 64) return;
+  const uint64_t *flags = G.fm_flags;
+  __shared__ double fm_roots[2 * kNC * 64];
+  double *R = fm_roots + threadIdx.x;
+  uint64_t heads = state_pass ? 1 : flags[2 * w];
+  while (heads) {
+    const int b = __builtin_ctzll(heads);
+    heads &= heads - 1;
+    int64_t h, s0 = 0, s1 = rows;                          // run's first frame, its stream's [first, end)
+    if (state_pass) {
+      h = rows;                                            // no run at the end: the last row is the one to solve
+      while (h > 0 && fm_bit(flags, h - 1, 0)) h--;
+    } else {
+      h = w * 64 + b;
+      if (!G.op_mode) {                                    // the utterance of frame h (frame_off20[u] <= h < frame_off20[u + 1])
+        int lo = 0, hi = G.n_utt20;
+        while (hi - lo > 1) { const int mid = (lo + hi) / 2; if (G.frame_off20[mid] <= h) lo = mid; else hi = mid; }
+        s0 = G.frame_off20[lo]; s1 = G.frame_off20[lo + 1];
+      }
+      if (h > s0 && fm_bit(flags, h - 1, 0)) continue;     // inside a run: its first frame's thread does it
+    }
+    for (int i = 0; i < 2 * kNC; ++i) GM_ROOT(R, i) = (h == s0 && G.op_mode && G.fm_resume) ? G.fm_state[i] : 0.0;
+    for (int64_t f = h > s0 ? h - 1 : h; f < s1; ++f) {
+      if (f < h || fm_bit(flags, f, 1)) (void)fm_solve(G.lpc + f * G.lpc_ld, R);
+      fm_fold_and_write(G, R, (f < h || state_pass) ? nullptr : G.formants + f * G.fm_ld);
+      if (f + 1 >= s1 || !fm_bit(flags, f + 1, 0)) break;
+    }
+    if (state_pass)
+      for (int i = 0; i < 2 * kNC; ++i) G.fm_state[i] = GM_ROOT(R, i);
+  }
 }
 #undef GM_MATC
 #undef GM_MATF
@@ -1243,7 +1309,15 @@ hipError_t launch_gemaps_lpc_rows(const GemapsParams &G, hipStream_t s) {
 }
 static hipError_t launch_formants(const GemapsParams &G, int64_t rows, hipStream_t s) {
   if (rows <= 0) return hipSuccess;
-  SMILEHIP_KLAUNCH(lld_gemaps_formants, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, s, G);
+  if (!G.fm_flags || (!G.op_mode && !G.frame_off20) || (G.op_mode && G.fm_resume && !G.fm_state)) return hipErrorInvalidValue;
+  const int64_t words = (rows + 63) / 64;
+  SMILEHIP_KLAUNCH(lld_gemaps_formants, dim3((unsigned)words), dim3(64), 0, s, G);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  SMILEHIP_KLAUNCH(lld_gemaps_formants_fix, dim3((unsigned)((words + 63) / 64)), dim3(64), 0, s, G, 0);
+  e = hipGetLastError();
+  if (e != hipSuccess || !G.op_mode || !G.fm_state) return e;
+  SMILEHIP_KLAUNCH(lld_gemaps_formants_fix, dim3(1), dim3(64), 0, s, G, 1);
   return hipGetLastError();
 }
 hipError_t launch_gemaps_formant_rows(const GemapsParams &G, hipStream_t s) {

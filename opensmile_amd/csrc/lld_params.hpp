@@ -219,6 +219,12 @@ struct GemapsParams {
   float *formants;                  // [total_frames20 x 10] 5 frequencies | 5 bandwidths
   int64_t total_frames20;
   double fm_T, fm_min, fm_max;      // sample period of the resampled signal, formant search range
+  uint64_t *fm_flags;               // [2 x ceil(frames / 64)] per 64 frames: those whose root solver gave up | those of them that had
+                                    //   found roots before (lld_gemaps_formants writes them, lld_gemaps_formants_fix reads them)
+  const int64_t *frame_off20;       // batch: [n_utt20 + 1] 20 ms frame offsets of the utterances (the root carry stays inside one)
+  int32_t n_utt20;
+  int32_t fm_resume;                // op mode: the first row's predecessor roots are fm_state's (else zeros)
+  double *fm_state;                 // op mode, optional: [22] the folded roots after the last row (read if fm_resume, then written)
   // ---- 60 ms chain ----
   double fsSec60;                   // frameSizeSec of the 60 ms spectrum level (frequency axis of cHarmonics)
   const float *pitch3;              // [total_frames60 x 3] F0final, F0finalLog, voicing (after the energy gate)

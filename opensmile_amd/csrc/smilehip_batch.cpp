@@ -149,7 +149,8 @@ extern "C" int smilehip_batch_create(smilehip_plan *plan, const int64_t *h_off, 
                   double(nf * 254 + nf60 * 14 + nfin * 36) * 4e-9);
     }
     std::vector<int32_t> zp(size_t(n_utt ? n_utt : 1), 0);
-    if ((rc = b->d_pending_j.upload(zp)) || (rc = b->d_harm_ctl.upload(std::vector<int32_t>(2, 0)))) {
+    if ((rc = b->d_pending_j.upload(zp)) || (rc = b->d_harm_ctl.upload(std::vector<int32_t>(2, 0))) ||
+        (rc = b->d_fm_flags.upload(std::vector<uint64_t>(2 * ((nf + 63) / 64), 0)))) {
       delete b;
       return rc;
     }
@@ -793,6 +794,7 @@ static void fill_gemaps_params(const smilehip_plan *plan, const smilehip_batch *
   G.raw20 = b->d_raw20.p; G.spec220 = b->d_spec220.p;
   G.lpc = b->d_lpc.p; G.formants = b->d_formants.p;
   G.total_frames20 = b->total_frames;
+  G.fm_flags = b->d_fm_flags.p; G.frame_off20 = b->d_frame_off.p; G.n_utt20 = b->n_utt;
   G.pitch3 = b->d_pitch3.p; G.jit4 = b->d_jit4.p; G.shim_db = b->d_shim.p; G.harm6 = b->d_harm6.p;
   G.frame_off60 = fb->d_frame_off.p;
   G.tile60 = fb->d_tile_rec.p;

@@ -55,17 +55,30 @@ extern "C" int smilehip_lpc_frames(smilehip_plan *p, const float *d_x, int64_t l
   return SMILEHIP_OK;
 }
 
-extern "C" int smilehip_formantlpc_frames(smilehip_plan *p, const float *d_lpc, int64_t ld_src, float *d_dst, int64_t ld_dst,
-                                          int64_t n_frames, void *stream) {
-  int rc = need_egemaps(p, "smilehip_formantlpc_frames");
+extern "C" int smilehip_formantlpc_rows(smilehip_plan *p, const float *d_lpc, int64_t ld_src, float *d_dst, int64_t ld_dst,
+                                        int64_t n_frames, void *d_state, int32_t resume, void *stream) {
+  int rc = need_egemaps(p, "smilehip_formantlpc_rows");
   if (rc) return rc;
-  if ((rc = check_rows(d_lpc, d_dst, ld_src, ld_dst, n_frames, 11, 10, "smilehip_formantlpc_frames"))) return rc;
+  if ((rc = check_rows(d_lpc, d_dst, ld_src, ld_dst, n_frames, 11, 10, "smilehip_formantlpc_rows"))) return rc;
+  if (resume && !d_state) return fail(SMILEHIP_ERR_INVALID, "smilehip_formantlpc_rows: resume without a state buffer");
+  if (n_frames == 0) return SMILEHIP_OK;
+  const size_t words = 2 * size_t((n_frames + 63) / 64);
+  if (p->d_fm_flags.n < words) {                         // grown on demand; the old block may still be in use on the stream
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    if ((rc = p->d_fm_flags.upload(std::vector<uint64_t>(words, 0)))) return rc;
+  }
   GemapsParams G;
   gemaps_plan_consts(p, G);
   G.op_mode = 1; G.lpc = const_cast<float *>(d_lpc); G.lpc_ld = ld_src; G.formants = d_dst; G.fm_ld = ld_dst; G.op_rows = n_frames;
+  G.fm_flags = p->d_fm_flags.p; G.fm_state = static_cast<double *>(d_state); G.fm_resume = resume ? 1 : 0;
   hipError_t e = launch_gemaps_formant_rows(G, (hipStream_t)stream);
   if (e != hipSuccess) return fail(SMILEHIP_ERR_HIP, "cFormantLpc kernel launch failed: %s", hipGetErrorString(e));
   return SMILEHIP_OK;
+}
+
+extern "C" int smilehip_formantlpc_frames(smilehip_plan *p, const float *d_lpc, int64_t ld_src, float *d_dst, int64_t ld_dst,
+                                          int64_t n_frames, void *stream) {
+  return smilehip_formantlpc_rows(p, d_lpc, ld_src, d_dst, ld_dst, n_frames, nullptr, 0, stream);
 }
 
 extern "C" int smilehip_harmonics_frames(smilehip_plan *p, const float *d_f0, const float *d_formants, int64_t ld_formants,

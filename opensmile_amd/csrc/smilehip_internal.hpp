@@ -158,6 +158,7 @@ struct smilehip_plan {
   float rasta_iir = 0.f, rasta_fir[5] = {0, 0, 0, 0, 0};
   // eGeMAPS chain: cSpecResample's tables (transposed), cSpectral's band-slope edges and frequency range
   DevBuf<float> d_rs_cos, d_rs_sin;
+  DevBuf<uint64_t> d_fm_flags;              // smilehip_formantlpc_rows: GemapsParams::fm_flags of the largest call so far
   int32_t gm_sl_iL[2] = {0, 0}, gm_sl_iR[2] = {0, 0}, gm_rng_lo = 0, gm_rng_hi = 0, gm_ar_n1 = 0, gm_ar_n2 = 0;
   double gm_sl_wL[2] = {0, 0}, gm_sl_wR[2] = {0, 0}, gm_sl_Nind[2] = {0, 0};
   float gm_spec_floor = 0.f, gm_log_spec_floor = 0.f, gm_log_spec_factor = 0.f;
@@ -216,6 +217,7 @@ struct smilehip_batch {
   DevBuf<float> d_raw20, d_spec220, d_lpc, d_formants, d_pitch3, d_shim, d_harm6, d_func_in;
   DevBuf<int32_t> d_pending_j;
   DevBuf<int32_t> d_harm_ctl;             // eGeMAPS chain: lld_gemaps_harm's tile counter
+  DevBuf<uint64_t> d_fm_flags;            // eGeMAPS chain: cFormantLpc's frames whose root solver gave up (GemapsParams::fm_flags)
   DevBuf<int64_t> d_fin_off;              // [n_utt+1] rows of func_in: T20 + 1 per utterance with a 60 ms frame
   std::vector<int64_t> h_fin_off;
   bool gm_ran = false;

@@ -82,9 +82,12 @@ class cHipLpc : public BlockVP<cLpc> {
   }
 };
 
-// cFormantLpc::processVector (src/lld/formantLpc.cpp:192-290): 5 formants + bandwidths from 11 LP coefficients at 11 kHz
+// cFormantLpc::processVector (src/lld/formantLpc.cpp:192-290): 5 formants + bandwidths from 11 LP coefficients at 11 kHz. The roots
+// the component carries from frame to frame (a frame whose root solver gives up keeps them) live on the device between ticks.
 class cHipFormantLpc : public BlockVP<cFormantLpc> {
   FrameIO io_;
+  DevBytes state_;
+  bool started_ = false;
   bool cpu_warned_ = false;
   int usable_ = -1;
  protected:
@@ -103,7 +106,9 @@ class cHipFormantLpc : public BlockVP<cFormantLpc> {
     }
     io_.ensure(Nsrc, Ndst);
     io_.up(src, Nsrc);
-    check(smilehip_formantlpc_frames(gemaps_plan(0, (long)getDouble("maxF")), io_.d_in, Nsrc, io_.d_out, Ndst, g_blk.n, nullptr));
+    check(smilehip_formantlpc_rows(gemaps_plan(0, (long)getDouble("maxF")), io_.d_in, Nsrc, io_.d_out, Ndst, g_blk.n,
+                                   state_.ensure(SMILEHIP_FORMANT_STATE_BYTES), started_ ? 1 : 0, nullptr));
+    if (g_blk.n > 0) started_ = true;
     io_.down(dst, Ndst);
     g_frames[19] += g_blk.n;
     return (int)Ndst;

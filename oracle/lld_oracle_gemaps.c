@@ -411,7 +411,9 @@ static int zs_qr(double *h, long nc, double *root)                 /* zerosolveQ
  * octaveCorrection = 0: lpc (n_lpc coefficients) -> dst [nf frequencies | nf bandwidths]; T = sample period of the
  * resampled signal (cSpecResample::configureWriter sets basePeriod = 1 / targetFs). When the QR iteration does not
  * converge the reference goes on with whatever the roots array holds (zerosolve.cpp:337-341): `roots` carries it over
- * from frame to frame like the reference's member does. */
+ * from frame to frame like the reference's member does -- the previous frame's roots, folded into the unit circle, in
+ * every slot the frame found none. A NaN LP coefficient makes the iteration give up
+ * (tests/test_oracle_pin_formant_carry.py pins this on the binary, tests/test_gpu_formant_carry.py holds the device to it). */
 void lldo_formant_lpc(const float *lpc_in, int n_lpc, int nf, double T, double min_f, double max_f, double *roots,
                       float *dst)
 {
