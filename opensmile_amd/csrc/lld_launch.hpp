@@ -31,6 +31,7 @@ struct Fast512Host {
   int mel_conflict_steps = 0;   // LDS bank model: extra cycles of the mel power reads per step set (0 = conflict-free)
   float mel_scale = 1.0f;
   int max_blocks = 512;     // resident blocks of the fast kernel (2 per CU), set from the device
+  bool force_padded = false;  // SMILEHIP_MFCC512_FORCE_PADDED=1 at plan time: lld_mfcc512_padded even at pad_left = 0 (tests)
 };
 bool fast512_applicable(int Nfft, int N);
 int fast512_tile_frames();

@@ -172,9 +172,39 @@ __device__ __forceinline__ float dpp_f(float v) {
 // SGPRs: nothing to spill (a spill reload would put an s_waitcnt vmcnt(0) behind the loads and wait out the whole memory
 // latency in every pass). Samples outside a frame meet a zero of the window table and every stored frame lies inside
 // its utterance, so out-of-range addresses are only clamped into the buffer (wave-uniform branch, first / last span).
-template <int MP, bool ALIGNED>
+//
+// PREEMPH: the predecessor x[2n - 1] of pair n's even sample is the neighbour lane's odd sample (DPP row_ror:1; lane 0 takes lane
+// 15's of the register one pair down). (round 7, measured and NOT taken) -DSMILEHIP_MFCC512_PRED_LOADS loads it instead: a third,
+// sign-extending 16-bit load per m (byte offset -2; the sample in front of the buffer is the offset's wrap-around and reads as zero)
+// and one 32-bit v_cvt_f32_i32 where the DPP form takes a DPP move and a select, both 64-bit encoded -- 849 -> 803 VALU instructions
+// per pass with the other round-7 changes, but the launch was 1.7 % SLOWER than without it (0.3641 against 0.3580 ms per 998 000
+// frames, three A/B pairs): thirteen more vector-memory instructions per pass cost more than the issue cycles they save.
+#ifdef SMILEHIP_MFCC512_PRED_LOADS
+#ifdef SMILEHIP_MFCC512_GLOBAL_LOADS
+#error "SMILEHIP_MFCC512_GLOBAL_LOADS loads no predecessor samples"
+#endif
+constexpr bool kPredLoads = true;
+#else
+constexpr bool kPredLoads = false;
+#endif
+// (round 7, measured and NOT taken) -DSMILEHIP_MFCC512_B16_SAMPLES: dword-aligned input read with the unaligned form's two 16-bit
+// loads per pair as well (32-bit v_cvt_f32_i32 instead of the 64-bit SDWA conversions). Alone on top of the kept form: 821 VALU
+// instructions, 129 of them 64-bit, 127 VGPRs, no scratch; its replayed VALU stream is shorter (0.2931 against 0.3022 ms per 998 000
+// frames) but the launch is 4 % SLOWER (0.3749 against 0.3605 ms, three A/B rounds on one box): 26 buffer loads per pass instead of
+// 13 for the same bytes. (Stacked on the predecessor loads the build spilled -- 128 VGPRs, scratch reloads in the pass loop -- and
+// its 0.4957 ms measures that.)
+#ifdef SMILEHIP_MFCC512_B16_SAMPLES
+#ifdef SMILEHIP_MFCC512_GLOBAL_LOADS
+#error "SMILEHIP_MFCC512_GLOBAL_LOADS loads dwords for aligned input: it cannot be combined with SMILEHIP_MFCC512_B16_SAMPLES"
+#endif
+constexpr bool kB16Samples = true;
+#else
+constexpr bool kB16Samples = false;
+#endif
+template <int MP, bool ALIGNED, bool PREEMPH>
 struct FrameRegs {
-  uint32_t v[ALIGNED ? MP : 2 * MP];
+  uint32_t v[ALIGNED && !kB16Samples ? MP : 2 * MP];
+  uint32_t p[PREEMPH && kPredLoads ? MP : 1];        // x[2n - 1], sign-extended
 };
 
 // (round 6) The loads are BUFFER loads: a wave-uniform resource descriptor (base = the pass's first sample, size = what is left of the
@@ -183,9 +213,9 @@ struct FrameRegs {
 // replaces the clamped-address branch: a read behind the end of the buffer (or in front of it: the offset wraps to a huge unsigned
 // value) returns zero, which is as good as the clamped sample -- such samples meet a zero of the window table or belong to a frame
 // that is not stored. -DSMILEHIP_MFCC512_GLOBAL_LOADS builds the round-5 form (A/B aid).
-template <int MP, bool ALIGNED>
+template <int MP, bool ALIGNED, bool PREEMPH>
 __device__ __forceinline__ void pcm_prefetch(const int16_t *pcm, int64_t pcm_total, int64_t base, int H, int lane,
-                                             FrameRegs<MP, ALIGNED> &R) {
+                                             FrameRegs<MP, ALIGNED, PREEMPH> &R) {
 #ifndef SMILEHIP_MFCC512_GLOBAL_LOADS
   const int64_t b0 = base < 0 ? 0 : base;                // (negative only for the buffer's first frames under symmetric zero padding)
   int64_t left = (pcm_total - b0) * 2;                   // bytes behind the descriptor's base
@@ -193,9 +223,13 @@ __device__ __forceinline__ void pcm_prefetch(const int16_t *pcm, int64_t pcm_tot
   const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<int16_t *>(pcm + b0), 0, (int)(uint32_t)left, 0x00020000);
   uint32_t lo = ((uint32_t)(lane >> 4) * (uint32_t)H + 2u * (uint32_t)(lane & 15)) * 2u + (uint32_t)((base - b0) * 2);
   asm volatile("" : "+v"(lo));                           // opaque per call: no hoisted per-m offset registers
+  uint32_t lo_p = lo - 2u;                               // the predecessor of pair 0 (m = 0 only: the immediate offset is unsigned)
+  if (PREEMPH && kPredLoads) asm volatile("" : "+v"(lo_p));
 #pragma unroll
   for (int m = 0; m < MP; ++m) {
-    if (ALIGNED) {
+    if (PREEMPH && kPredLoads)
+      R.p[m] = (uint32_t)(int32_t)(int16_t)__builtin_amdgcn_raw_buffer_load_b16(rsrc, m == 0 ? (int)lo_p : (int)lo + 64 * m - 2, 0, 0);
+    if (ALIGNED && !kB16Samples) {
       R.v[m] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)lo + 64 * m, 0, 0);
     } else {
       R.v[2 * m] = (uint32_t)(int32_t)(int16_t)__builtin_amdgcn_raw_buffer_load_b16(rsrc, (int)lo + 64 * m, 0, 0);
@@ -272,8 +306,12 @@ __device__ unsigned long long g_phase[16];
 // acceleration cells of the final rows. The expressions and the index clamps are lld_chain_tiled's (lld_kernels.hip: chain_op,
 // level 1 has T + 2 rows, all of which level 2 reads as data), so the values equal the separate kernel's bit for bit
 // (tests/test_gpu_mfcc.py::test_fused_delta_equals_window_chain). Tiles are FTileRec (lld_params.hpp).
-template <int MP, bool PREEMPH, bool USE_POWER, bool ALIGNED, bool PLP, int UC, bool DELTA = false>
-__global__ void __launch_bounds__(kWavesPerBlock * 64, 4) lld_mfcc512(LldParams P, Fast512Tables F) {
+// PAD0 (round 7): the frame's first sample is pair 0's even sample (pad_left = 0: every geometry without zeroPadSymmetric), so
+// R2's first-sample fix-up y[0] = (1-k) x[0] is one select at m = 0 instead of one per m (the general form's sample position is
+// a runtime value). The kernels lld_mfcc512 (PAD0, and every instance without pre-emphasis) and lld_mfcc512_padded (any pad_left,
+// instantiated with PREEMPH only) below share this body.
+template <int MP, bool PREEMPH, bool USE_POWER, bool ALIGNED, bool PLP, int UC, bool DELTA, bool PAD0>
+__device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast512Tables &F) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int lane = threadIdx.x & 63;
   // wave-uniform by construction; tell the compiler so that everything derived from it
@@ -325,7 +363,7 @@ __global__ void __launch_bounds__(kWavesPerBlock * 64, 4) lld_mfcc512(LldParams 
   const uint32_t out_off = (uint32_t)(g * (int)P.ld_out + j) * 4u;
   const uint32_t out_off_d = out_off + (uint32_t)P.n_mfcc * 4u;
   const uint32_t out_off_dd = out_off + (uint32_t)P.n_mfcc * 8u;
-  const float kpre = P.de ? -P.k : P.k;        // y = x - kpre * x'  (de: y = x + k x')
+  const float nkpre = P.de ? P.k : -P.k;       // y = x + nkpre * x'  (de: y = x + k x'), wave-uniform: the FMAs below stay v_fmac
   const int m0 = P.pad_left >> 5, j0 = (P.pad_left >> 1) & 15;       // where sample 0 of a frame sits
   float *pb_k = s_pb + pb_pos(j);              // my bins k = j + 16 q sit 24 q floats further on
   float *pb_m = s_pb + pb_pos(256 - j);        // their mirror images 256 - k sit 24 q floats back
@@ -360,8 +398,8 @@ __global__ void __launch_bounds__(kWavesPerBlock * 64, 4) lld_mfcc512(LldParams 
   int64_t nxt_samp0 = cur_samp0;
   if (has_next) nxt_samp0 = recs[tile + tile_stride].samp0;
   int tp = 0;                                          // first frame of the pass, relative to the tile
-  FrameRegs<MP, ALIGNED> R;
-  pcm_prefetch<MP, ALIGNED>(P.pcm, P.pcm_total, cur_samp0 - P.pad_left, P.H, lane, R);
+  FrameRegs<MP, ALIGNED, PREEMPH> R;
+  pcm_prefetch<MP, ALIGNED, PREEMPH>(P.pcm, P.pcm_total, cur_samp0 - P.pad_left, P.H, lane, R);
   unsigned char *pend_row = nullptr;                   // deferred store of the previous pass (wave-uniform row base)
   float pend_val = 0.0f;
   bool pend_live = false;
@@ -442,11 +480,12 @@ __global__ void __launch_bounds__(kWavesPerBlock * 64, 4) lld_mfcc512(LldParams 
     float re[16], im[16];
     {
       float tprev = 0.0f;                        // odd sample of pair 15 + 16 (m-1), as lane j = 0 needs it
+      (void)tprev;
 #pragma unroll
       for (int m = 0; m < 16; ++m) {
         if (m < MP) {
           float a, b;
-          if constexpr (ALIGNED) {
+          if constexpr (ALIGNED && !kB16Samples) {
             a = (float)(int16_t)(R.v[m] & 0xffffu);
             b = (float)(int16_t)(R.v[m] >> 16);
           } else {
@@ -455,21 +494,27 @@ __global__ void __launch_bounds__(kWavesPerBlock * 64, 4) lld_mfcc512(LldParams 
           }
           float ya = a, yb = b;
           if (PREEMPH) {
-            const float t = dpp_f<0x121>(b);     // row_ror:1 -- lane j sees the odd sample of pair j-1 (lane 0: of lane 15)
-            const float pa = (j == 0) ? tprev : t;
-            tprev = t;
+            float pa;
+            if constexpr (kPredLoads) {
+              pa = (float)(int32_t)R.p[m];         // x[2n - 1] (SMILEHIP_MFCC512_PRED_LOADS)
+            } else {
+              const float t = dpp_f<0x121>(b);     // row_ror:1 -- lane j sees the odd sample of pair j-1 (lane 0: of lane 15)
+              pa = (j == 0) ? tprev : t;
+              tprev = t;
+            }
 #ifndef SMILEHIP_MFCC512_PREEMPH_TWO_ROUNDINGS
             // (round 6) one rounding where the reference has two (preemphasis.cpp: x - k x' as a product and a difference): 26 vector
             // instructions fewer per pass, 0.3745 -> 0.3665 ms per 998 000 frames, and the distance to the reference went DOWN
             // (per-frame-scaled 1.048e-6 -> 1.041e-6, max abs 1.56e-4 -> 1.49e-4: the fused form is the exact difference rounded once).
             // This kernel's contract is the 1e-5 gate; the reference's own rounding sequence is lld_mfcc_generic's.
-            ya = fmaf(-kpre, pa, a);
-            yb = fmaf(-kpre, a, b);
+            // (round 7) yb first: then both are v_fmac (the addend is the destination, -k an SGPR operand), no VOP3 v_fma_f32.
+            yb = fmaf(nkpre, a, b);
+            ya = fmaf(nkpre, pa, a);
 #else
-            ya = a - kpre * pa;
-            yb = b - kpre * a;
+            yb = b + nkpre * a;
+            ya = a + nkpre * pa;
 #endif
-            if (m == m0 && j == j0) ya = P.one_minus_k * a;      // y[0] = (1-k) x[0]
+            if (PAD0 ? (m == 0 && j == 0) : (m == m0 && j == j0)) ya = P.one_minus_k * a;      // y[0] = (1-k) x[0]
           }
           const float2 w = s_win[m * 16 + j];
           re[m] = ya * w.x;
@@ -611,7 +656,7 @@ __global__ void __launch_bounds__(kWavesPerBlock * 64, 4) lld_mfcc512(LldParams 
     const bool more = !advance || has_next;
     if (advance) ntp = 0;
     if (more)
-      pcm_prefetch<MP, ALIGNED>(P.pcm, P.pcm_total, (advance ? nxt_samp0 : cur_samp0) + (int64_t)ntp * P.H - P.pad_left, P.H, lane, R);
+      pcm_prefetch<MP, ALIGNED, PREEMPH>(P.pcm, P.pcm_total, (advance ? nxt_samp0 : cur_samp0) + (int64_t)ntp * P.H - P.pad_left, P.H, lane, R);
 
     PHASE(7);                                   // prefetch issue
     // ------------------------------------------------------------ mel (R6)
@@ -708,6 +753,15 @@ __global__ void __launch_bounds__(kWavesPerBlock * 64, 4) lld_mfcc512(LldParams 
   PHASE_FLUSH;
 }
 
+template <int MP, bool PREEMPH, bool USE_POWER, bool ALIGNED, bool PLP, int UC, bool DELTA = false>
+__global__ void __launch_bounds__(kWavesPerBlock * 64, 4) lld_mfcc512(LldParams P, Fast512Tables F) {
+  lld_mfcc512_body<MP, PREEMPH, USE_POWER, ALIGNED, PLP, UC, DELTA, true>(P, F);
+}
+template <int MP, bool PREEMPH, bool USE_POWER, bool ALIGNED, bool PLP, int UC, bool DELTA = false>
+__global__ void __launch_bounds__(kWavesPerBlock * 64, 4) lld_mfcc512_padded(LldParams P, Fast512Tables F) {
+  lld_mfcc512_body<MP, PREEMPH, USE_POWER, ALIGNED, PLP, UC, DELTA, false>(P, F);
+}
+
 #ifdef SMILEHIP_PHASE_TIMING
 extern "C" int smilehip_debug_phase(unsigned long long *out16, int reset) {
   if (out16 && hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_phase), sizeof(unsigned long long) * 16) != hipSuccess) return -1;
@@ -737,6 +791,8 @@ int fast512_build_host(const smilehip_lld_config &cfg, const Geometry &geo, cons
   const int H = (int)geo.H, N = (int)geo.N;
   if (mel.n_bands > 27 || dct.n_mfcc > 16 || cfg.win_offset != 0.0 || (pad_left & 1) || (H & 1) || H < 2) return -1;
   h.mp = (pad_left + N) <= 13 * 32 ? 13 : 16;
+  const char *fp = getenv("SMILEHIP_MFCC512_FORCE_PADDED");
+  h.force_padded = fp != nullptr && fp[0] == '1';
   h.tw256.resize(256);
   for (int k1 = 0; k1 < 16; ++k1)
     for (int j = 0; j < 16; ++j) {
@@ -894,6 +950,24 @@ int fast512_build_host(const smilehip_lld_config &cfg, const Geometry &geo, cons
   return 0;
 }
 
+template <int MP, bool PREEMPH, bool USE_POWER, bool ALIGNED, bool PLP, int UC, bool DELTA = false>
+static hipError_t launch_mfcc512_one(bool padded, unsigned grid, size_t lds, hipStream_t s, const LldParams &P, const Fast512Tables &F) {
+  if constexpr (PREEMPH) {
+    if (padded) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&lld_mfcc512_padded<MP, PREEMPH, USE_POWER, ALIGNED, PLP, UC, DELTA>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return e;
+      SMILEHIP_KLAUNCH((lld_mfcc512_padded<MP, PREEMPH, USE_POWER, ALIGNED, PLP, UC, DELTA>), dim3(grid), dim3(kWavesPerBlock * 64), lds, s, P, F);
+      return hipSuccess;
+    }
+  }
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&lld_mfcc512<MP, PREEMPH, USE_POWER, ALIGNED, PLP, UC, DELTA>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  SMILEHIP_KLAUNCH((lld_mfcc512<MP, PREEMPH, USE_POWER, ALIGNED, PLP, UC, DELTA>), dim3(grid), dim3(kWavesPerBlock * 64), lds, s, P, F);
+  return hipSuccess;
+}
+
 hipError_t launch_mfcc512(const LldParams &P, const Fast512Tables &F, const Fast512Host &h, bool aligned, bool fused_delta, hipStream_t s) {
   const int shared_floats = 256 * 2 + h.mp * 16 * 2 + 256 * 2 + h.mel_units * 16 * 8 + 16 * 28 + 48;
   const size_t lds = sizeof(float) * (size_t(shared_floats) + size_t(kWavesPerBlock) * kWaveFloats);
@@ -904,12 +978,13 @@ hipError_t launch_mfcc512(const LldParams &P, const Fast512Tables &F, const Fast
   if (const char *e = getenv("SMILEHIP_DEBUG_GRID")) grid = (unsigned)atoi(e);
 #endif
   bool launched = false;
+  // pad_left = 0 (frame sample 0 in lane 0, register 0): lld_mfcc512; symmetric zero padding: lld_mfcc512_padded (PREEMPH only:
+  // without pre-emphasis there is no fix-up and the two kernels are the same code)
+  const bool padded = P.pad_left != 0 || h.force_padded;
 #define SMILEHIP_LAUNCH(...)                                                                                    \
   {                                                                                                             \
-    const void *fn = reinterpret_cast<const void *>(&lld_mfcc512<__VA_ARGS__>);                                 \
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);               \
+    hipError_t e = launch_mfcc512_one<__VA_ARGS__>(padded, grid, lds, s, P, F);                                 \
     if (e != hipSuccess) return e;                                                                              \
-    SMILEHIP_KLAUNCH((lld_mfcc512<__VA_ARGS__>), dim3(grid), dim3(kWavesPerBlock * 64), lds, s, P, F);        \
     launched = true;                                                                                            \
   }
 #define SMILEHIP_MATCH(MPV, PE, UP, AL, PL, UCV)                                                                \
