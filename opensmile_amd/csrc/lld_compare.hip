@@ -17,6 +17,7 @@
 
 #include <cstdlib>
 
+#include "batch_layout.hpp"
 #include "lld_blocks.hpp"
 #include "lld_fft.hpp"
 #include "lld_blocks_compare.hpp"
@@ -28,7 +29,7 @@
 namespace smilehip {
 
 namespace {
-constexpr int kRun = 8;          // frames per run when the caller names none (the flux needs the previous frame's magnitudes)
+constexpr int kRun = kRunFramesMin;   // frames per run when the caller names none (the flux needs the previous frame's magnitudes)
 
 }  // namespace
 
@@ -630,14 +631,6 @@ hipError_t launch_compare(const LldParams &P, const CompareParams &Q, int n_runs
     SMILEHIP_KLAUNCH(lld_compare_groupA, dim3((unsigned)((total_rows * 4 + 255) / 256)), dim3(256), 0, s, P.frame_off,
                        d_row_off, P.n_utt, total_rows, Q, d_out, ld_out, de_col);
   return hipGetLastError();
-}
-
-// Frames per run for a batch of `total_frames` 20 ms frames: a run costs one transform more than its frames (the warm-up frame),
-// 12.5 % at 8; the longest of 8 / 16 / 32 / 64 that still leaves >= 65 536 runs (21 per wave slot of the device).
-int compare_run_frames(int64_t total_frames) {
-  int L = kRun;
-  while (L < 64 && total_frames / (2 * L) >= 65536) L *= 2;
-  return L;
 }
 
 }  // namespace smilehip

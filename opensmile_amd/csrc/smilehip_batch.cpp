@@ -1,13 +1,130 @@
 // libsmilehip, C ABI part 3: batches (packed utterances), the fused chain runs, functionals, timing.
 #include "smilehip_internal.hpp"
+#include "batch_layout.hpp"
 
 // ------------------------------------------------------------------ batch
+// A batch is (1) its layout -- host index arithmetic, batch_layout.hpp --, (2) that layout's index vectors on the device and
+// (3) the scratch matrices of its plan's chain kind, one alloc_*_scratch below per kind. The order and the sizes of the device
+// allocations are part of the behaviour: the block cache behind DevBuf hands blocks out by exact size.
 smilehip_batch::~smilehip_batch() { delete f0_batch; }
 
-static inline bool compare_ab_like(const smilehip_plan *p) {
-  return p->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE_AB || p->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE;
+static inline bool mfcc_like(const smilehip_plan *p) {
+  return p->cfg.chain_kind == SMILEHIP_CHAIN_MFCC || p->cfg.chain_kind == SMILEHIP_CHAIN_PLP;
 }
-static inline bool is_egemaps(const smilehip_plan *p) { return p->cfg.chain_kind == SMILEHIP_CHAIN_EGEMAPS; }
+
+static BatchLayoutSpec layout_spec(const smilehip_plan *plan) {
+  const smilehip_lld_config &c = plan->cfg;
+  BatchLayoutSpec s;
+  s.chain_kind = c.chain_kind;
+  s.N = plan->geo.N; s.H = plan->geo.H; s.period = plan->geo.period;
+  s.row_extra = plan_row_extra(plan);
+  s.fused_delta_eligible = plan->use_fast && mfcc_like(plan) && c.n_delta == 2 && c.delta_win == 2 && !c.append_log_energy && !c.cms &&
+                           !getenv("SMILEHIP_NO_FUSED_DELTA");
+  s.fast_slots = std::max<int64_t>(1, plan->fast.max_blocks) * 8;
+  s.tile_frames = plan->use_fast ? fast512_tile_frames() : (c.chain_kind == SMILEHIP_CHAIN_COMPARE_F0 ? f0_tile_frames() : (int64_t(1) << 40));
+  s.dtile_rows = chain_tile_rows(); s.short_T = chain_short_max(); s.jitter_chunk = jitter_chunk_frames();
+  if (const char *rf = getenv("SMILEHIP_RUN_FRAMES")) { const int v = atoi(rf); if (v >= 1 && v <= 4096) s.run_frames_override = v; }   // A/B switch
+  return s;
+}
+
+static inline size_t at_least_one(int64_t n) { return size_t(n ? n : 1); }
+
+// MFCC / PLP: the delta-fused fast kernel's tiles, or -- with deltas to follow and no fused run -- the compact static block
+static int alloc_mfcc_scratch(const smilehip_plan *plan, smilehip_batch *b, const BatchLayout &L) {
+  b->n_ftiles = (int32_t)L.ftiles.size();
+  if (b->n_ftiles) return b->d_ftile_rec.upload(L.ftiles);
+  if (plan->cfg.n_delta > 0 && b->total_frames > 0 && b->d_static.alloc(size_t(b->total_frames) * size_t(plan_n_static(plan))))
+    return fail(SMILEHIP_ERR_HIP, "hipMalloc of the static-block scratch failed");
+  return SMILEHIP_OK;
+}
+
+static int alloc_is09_scratch(smilehip_batch *b, const BatchLayout &L) {
+  int rc;
+  if (b->total_frames > 0 && (rc = b->d_frame_utt.upload(L.frame_utt))) return rc;
+  if (b->d_raw16.alloc(size_t(b->total_frames) * 16)) return fail(SMILEHIP_ERR_HIP, "hipMalloc of the IS09 scratch matrix failed");
+  return SMILEHIP_OK;
+}
+
+static int alloc_compare_ab_scratch(smilehip_batch *b, const BatchLayout &L) {
+  int rc;
+  b->n_runs = (int32_t)L.run_utt.size();
+  if ((rc = b->d_run_utt.upload(L.run_utt)) || (rc = b->d_run_t0.upload(L.run_t0))) return rc;
+  const size_t nf = at_least_one(b->total_frames);
+  if (b->d_rawA.alloc(nf * 4) || b->d_rawB.alloc(nf * 55) || b->d_mel1.alloc(nf * 26) || b->d_b_extra.alloc(at_least_one(b->n_utt) * 110))
+    return fail(SMILEHIP_ERR_HIP, "hipMalloc of the ComParE scratch matrices failed");
+  (void)hipMemset(b->d_rawA.p, 0, nf * 4 * sizeof(float));
+  return SMILEHIP_OK;
+}
+
+static int alloc_f0_scratch(const smilehip_plan *plan, smilehip_batch *b, const BatchLayout &L) {
+  const size_t nf = at_least_one(b->total_frames);
+  if (b->d_shs.alloc(nf * 21) || b->d_e60.alloc(nf)) return fail(SMILEHIP_ERR_HIP, "hipMalloc of the F0 scratch matrices failed");
+  const size_t nab = (size_t)std::max<int64_t>(f0_scratch_doubles(b->n_tiles, (int)plan->geo.K), 1);
+  if (b->d_f0_ab.alloc(nab)) return fail(SMILEHIP_ERR_HIP, "hipMalloc of the F0 row scratch (%zu MB) failed", nab * sizeof(double) >> 20);
+  // SMILEHIP_F0_PIPE=1 (round 6, measured and NOT the default): a second set of rows for the chunk pipeline (F0Pipe). Bit-identical
+  // (tests/test_gpu_f0_pipe.py) and no faster: config 4 243.4 ms piped against 241.0 ms chunk after chunk, config 5 1087 against
+  // 1081 -- side by side the three kernels stretch (spec 39 -> 102 ms, cand 36 -> 45, sweep 26 -> 38 summed) by what they gain;
+  // the idle issue slots their counters show are not slots another kernel's waves can use.
+  static const bool pipe_on = [] { const char *e = getenv("SMILEHIP_F0_PIPE"); return e && e[0] == '1'; }();
+  if (pipe_on && b->n_tiles > f0_chunk_tiles()) {
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b / 4 <= nab * sizeof(double) || b->d_f0_ab2.alloc(nab))
+      (void)hipGetLastError();                            // (optional: the run goes chunk after chunk without it)
+  }
+  int rc;
+  const std::vector<int32_t> zp(at_least_one(b->n_utt), 0);
+  if ((rc = b->d_pending.upload(zp)) || (rc = b->d_jit_redo.upload(zp)) || (rc = b->d_jit_utt.upload(L.jit_utt)) ||
+      (rc = b->d_jit_t0.upload(L.jit_t0)) || (rc = b->d_jit_ctl.upload(std::vector<int32_t>(2, 0))))
+    return rc;
+  return SMILEHIP_OK;
+}
+
+// The whole ComParE level: groups A+B here, the F0 group in a 60 ms sub-batch of plan->f0_plan
+static int alloc_compare_scratch(smilehip_plan *plan, smilehip_batch *b, const BatchLayout &L) {
+  int rc;
+  if ((rc = alloc_compare_ab_scratch(b, L)) || (rc = smilehip_batch_create(plan->f0_plan, b->h_samp_off.data(), b->n_utt, &b->f0_batch)))
+    return rc;
+  const size_t nf = at_least_one(b->f0_batch->total_frames);
+  if (b->d_pitch2.alloc(nf * 2) || b->d_jit4.alloc(nf * 4)) return fail(SMILEHIP_ERR_HIP, "hipMalloc of the F0 group's scratch matrices failed");
+  return SMILEHIP_OK;
+}
+
+// cHarmonics reads gemapsv01b_fftmagG60, the level cSpecScale reads: lld_f0_spec keeps its magnitudes (2 KB per 60 ms frame) and
+// lld_gemaps_harm starts from them instead of windowing and transforming every voiced frame a second time. Kept only while it
+// is a modest part of what is free (the caller's output matrices come after this); SMILEHIP_HARM_KEEP_MAG=0 / =1 forces it.
+static void try_keep_magnitudes(const smilehip_plan *f0_plan, smilehip_batch *fb) {
+  if (fb->total_frames <= 0) return;
+  const int64_t ld = (f0_plan->geo.K + 3) & ~int64_t(3);
+  const size_t n = size_t(fb->total_frames) * size_t(ld);
+  size_t free_b = 0, total_b = 0;
+  const char *env = getenv("SMILEHIP_HARM_KEEP_MAG");
+  bool keep = hipMemGetInfo(&free_b, &total_b) == hipSuccess && n * sizeof(float) <= free_b / 2;
+  if (env && env[0] == '0') keep = false;
+  if (env && env[0] == '1') keep = true;
+  if (keep && fb->d_mag_keep.alloc(n) == SMILEHIP_OK)
+    fb->mag_ld = ld;
+  else
+    (void)hipGetLastError();                              // (optional: cHarmonics transforms again without it)
+}
+
+static int alloc_egemaps_scratch(smilehip_plan *plan, smilehip_batch *b, const BatchLayout &L) {
+  int rc;
+  b->n_runs = (int32_t)L.run_utt.size();
+  if ((rc = b->d_run_utt.upload(L.run_utt)) || (rc = b->d_run_t0.upload(L.run_t0)) || (rc = b->d_fin_off.upload(b->h_fin_off)) ||
+      (rc = smilehip_batch_create(plan->f0_plan, b->h_samp_off.data(), b->n_utt, &b->f0_batch)))
+    return rc;
+  const size_t nf = at_least_one(b->total_frames), nf60 = at_least_one(b->f0_batch->total_frames), nfin = at_least_one(b->h_fin_off[b->n_utt]);
+  if (b->d_raw20.alloc(nf * 12) || b->d_spec220.alloc(nf * 220) || b->d_lpc.alloc(nf * 12) || b->d_formants.alloc(nf * 10) ||
+      b->d_pitch3.alloc(nf60 * 3) || b->d_jit4.alloc(nf60 * 4) || b->d_shim.alloc(nf60) || b->d_harm6.alloc(nf60 * 6) ||
+      b->d_func_in.alloc(nfin * 36))
+    return fail(SMILEHIP_ERR_HIP, "hipMalloc of the eGeMAPS scratch matrices failed (%.1f GB needed)",
+                double(nf * 254 + nf60 * 14 + nfin * 36) * 4e-9);
+  if ((rc = b->d_pending_j.upload(std::vector<int32_t>(at_least_one(b->n_utt), 0))) || (rc = b->d_harm_ctl.upload(std::vector<int32_t>(2, 0))) ||
+      (rc = b->d_fm_flags.upload(std::vector<uint64_t>(2 * ((nf + 63) / 64), 0))))
+    return rc;
+  try_keep_magnitudes(plan->f0_plan, b->f0_batch);
+  return SMILEHIP_OK;
+}
 
 extern "C" int smilehip_batch_create(smilehip_plan *plan, const int64_t *h_off, int32_t n_utt, smilehip_batch **out) {
   if (!plan || !out || n_utt < 0 || (n_utt > 0 && !h_off)) return fail(SMILEHIP_ERR_INVALID, "smilehip_batch_create: bad argument");
@@ -15,293 +132,35 @@ extern "C" int smilehip_batch_create(smilehip_plan *plan, const int64_t *h_off, 
   if (!plan->ctx) return fail(SMILEHIP_ERR_NO_DEVICE, "host-only plan: no device attached (tables only)");
   if (plan->stage_mask != SMILEHIP_STAGE_ALL) return fail(SMILEHIP_ERR_INVALID, "single-component plan cannot run the fused chain");
   HIP_TRY(hipSetDevice(plan->ctx->device));
-  auto *b = new (std::nothrow) smilehip_batch();
+  std::unique_ptr<smilehip_batch> b(new (std::nothrow) smilehip_batch());
   if (!b) return fail(SMILEHIP_ERR_NOMEM, "out of host memory");
+  BatchLayout L;
+  if (const int bad = batch_layout(layout_spec(plan), h_off, n_utt, L))
+    return fail(SMILEHIP_ERR_INVALID, "sample offsets must be non-decreasing (utterance %d)", bad - 1);
   b->plan = plan;
   b->n_utt = n_utt;
-  b->h_samp_off.assign(h_off, h_off + (n_utt ? n_utt + 1 : 0));
-  if (n_utt == 0) b->h_samp_off.assign(1, 0);
-  b->h_frame_off.assign(size_t(n_utt) + 1, 0);
-  b->h_row_off.assign(size_t(n_utt) + 1, 0);
-  const int short_T = chain_short_max();
-  const int row_extra = plan_row_extra(plan);
-  std::vector<int32_t> tile_utt, tile_t0, dtile_utt, dtile_t0, run_utt, run_t0;
-  std::vector<TileRec> tile_rec;
-  const int64_t dtile = chain_tile_rows();
-  const int64_t tile_frames = plan->use_fast ? fast512_tile_frames()
-                              : (plan->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE_F0 ? f0_tile_frames() : (int64_t(1) << 40));
-  {                                                      // the run length of the 20 ms frame kernels (lld_compare.hip / lld_gemaps.hip)
-    int64_t total_T = 0;
-    for (int32_t u = 0; u < n_utt; ++u) { const int64_t len = h_off[u + 1] - h_off[u]; if (len > 0) total_T += smilehip_num_frames(plan, len); }
-    b->run_frames = compare_run_frames(total_T);
-    if (const char *rf = getenv("SMILEHIP_RUN_FRAMES")) { const int v = atoi(rf); if (v >= 1 && v <= 4096) b->run_frames = v; }   // A/B switch
-  }
-  for (int32_t u = 0; u < n_utt; ++u) {
-    const int64_t len = h_off[u + 1] - h_off[u];
-    if (len < 0) {
-      delete b;
-      return fail(SMILEHIP_ERR_INVALID, "sample offsets must be non-decreasing (utterance %d)", u);
-    }
-    const int64_t T = smilehip_num_frames(plan, len);
-    int64_t rows = T > 0 ? T + row_extra : 0;
-    if (compare_ab_like(plan)) {
-      // rows = T60 + 1 where T60 = frames of the 60 ms framer ([is13_frame60]); none if T60 < 4
-      const int64_t N60 = std::lround(0.060 / plan->geo.period);
-      const int64_t T60 = (len >= N60) ? (len - N60) / plan->geo.H + 1 : 0;
-      rows = (T60 >= 4) ? T60 + 1 : 0;
-      for (int64_t t0 = 0; t0 < T; t0 += b->run_frames) {
-        run_utt.push_back(u);
-        run_t0.push_back((int32_t)t0);
-      }
-    }
-    if (is_egemaps(plan)) {
-      // rows = T60 + 1 (what both egemapsv02_lldsetE_smo and egemapsv02_lldsetF_smo hold); none without a 60 ms frame
-      const int64_t N60 = std::lround(0.060 / plan->geo.period);
-      const int64_t T60 = (len >= N60) ? (len - N60) / plan->geo.H + 1 : 0;
-      rows = (T60 >= 1) ? T60 + 1 : 0;
-      for (int64_t t0 = 0; t0 < T; t0 += b->run_frames) {
-        run_utt.push_back(u);
-        run_t0.push_back((int32_t)t0);
-      }
-      if (b->h_fin_off.empty()) b->h_fin_off.assign(size_t(n_utt) + 1, 0);
-      b->h_fin_off[u + 1] = b->h_fin_off[u] + (T60 >= 1 ? T + 1 : 0);
-    }
-    b->h_frame_off[u + 1] = b->h_frame_off[u] + T;
-    b->h_row_off[u + 1] = b->h_row_off[u] + rows;
-    if (T > 0 && T <= short_T) b->h_short.push_back(u);
-    if (T > 0 && (h_off[u] & 1)) b->all_even = false;
-    for (int64_t t0 = 0; t0 < T; t0 += tile_frames) {
-      tile_utt.push_back(u);
-      tile_t0.push_back((int32_t)t0);
-      TileRec r;
-      r.samp0 = h_off[u] + t0 * plan->geo.H;
-      r.row0 = b->h_frame_off[u] + t0;
-      r.n_frames = (int32_t)std::min<int64_t>(tile_frames, T - t0);
-      r.pad = 0;
-      tile_rec.push_back(r);
-    }
-    for (int64_t t0 = 0; t0 < rows; t0 += dtile) {
-      dtile_utt.push_back(u);
-      dtile_t0.push_back((int32_t)t0);
-    }
-  }
-  b->total_frames = b->h_frame_off[n_utt];
-  b->total_rows = b->h_row_off[n_utt];
-  b->n_tiles = (int32_t)tile_utt.size();
-  b->n_dtiles = (int32_t)dtile_utt.size();
+  b->total_frames = L.total_frames; b->total_rows = L.total_rows;
+  b->n_tiles = (int32_t)L.tile_utt.size(); b->n_dtiles = (int32_t)L.dtile_utt.size();
+  b->run_frames = L.run_frames; b->all_even = L.all_even;
   int rc;
-  if ((rc = b->d_samp_off.upload(b->h_samp_off)) || (rc = b->d_frame_off.upload(b->h_frame_off)) ||
-      (rc = b->d_row_off.upload(b->h_row_off)) ||
-      (rc = b->d_tile_utt.upload(tile_utt)) || (rc = b->d_tile_t0.upload(tile_t0)) || (rc = b->d_tile_rec.upload(tile_rec)) ||
-      (rc = b->d_dtile_utt.upload(dtile_utt)) || (rc = b->d_dtile_t0.upload(dtile_t0)) ||
-      (rc = b->d_short.upload(b->h_short))) {
-    delete b;
+  if ((rc = b->d_samp_off.upload(L.samp_off)) || (rc = b->d_frame_off.upload(L.frame_off)) || (rc = b->d_row_off.upload(L.row_off)) ||
+      (rc = b->d_tile_utt.upload(L.tile_utt)) || (rc = b->d_tile_t0.upload(L.tile_t0)) || (rc = b->d_tile_rec.upload(L.tile_rec)) ||
+      (rc = b->d_dtile_utt.upload(L.dtile_utt)) || (rc = b->d_dtile_t0.upload(L.dtile_t0)) || (rc = b->d_short.upload(L.short_utts)))
     return rc;
+  b->h_samp_off = std::move(L.samp_off);                  // what the runs and the functionals read on the host
+  b->h_frame_off = std::move(L.frame_off); b->h_row_off = std::move(L.row_off);
+  b->h_fin_off = std::move(L.fin_off); b->h_short = std::move(L.short_utts);
+  switch (plan->cfg.chain_kind) {
+    case SMILEHIP_CHAIN_IS09: rc = alloc_is09_scratch(b.get(), L); break;
+    case SMILEHIP_CHAIN_COMPARE_AB: rc = alloc_compare_ab_scratch(b.get(), L); break;
+    case SMILEHIP_CHAIN_COMPARE_F0: rc = alloc_f0_scratch(plan, b.get(), L); break;
+    case SMILEHIP_CHAIN_COMPARE: rc = alloc_compare_scratch(plan, b.get(), L); break;
+    case SMILEHIP_CHAIN_EGEMAPS: rc = alloc_egemaps_scratch(plan, b.get(), L); break;
+    case SMILEHIP_CHAIN_MFCC:
+    case SMILEHIP_CHAIN_PLP: rc = alloc_mfcc_scratch(plan, b.get(), L); break;
   }
-  if (plan->cfg.chain_kind == SMILEHIP_CHAIN_IS09 && b->total_frames > 0) {
-    std::vector<int32_t> fu((size_t)b->total_frames);
-    for (int32_t u = 0; u < n_utt; ++u) std::fill(fu.begin() + b->h_frame_off[u], fu.begin() + b->h_frame_off[u + 1], u);
-    if ((rc = b->d_frame_utt.upload(fu))) { delete b; return rc; }
-  }
-  if (compare_ab_like(plan)) {
-    b->n_runs = (int32_t)run_utt.size();
-    if ((rc = b->d_run_utt.upload(run_utt)) || (rc = b->d_run_t0.upload(run_t0))) {
-      delete b;
-      return rc;
-    }
-    const size_t nf = size_t(b->total_frames ? b->total_frames : 1);
-    if (smilehip::dev_malloc(reinterpret_cast<void **>(&b->d_rawA.p), nf * 4 * sizeof(float)) != hipSuccess ||
-        smilehip::dev_malloc(reinterpret_cast<void **>(&b->d_rawB.p), nf * 55 * sizeof(float)) != hipSuccess ||
-        smilehip::dev_malloc(reinterpret_cast<void **>(&b->d_mel1.p), nf * 26 * sizeof(float)) != hipSuccess) {
-      delete b;
-      return fail(SMILEHIP_ERR_HIP, "hipMalloc of the ComParE scratch matrices failed");
-    }
-    b->d_rawA.n = nf * 4; b->d_rawB.n = nf * 55; b->d_mel1.n = nf * 26;
-    b->d_b_extra.n = size_t(n_utt ? n_utt : 1) * 110;
-    if (smilehip::dev_malloc(reinterpret_cast<void **>(&b->d_b_extra.p), b->d_b_extra.n * sizeof(float)) != hipSuccess) {
-      delete b;
-      return fail(SMILEHIP_ERR_HIP, "hipMalloc of the ComParE scratch matrices failed");
-    }
-    (void)hipMemset(b->d_rawA.p, 0, nf * 4 * sizeof(float));
-  }
-  if (is_egemaps(plan)) {
-    b->n_runs = (int32_t)run_utt.size();
-    if (b->h_fin_off.empty()) b->h_fin_off.assign(size_t(n_utt) + 1, 0);
-    if ((rc = b->d_run_utt.upload(run_utt)) || (rc = b->d_run_t0.upload(run_t0)) || (rc = b->d_fin_off.upload(b->h_fin_off)) ||
-        (rc = smilehip_batch_create(plan->f0_plan, h_off, n_utt, &b->f0_batch))) {
-      delete b;
-      return rc;
-    }
-    const size_t nf = size_t(b->total_frames ? b->total_frames : 1);
-    const size_t nf60 = size_t(b->f0_batch->total_frames ? b->f0_batch->total_frames : 1);
-    const size_t nfin = size_t(b->h_fin_off[n_utt] ? b->h_fin_off[n_utt] : 1);
-    auto alloc = [&](DevBuf<float> &d, size_t n) {
-      d.release();
-      if (smilehip::dev_malloc(reinterpret_cast<void **>(&d.p), n * sizeof(float)) != hipSuccess) return false;
-      d.n = n;
-      return true;
-    };
-    if (!alloc(b->d_raw20, nf * 12) || !alloc(b->d_spec220, nf * 220) || !alloc(b->d_lpc, nf * 12) || !alloc(b->d_formants, nf * 10) ||
-        !alloc(b->d_pitch3, nf60 * 3) || !alloc(b->d_jit4, nf60 * 4) || !alloc(b->d_shim, nf60) || !alloc(b->d_harm6, nf60 * 6) ||
-        !alloc(b->d_func_in, nfin * 36)) {
-      delete b;
-      return fail(SMILEHIP_ERR_HIP, "hipMalloc of the eGeMAPS scratch matrices failed (%.1f GB needed)",
-                  double(nf * 254 + nf60 * 14 + nfin * 36) * 4e-9);
-    }
-    std::vector<int32_t> zp(size_t(n_utt ? n_utt : 1), 0);
-    if ((rc = b->d_pending_j.upload(zp)) || (rc = b->d_harm_ctl.upload(std::vector<int32_t>(2, 0))) ||
-        (rc = b->d_fm_flags.upload(std::vector<uint64_t>(2 * ((nf + 63) / 64), 0)))) {
-      delete b;
-      return rc;
-    }
-    // cHarmonics reads gemapsv01b_fftmagG60, the level cSpecScale reads: lld_f0_spec keeps its magnitudes (2 KB per 60 ms frame) and
-    // lld_gemaps_harm starts from them instead of windowing and transforming every voiced frame a second time. Kept only while it
-    // is a modest part of what is free (the caller's output matrices come after this); SMILEHIP_HARM_KEEP_MAG=0 / =1 forces it.
-    if (b->f0_batch->total_frames > 0) {
-      smilehip_batch *fb = b->f0_batch;
-      const int64_t ld = (plan->f0_plan->geo.K + 3) & ~int64_t(3);
-      const size_t need = size_t(fb->total_frames) * size_t(ld) * sizeof(float);
-      size_t free_b = 0, total_b = 0;
-      const char *env = getenv("SMILEHIP_HARM_KEEP_MAG");
-      bool keep = hipMemGetInfo(&free_b, &total_b) == hipSuccess && need <= free_b / 2;
-      if (env && env[0] == '0') keep = false;
-      if (env && env[0] == '1') keep = true;
-      if (keep && smilehip::dev_malloc(reinterpret_cast<void **>(&fb->d_mag_keep.p), need) == hipSuccess) {
-        fb->d_mag_keep.n = need / sizeof(float);
-        fb->mag_ld = ld;
-      } else {
-        fb->d_mag_keep.p = nullptr;
-        (void)hipGetLastError();
-      }
-    }
-  }
-  // The fast kernel with the two regression stages inside (lld_mfcc512<..., DELTA>): tiles as long as the batch allows -- a tile
-  // pays one pass of four frames before it (inside an utterance) and one behind it. L = the tile length whose estimate
-  // ceil(tiles / wave slots) x (L / 4 + 2) passes is smallest; an utterance is cut into equal parts of at most L frames
-  // (multiples of four: a frame's lane group is its index mod 4).
-  if (plan->use_fast && (plan->cfg.chain_kind == SMILEHIP_CHAIN_MFCC || plan->cfg.chain_kind == SMILEHIP_CHAIN_PLP) &&
-      plan->cfg.n_delta == 2 && plan->cfg.delta_win == 2 && !plan->cfg.append_log_energy && !plan->cfg.cms && plan->ctx &&
-      b->total_frames > 0 && b->all_even && !getenv("SMILEHIP_NO_FUSED_DELTA")) {     // (all_even: the dword loads of the aligned instance)
-    const int64_t slots = std::max<int64_t>(1, plan->fast.max_blocks) * 8;
-    const auto parts_of = [&](int64_t T, int64_t L) { return (T + L - 1) / L; };
-    int64_t bestL = 32;
-    double best = 1e300;
-    // (the count of distinct utterance lengths, not the count of utterances, is what the 505 candidate lengths are tried on)
-    std::map<int64_t, int64_t> hist;
-    for (int32_t u = 0; u < n_utt; ++u) {
-      const int64_t T = b->h_frame_off[u + 1] - b->h_frame_off[u];
-      if (T > 0) hist[T]++;
-    }
-    for (int64_t L = 32; L <= 2048; L += 4) {
-      int64_t n = 0;
-      for (const auto &h : hist) n += h.second * ((h.first <= short_T) ? 1 : parts_of(h.first, L));
-      const double cost = double((n + slots - 1) / slots) * double(L / 4 + 2);
-      if (cost <= best) { best = cost; bestL = L; }
-    }
-    std::vector<FTileRec> ft;
-    for (int32_t u = 0; u < n_utt; ++u) {
-      const int64_t T = b->h_frame_off[u + 1] - b->h_frame_off[u];
-      if (T <= 0) continue;
-      const int64_t parts = (T <= short_T) ? 1 : parts_of(T, bestL);
-      const int64_t len = (((T + parts - 1) / parts) + 3) & ~int64_t(3);
-      for (int64_t t0 = 0; t0 < T; t0 += len) {
-        const int64_t t1 = std::min<int64_t>(T, t0 + len), p0 = t0 > 0 ? t0 - 4 : 0;
-        FTileRec r;
-        r.samp0 = h_off[u] + p0 * plan->geo.H;
-        r.row0 = b->h_frame_off[u] + p0;
-        const int64_t last = (t1 + 3) & ~int64_t(3);      // first frame of the last pass: the one behind the tile's last frame (rows are written one pass late)
-        r.n_frames = (int32_t)(last - p0 + 4);
-        r.live_n = (int32_t)(T - p0);
-        r.e0 = (int32_t)(t0 - p0);
-        r.e1 = (int32_t)(t1 - p0);
-        r.lo = (int32_t)(-p0);
-        r.delta_on = T > short_T;
-        ft.push_back(r);
-      }
-    }
-    std::stable_sort(ft.begin(), ft.end(), [](const FTileRec &a, const FTileRec &c) { return a.n_frames > c.n_frames; });   // long tiles first
-    b->n_ftiles = (int32_t)ft.size();
-    if ((rc = b->d_ftile_rec.upload(ft))) { delete b; return rc; }
-  }
-  if ((plan->cfg.chain_kind == SMILEHIP_CHAIN_MFCC || plan->cfg.chain_kind == SMILEHIP_CHAIN_PLP) && plan->cfg.n_delta > 0 &&
-      plan->ctx && b->total_frames > 0 && b->n_ftiles == 0) {
-    const size_t n = size_t(b->total_frames) * size_t(plan_n_static(plan));
-    if (smilehip::dev_malloc(reinterpret_cast<void **>(&b->d_static.p), n * sizeof(float)) != hipSuccess) {
-      delete b;
-      return fail(SMILEHIP_ERR_HIP, "hipMalloc of the static-block scratch failed");
-    }
-    b->d_static.n = n;
-  }
-  if (plan->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE_F0) {
-    const size_t nf = size_t(b->total_frames ? b->total_frames : 1);
-    if (smilehip::dev_malloc(reinterpret_cast<void **>(&b->d_shs.p), nf * 21 * sizeof(float)) != hipSuccess ||
-        smilehip::dev_malloc(reinterpret_cast<void **>(&b->d_e60.p), nf * sizeof(float)) != hipSuccess) {
-      delete b;
-      return fail(SMILEHIP_ERR_HIP, "hipMalloc of the F0 scratch matrices failed");
-    }
-    b->d_shs.n = nf * 21; b->d_e60.n = nf;
-    const size_t nab = (size_t)std::max<int64_t>(f0_scratch_doubles(b->n_tiles, (int)plan->geo.K), 1);
-    if (smilehip::dev_malloc(reinterpret_cast<void **>(&b->d_f0_ab.p), nab * sizeof(double)) != hipSuccess) {
-      delete b;
-      return fail(SMILEHIP_ERR_HIP, "hipMalloc of the F0 row scratch (%zu MB) failed", nab * sizeof(double) >> 20);
-    }
-    b->d_f0_ab.n = nab;
-    // SMILEHIP_F0_PIPE=1 (round 6, measured and NOT the default): a second set of rows for the chunk pipeline (F0Pipe). Bit-identical
-    // (tests/test_gpu_f0_pipe.py) and no faster: config 4 243.4 ms piped against 241.0 ms chunk after chunk, config 5 1087 against
-    // 1081 -- side by side the three kernels stretch (spec 39 -> 102 ms, cand 36 -> 45, sweep 26 -> 38 summed) by what they gain;
-    // the idle issue slots their counters show are not slots another kernel's waves can use.
-    {
-      static const bool pipe_on = [] { const char *e = getenv("SMILEHIP_F0_PIPE"); return e && e[0] == '1'; }();
-      if (pipe_on && b->n_tiles > f0_chunk_tiles()) {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b / 4 > nab * sizeof(double) &&
-            smilehip::dev_malloc(reinterpret_cast<void **>(&b->d_f0_ab2.p), nab * sizeof(double)) == hipSuccess)
-          b->d_f0_ab2.n = nab;
-        else
-          (void)hipGetLastError();
-      }
-    }
-    std::vector<int32_t> zp(size_t(n_utt ? n_utt : 1), 0);
-    if ((rc = b->d_pending.upload(zp)) || (rc = b->d_jit_redo.upload(zp))) {
-      delete b;
-      return rc;
-    }
-    // cPitchJitter's work items: 64 consecutive frames of one utterance each, all first chunks, then all second chunks, ...
-    // (the chains that begin in a chunk can run to the utterance's end: the longest possible ones are launched first)
-    std::vector<int32_t> ju, jt;
-    int64_t maxT = 0;
-    for (int32_t u = 0; u < n_utt; ++u) maxT = std::max(maxT, b->h_frame_off[u + 1] - b->h_frame_off[u]);
-    for (int64_t t0 = 0; t0 < maxT; t0 += jitter_chunk_frames())
-      for (int32_t u = 0; u < n_utt; ++u)
-        if (t0 < b->h_frame_off[u + 1] - b->h_frame_off[u]) { ju.push_back(u); jt.push_back((int32_t)t0); }
-    if ((rc = b->d_jit_utt.upload(ju)) || (rc = b->d_jit_t0.upload(jt)) || (rc = b->d_jit_ctl.upload(std::vector<int32_t>(2, 0)))) {
-      delete b;
-      return rc;
-    }
-  }
-  if (plan->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE) {
-    if ((rc = smilehip_batch_create(plan->f0_plan, h_off, n_utt, &b->f0_batch))) {
-      delete b;
-      return rc;
-    }
-    const size_t nf = size_t(b->f0_batch->total_frames ? b->f0_batch->total_frames : 1);
-    if (smilehip::dev_malloc(reinterpret_cast<void **>(&b->d_pitch2.p), nf * 2 * sizeof(float)) != hipSuccess ||
-        smilehip::dev_malloc(reinterpret_cast<void **>(&b->d_jit4.p), nf * 4 * sizeof(float)) != hipSuccess) {
-      delete b;
-      return fail(SMILEHIP_ERR_HIP, "hipMalloc of the F0 group's scratch matrices failed");
-    }
-    b->d_pitch2.n = nf * 2; b->d_jit4.n = nf * 4;
-  }
-  if (plan->cfg.chain_kind == SMILEHIP_CHAIN_IS09) {
-    std::vector<float> zero;   // allocate only
-    b->d_raw16.release();
-    b->d_raw16.n = size_t(b->total_frames) * 16;
-    if (smilehip::dev_malloc(reinterpret_cast<void **>(&b->d_raw16.p), (b->d_raw16.n ? b->d_raw16.n : 1) * sizeof(float)) != hipSuccess) {
-      delete b;
-      return fail(SMILEHIP_ERR_HIP, "hipMalloc of the IS09 scratch matrix failed");
-    }
-  }
-  *out = b;
+  if (rc) return rc;
+  *out = b.release();
   return SMILEHIP_OK;
 }
 
@@ -375,6 +234,28 @@ static void fill_params(const smilehip_plan *p, const smilehip_batch *b, const i
   P.plp_sin = p->d_plp_sin.p;
 }
 
+// The window chain (lld_kernels.hip) over a batch's rows: level 0 = x, the batch's window-chain tiles and its short utterances.
+// The caller sets the stages (copy_col, n_stages, kind[], W[], out_col[]).
+static ChainParams chain_params(const smilehip_batch *b, const float *x, int64_t ld_x, int32_t D, float *out, int64_t ld_out) {
+  ChainParams Q;
+  std::memset(&Q, 0, sizeof(Q));
+  Q.frame_off = b->d_frame_off.p;
+  Q.row_off = b->d_row_off.p;
+  Q.tile_utt = b->d_dtile_utt.p;
+  Q.tile_t0 = b->d_dtile_t0.p;
+  Q.n_tiles = b->n_dtiles;
+  Q.n_utt = b->n_utt;
+  Q.x = x;
+  Q.ld_x = ld_x;
+  Q.out = out;
+  Q.ld_out = ld_out;
+  Q.D = D;
+  Q.short_T = chain_short_max();
+  Q.short_utts = b->d_short.p;
+  Q.n_short = (int32_t)b->h_short.size();
+  return Q;
+}
+
 // R13 for a batch whose rows == frames: level 0 = x (leading dimension ld_x); writes [copy of x at copy_col (if >= 0) |
 // order 1 at D | order 2 at 2D] into out
 static int delta_chain_from(smilehip_plan *plan, smilehip_batch *b, const float *d_x, int64_t ld_x, int copy_col, float *d_io,
@@ -385,28 +266,13 @@ static int delta_chain_from(smilehip_plan *plan, smilehip_batch *b, const float 
   if (b->total_frames == 0) return SMILEHIP_OK;
   // rows == frames is what this entry point assumes (d_io holds the static block)
   if (b->total_rows != b->total_frames) return fail(SMILEHIP_ERR_INVALID, "smilehip_delta_chain: batch belongs to a chain with extra rows");
-  ChainParams Q;
-  std::memset(&Q, 0, sizeof(Q));
-  Q.frame_off = b->d_frame_off.p;
-  Q.row_off = b->d_row_off.p;
-  Q.tile_utt = b->d_dtile_utt.p;
-  Q.tile_t0 = b->d_dtile_t0.p;
-  Q.n_tiles = b->n_dtiles;
-  Q.n_utt = b->n_utt;
-  Q.x = d_x;
-  Q.ld_x = ld_x;
+  ChainParams Q = chain_params(b, d_x, ld_x, D, d_io, ld);
   Q.copy_col = copy_col;
-  Q.out = d_io;
-  Q.ld_out = ld;
-  Q.D = D;
   Q.n_stages = n_orders;
   Q.kind[0] = Q.kind[1] = 0;
   Q.W[0] = Q.W[1] = W;
   Q.out_col[0] = D;
   Q.out_col[1] = 2 * D;
-  Q.short_T = chain_short_max();
-  Q.short_utts = b->d_short.p;
-  Q.n_short = (int32_t)b->h_short.size();
   hipError_t e = launch_chain(Q, (hipStream_t)stream);
   if (e != hipSuccess) return fail(SMILEHIP_ERR_HIP, "window-chain kernel launch failed: %s", hipGetErrorString(e));
   return SMILEHIP_OK;
@@ -473,26 +339,14 @@ extern "C" int smilehip_mfcc_run(smilehip_plan *plan, smilehip_batch *b, const i
   if (plan->timing) HIP_TRY(hipEventRecord(ev[1], s));
   if (fused_delta) {                                   // what is left: the tick-accurate path of the very short utterances, in place
     if (!b->h_short.empty()) {
-      ChainParams Q;
-      std::memset(&Q, 0, sizeof(Q));
-      Q.frame_off = b->d_frame_off.p;
-      Q.row_off = b->d_row_off.p;
-      Q.n_tiles = 0;
-      Q.n_utt = b->n_utt;
-      Q.x = d_out;
-      Q.ld_x = ld_out;
+      ChainParams Q = chain_params(b, d_out, ld_out, n_static, d_out, ld_out);
+      Q.tile_utt = Q.tile_t0 = nullptr; Q.n_tiles = 0;   // (no tiles: the long utterances' rows are written already)
       Q.copy_col = -1;
-      Q.out = d_out;
-      Q.ld_out = ld_out;
-      Q.D = n_static;
       Q.n_stages = 2;
       Q.kind[0] = Q.kind[1] = 0;
       Q.W[0] = Q.W[1] = plan->cfg.delta_win;
       Q.out_col[0] = n_static;
       Q.out_col[1] = 2 * n_static;
-      Q.short_T = chain_short_max();
-      Q.short_utts = b->d_short.p;
-      Q.n_short = (int32_t)b->h_short.size();
       e = launch_chain(Q, s);
       if (e != hipSuccess) return fail(SMILEHIP_ERR_HIP, "window-chain kernel launch failed: %s", hipGetErrorString(e));
     }
@@ -546,28 +400,13 @@ static int is09_run(smilehip_plan *plan, smilehip_batch *b, const int16_t *d_pcm
   hipError_t e = launch_is09(P, I, s);
   if (e != hipSuccess) return fail(SMILEHIP_ERR_HIP, "IS09 kernel launch failed: %s", hipGetErrorString(e));
   if ((trc = timing_mark(plan, 1, s))) return trc;
-  ChainParams Q;
-  std::memset(&Q, 0, sizeof(Q));
-  Q.frame_off = b->d_frame_off.p;
-  Q.row_off = b->d_row_off.p;
-  Q.tile_utt = b->d_dtile_utt.p;
-  Q.tile_t0 = b->d_dtile_t0.p;
-  Q.n_tiles = b->n_dtiles;
-  Q.n_utt = b->n_utt;
-  Q.x = b->d_raw16.p;
-  Q.ld_x = 16;
+  ChainParams Q = chain_params(b, b->d_raw16.p, 16, 16, d_out, ld_out);
   Q.copy_col = -1;
-  Q.out = d_out;
-  Q.ld_out = ld_out;
-  Q.D = 16;
   Q.n_stages = 2;
   Q.kind[0] = 1; Q.W[0] = plan->cfg.sma_win / 2;          // cContourSmoother
   Q.kind[1] = 0; Q.W[1] = plan->cfg.delta_win;            // cDeltaRegression
   Q.out_col[0] = 0;
   Q.out_col[1] = 16;
-  Q.short_T = chain_short_max();
-  Q.short_utts = b->d_short.p;
-  Q.n_short = (int32_t)b->h_short.size();
   e = launch_chain(Q, s);
   if (e != hipSuccess) return fail(SMILEHIP_ERR_HIP, "window-chain kernel launch failed: %s", hipGetErrorString(e));
   return timing_mark(plan, 2, s);
@@ -599,7 +438,7 @@ static int compare_run(smilehip_plan *plan, smilehip_batch *b, const int16_t *d_
   Q.rasta_iir = plan->rasta_iir;
   for (int i = 0; i < 5; ++i) Q.rasta_fir[i] = plan->rasta_fir[i];
   Q.fsSec = plan->geo.fft_frame_size_sec;
-  Q.N60 = (int32_t)std::lround(0.060 / plan->geo.period);
+  Q.N60 = (int32_t)samples_60ms(plan->geo.period);
   Q.max_utt_samples = 0;
   for (size_t u2 = 0; u2 + 1 < b->h_samp_off.size(); ++u2) Q.max_utt_samples = std::max<int64_t>(Q.max_utt_samples, b->h_samp_off[u2 + 1] - b->h_samp_off[u2]);
   for (int i = 0; i < 2; ++i) {
@@ -613,28 +452,13 @@ static int compare_run(smilehip_plan *plan, smilehip_batch *b, const int16_t *d_
   hipError_t e = launch_compare(P, Q, b->n_runs, b->d_row_off.p, b->total_rows, d_out, ld_out, de_col, s);
   if (e != hipSuccess) return fail(SMILEHIP_ERR_HIP, "ComParE kernel launch failed: %s", hipGetErrorString(e));
   if ((trc = timing_mark(plan, 1, s))) return trc;
-  ChainParams C;
-  std::memset(&C, 0, sizeof(C));
-  C.frame_off = b->d_frame_off.p;
-  C.row_off = b->d_row_off.p;
-  C.tile_utt = b->d_dtile_utt.p;
-  C.tile_t0 = b->d_dtile_t0.p;
-  C.n_tiles = b->n_dtiles;
-  C.n_utt = b->n_utt;
-  C.x = b->d_rawB.p;
-  C.ld_x = 55;
+  ChainParams C = chain_params(b, b->d_rawB.p, 55, 55, d_out, ld_out);
   C.copy_col = -1;
-  C.out = d_out;
-  C.ld_out = ld_out;
-  C.D = 55;
   C.n_stages = 2;
   C.kind[0] = 1; C.W[0] = 1;
   C.kind[1] = 0; C.W[1] = 2;
   C.out_col[0] = 4;
   C.out_col[1] = de_col + 4;
-  C.short_T = chain_short_max();
-  C.short_utts = b->d_short.p;
-  C.n_short = (int32_t)b->h_short.size();
   e = launch_chain(C, s);
   if (e != hipSuccess) return fail(SMILEHIP_ERR_HIP, "window-chain kernel launch failed: %s", hipGetErrorString(e));
   e = launch_compare_b_extra(b->d_frame_off.p, b->d_row_off.p, b->n_utt, b->d_rawB.p, b->d_b_extra.p, s);
@@ -875,7 +699,7 @@ extern "C" int smilehip_batch_f0_pending(smilehip_batch *b, const int32_t **d_pe
 extern "C" int smilehip_batch_egemaps_taps(smilehip_batch *b, const float **d_raw20, const float **d_lpc, const float **d_formants,
                                            const float **d_pitch3, const float **d_jit4, const float **d_shim_db, const float **d_harm6,
                                            const float **d_func_in, const int32_t **d_pending, int64_t *h_frame_off60) {
-  if (!b || !is_egemaps(b->plan)) return fail(SMILEHIP_ERR_INVALID, "smilehip_batch_egemaps_taps: not an eGeMAPS chain batch");
+  if (!b || b->plan->cfg.chain_kind != SMILEHIP_CHAIN_EGEMAPS) return fail(SMILEHIP_ERR_INVALID, "smilehip_batch_egemaps_taps: not an eGeMAPS chain batch");
   if (d_raw20) *d_raw20 = b->d_raw20.p;
   if (d_lpc) *d_lpc = b->d_lpc.p;
   if (d_formants) *d_formants = b->d_formants.p;

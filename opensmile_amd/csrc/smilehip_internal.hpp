@@ -61,7 +61,8 @@ struct smilehip_context {
   }
 };
 
-// Device blocks of the batches and plans go through these two: by default hipMalloc / hipFree; with a block cache switched on
+// Device blocks of the batches and plans go through these two, and DevBuf::alloc / ::upload / ::release are the way in to them:
+// by default hipMalloc / hipFree; with a block cache switched on
 // (smilehip_alloc_cache, smilehip_core.cpp) a freed block is kept and handed out again for the next allocation of exactly its size --
 // a host that creates and destroys a batch per chunk of files then neither allocates nor, more to the point, runs into hipFree's
 // implicit synchronisation of the whole device, which would wait for the NEXT chunk's copies and kernels already under way.
@@ -83,6 +84,15 @@ struct DevBuf {
     if (p) smilehip::dev_free(p);
     p = nullptr;
     n = 0;
+  }
+  int alloc(size_t count) {                  // uninitialised; at least one element is allocated, n records `count`
+    release();
+    if (smilehip::dev_malloc(reinterpret_cast<void **>(&p), (count ? count : 1) * sizeof(T)) != hipSuccess) {
+      p = nullptr;
+      return fail(SMILEHIP_ERR_HIP, "device allocation of %zu bytes failed", (count ? count : 1) * sizeof(T));
+    }
+    n = count;
+    return SMILEHIP_OK;
   }
   int upload(const std::vector<T> &h) {
     release();
