@@ -7,7 +7,8 @@
 // algorithms operation for operation (sysdeps/ieee754/flt-32/e_logf.c, e_expf.c: S. Nagy's table + polynomial in double, in
 // the x86-64 "fma" build the dynamic linker selects on every CPU with FMA -- the products and sums below are fused exactly where
 // GCC fuses them there; e_log10f.c: fdlibm's float formula around logf, built without FMA). tests/test_glibc_float.py compiles
-// this header for the host and sweeps every float argument against the real libm; the tables are read out of that libm by
+// this header for the host and sweeps every float argument against the real libm, tests/test_gpu_device_math.py does the same with the
+// gfx950 build (every argument of every function, on the device); the tables are read out of that libm by
 // tools/gen_glibc_float_tables.py.
 #pragma once
 #include <cstdint>

@@ -75,16 +75,6 @@ __device__ __forceinline__ double lane_d(double x, int row_base4, int src) {
   const int lo = __builtin_amdgcn_ds_bpermute(row_base4 + 4 * src, __double2loint(x));
   return __hiloint2double(hi, lo);
 }
-// RN(a / b) from y = RN(1 / b) (the division itself, once per divisor): q0 = RN(a y) is within two ulps, one residual step makes
-// it faithful, the second returns the correctly rounded quotient (Markstein; lld_f0.hip: f0_div_by, tests/test_exact_sum_claims.py)
-// -- five full-rate operations instead of the ~25 of the division sequence, for operands well inside the normal range
-__device__ __forceinline__ double div_by(double a, double b, double y) {
-  const double q0 = a * y;
-  const double r0 = __builtin_fma(-q0, b, a);
-  const double q1 = __builtin_fma(r0, y, q0);
-  const double r1 = __builtin_fma(-q1, b, a);
-  return __builtin_fma(r1, y, q1);
-}
 // x, behind a wall the common-subexpression pass does not see through: the bins' powers as doubles are used by three loops a long
 // way apart, and the compiler would rather keep all seventeen (34 registers, spilled) than square and convert again
 __device__ __forceinline__ float fresh(float x) { asm volatile("" : "+v"(x)); return x; }
@@ -391,7 +381,7 @@ __device__ __forceinline__ void compare_frame_quad_body(const LldParams &P, cons
         const double entropy_floor = 0.0000001;
         double dn = frameSum;
         if (dn < (float)entropy_floor) dn = (float)entropy_floor;
-        // the frame's two divisors -- its power sum and log 2 -- by their reciprocals (div_by). Its range holds by construction:
+        // the frame's two divisors -- its power sum and log 2 -- by their reciprocals (div_markstein, lld_device.hpp). Its range holds by construction:
         // int16 samples are at most 1 in magnitude, a 320-sample frame's bins at most 320, the power sum at most 2.7e7 (and at
         // least the floor 1e-7); quotients and x log x stay between 1e-15 and 1e15
         const double inv_dn = 1.0 / dn;
@@ -406,9 +396,9 @@ __device__ __forceinline__ void compare_frame_quad_body(const LldParams &P, cons
             zf[k - 1] = (float)(s_sharp[k - 1] * p);         // :1455 / :1469
             double vv = p;
             if (vv <= entropy_floor) vv = entropy_floor;
-            const double ln = div_by(vv, dn, inv_dn);
+            const double ln = div_markstein(vv, dn, inv_dn);
             const double xl = ln * log_d<true>(ln, s_log);
-            e0 += (ln > 0.0) ? div_by(xl, kLog2, kInvLog2) : 0.0;
+            e0 += (ln > 0.0) ? div_markstein(xl, kLog2, kInvLog2) : 0.0;
             const double t1 = F0e * fresh(k) - (double)ctr;
             double mm = t1 * t1 * p;
             e1 += mm; mm *= t1; e2m += mm; e3 += mm * t1;

@@ -131,8 +131,9 @@ __device__ __forceinline__ float bin_magnitude(float2 X, bool edge) {
   return edge ? fabsf(X.x) : sqrtf(X.x * X.x + X.y * X.y);
 }
 // sqrtf for an argument in [2^-96, infinity): v_sqrt_f32 and the library sequence's two residual tests, without its scaling of small
-// arguments and its zero / infinity test (16 -> 9 instructions). Equal to sqrtf for every such float
-// (tools/ubench/sqrt_f32_normal_check.hip: all 1.88e9 of them on the device).
+// arguments and its zero / infinity test (16 -> 9 instructions). Equal to sqrtf for every such float: tests/test_gpu_device_math.py
+// runs sqrt_rn_batch<16> over all 2^32 bit patterns against the host's sqrtf, with waves that must take this branch and waves that
+// must not.
 __device__ __forceinline__ float sqrt_rn_normal(float x) {
   float s = __builtin_amdgcn_sqrtf(x);
   const float sm = __uint_as_float(__float_as_uint(s) - 1u), sp = __uint_as_float(__float_as_uint(s) + 1u);
@@ -144,12 +145,17 @@ __device__ __forceinline__ float sqrt_rn_normal(float x) {
 // v[m] = sqrtf(v[m]) for a lane's batch: the lean form when every value of every lane of the wave lies in [2^-96, infinity), the
 // library's otherwise (a zero, a tiny or a non-finite value anywhere: one wave-uniform test per batch). Callers put 1.0f where they
 // have no value.
+// (the wave-uniform choice on its own: true = every value of every lane lies in [2^-96, infinity))
 template <int N>
-__device__ __forceinline__ void sqrt_rn_batch(float (&v)[N]) {
+__device__ __forceinline__ bool sqrt_rn_batch_is_lean(const float (&v)[N]) {
   bool odd = false;
 #pragma unroll
   for (int m = 0; m < N; ++m) odd |= (__float_as_uint(v[m]) - 0x0f800000u) >= (0x7f800000u - 0x0f800000u);
-  if (__builtin_amdgcn_ballot_w64(odd) != 0) {
+  return __builtin_amdgcn_ballot_w64(odd) == 0;
+}
+template <int N>
+__device__ __forceinline__ void sqrt_rn_batch(float (&v)[N]) {
+  if (!sqrt_rn_batch_is_lean(v)) {
 #pragma unroll
     for (int m = 0; m < N; ++m) v[m] = sqrtf(v[m]);
   } else {
@@ -157,6 +163,54 @@ __device__ __forceinline__ void sqrt_rn_batch(float (&v)[N]) {
     for (int m = 0; m < N; ++m) v[m] = sqrt_rn_normal(v[m]);
   }
 }
+
+// RN(a / b) for a divisor whose correctly rounded reciprocal y = RN(1 / b) is known (the division itself, once per divisor, or a host
+// table): q0 = RN(a y) is within two ulps of the quotient, one residual correction makes it a faithful rounding, and a second one --
+// Markstein's theorem: y correctly rounded, q faithful, the residual a - b q exact in one FMA -- returns the correctly rounded
+// quotient, which is what the division instruction sequence (and the reference's divss / divsd) returns. Five full-rate operations
+// instead of the division's eleven (float) or ~25 (double). This is the ONE definition of the sequence: every kernel that divides
+// this way calls it, and tests/test_gpu_device_math.py runs these very functions on the device against a / b (float: all 2^23
+// significands at every normal exponent, both signs, for the divisors the chains use; double: 2^30 seeded numerators per divisor
+// of the F0 sweep's table and ComParE's frame divisors).
+//
+// Valid domain, float: a finite, b and y normal, and no residual or quotient in the subnormal range. The sequence does NOT return the
+// division's bits for a = +-0 (the sign is lost: fma(r1, y, q1) adds +0 and -0), for tiny a (the residuals underflow), for huge a
+// (q0 b overflows), for +-inf (fma(-inf, b, inf) = NaN) -- hence the guards below, which decide per wave.
+__host__ __device__ __forceinline__ float div_markstein(float a, float b, float y) {
+  const float q0 = a * y;
+  const float r0 = __builtin_fmaf(-q0, b, a);
+  const float q1 = __builtin_fmaf(r0, y, q0);
+  const float r1 = __builtin_fmaf(-q1, b, a);
+  return __builtin_fmaf(r1, y, q1);
+}
+// Valid domain, double: 2^-900 <= |a| <= 2^900 (or a = +0) with 2^-100 <= |b| <= 2^100 normal and y = RN(1 / b): then q0 b and every
+// residual (|r| <= 2^-51 |a|) are normal numbers, nothing overflows, and the theorem applies. Outside it the sequence is wrong the
+// way the float one is; in particular it loses the sign of a = -0 (returns +0 where a / b is -0 for b > 0). There is no guard: the
+// callers pass differences of non-negative magnitudes (x - y of equal values is +0 under round-to-nearest, never -0), floored powers
+// and their x log x, all between 1e-15 and 1e15.
+__host__ __device__ __forceinline__ double div_markstein(double a, double b, double y) {
+  const double q0 = a * y;
+  const double r0 = __builtin_fma(-q0, b, a);
+  const double q1 = __builtin_fma(r0, y, q0);
+  const double r1 = __builtin_fma(-q1, b, a);
+  return __builtin_fma(r1, y, q1);
+}
+// The float guards: true = this numerator needs the division itself. A caller ORs it over the values of a lane and takes the
+// sequence only when div_wave_is_safe() says that no lane of the wave has one (wave-uniform: no divergent mix of the two forms).
+//  - any sign (cAcf's normalisation, the delta regression): outside 2^-60 < |a| < 2^60 -- zeros, subnormals, tiny, huge, infinite, NaN
+__host__ __device__ __forceinline__ bool div_needs_division(float a) {
+  const float m = __builtin_fabsf(a);
+  return !(m > 0x1p-60f && m < 0x1p60f);
+}
+//  - values that are never negative (the summation spectrum of f0_shs, where +0 is common and the sequence returns +0 for it): a value
+//    in (0, 2^-100), an infinity or a NaN; anything with the sign bit set lands in the second test as well
+__host__ __device__ __forceinline__ bool div_needs_division_nonneg(float a) {
+  const uint32_t u = __builtin_bit_cast(uint32_t, a);
+  return (u - 1u) < (0x0d800000u - 1u) || u >= 0x7f800000u;
+}
+//  - the divisor (where it is not a constant): 2^-30 < b < 2^30
+__host__ __device__ __forceinline__ bool div_divisor_is_safe(float b) { return b > 0x1p-30f && b < 0x1p30f; }
+__device__ __forceinline__ bool div_wave_is_safe(bool lane_needs_division) { return __builtin_amdgcn_ballot_w64(lane_needs_division) == 0; }
 
 // smileMath_quadFrom3pts (smileUtil.c:1009-1033)
 __device__ __forceinline__ double quad_vertex(double x1, double y1, double x2, double y2, double x3, double y3, double &y) {

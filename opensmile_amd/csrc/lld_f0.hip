@@ -425,25 +425,22 @@ __device__ __forceinline__ int f0_shs(const F0Tbl &T, const F0Params &Q, int lan
     }
   // sum / nHarmonics (pitchShs.cpp:255). The chain's rows are >= +0: there the quotient is formed from the divisor's correctly rounded
   // reciprocal (one division per frame) by a product and two residual corrections -- five full-rate operations per bin instead of the
-  // division sequence's eleven (one of them a reciprocal) --, the correctly rounded quotient for every mantissa and every divisor
-  // 1 .. 32 (tools/ubench/div_f32_by_const_check.hip: all 2^23 x 32 x 10 exponents equal the division's bits) as long as the
-  // residuals do not underflow: a frame with a value in (0, 2^-100) takes the division (wave-uniform choice).
+  // division sequence's eleven (one of them a reciprocal) --, the correctly rounded quotient for every significand and every divisor
+  // 1 .. 32 (div_markstein, lld_device.hpp; tests/test_gpu_device_math.py: on the device, through this guard, all 2^23 significands
+  // at every normal exponent equal the division's bits) as long as the residuals do not underflow and the value is finite: a frame
+  // with a value in (0, 2^-100), an infinity or a NaN takes the division (wave-uniform choice; +inf / nh is +inf, the sequence's
+  // residual inf - inf a NaN).
   const float nh = (float)Q.n_harm;
   bool fast_div = false;
   if constexpr (CHAIN) {
-    bool tiny = false;
-    F0_FOR_BINS(m, j) tiny |= (__float_as_uint(hv[m]) - 1u) < (0x0d800000u - 1u);     // 0 < hv < 2^-100 (hv is never negative here)
-    fast_div = !__any(tiny);
+    bool odd = false;
+    F0_FOR_BINS(m, j) odd |= div_needs_division_nonneg(hv[m]);                        // (hv is never negative here)
+    fast_div = div_wave_is_safe(odd);
   }
   if (fast_div) {
     const float y = 1.0f / nh;
     F0_FOR_BINS(m, j) {
-      const float a = hv[m];
-      const float q0 = a * y;
-      const float r0 = __builtin_fmaf(-q0, nh, a);
-      const float q1 = __builtin_fmaf(r0, y, q0);
-      const float r1 = __builtin_fmaf(-q1, nh, a);
-      float s = __builtin_fmaf(r1, y, q1);
+      float s = div_markstein(hv[m], nh, y);
       if (s < 0) s = 0.0f;
       hv[m] = s;
     }
@@ -800,20 +797,10 @@ __global__ void __launch_bounds__(F0G<LOGM>::kSpecWaves * 64) lld_f0_spec_g(LldP
   f0_spec_body<LOGM, true>(P, Q);
 }
 
-// RN(a / b) for a divisor whose correctly rounded reciprocal y = RN(1 / b) is known (host table): q0 = RN(a y) is within two
-// ulps of the quotient, one residual correction makes it a faithful rounding, and a second one -- Markstein's theorem: y
-// correctly rounded, q faithful, the residual a - b q exact in one FMA -- returns the correctly rounded quotient, which is
-// what the division instruction sequence (and the reference's divsd) returns. Five full-rate operations instead of the
-// ~14 of v_div_scale / v_rcp_f64 / refinement / v_div_fmas / v_div_fixup. No overflow / underflow here: the operands are
-// differences of spectrum magnitudes (floats widened) and products of octave-axis distances, 1e-5 .. 2.
-// tests/test_exact_sum_claims.py runs the same sequence against the division on the tables' divisors.
-__device__ __forceinline__ double f0_div_by(double a, double b, double y) {
-  const double q0 = a * y;
-  const double r0 = __builtin_fma(-q0, b, a);
-  const double q1 = __builtin_fma(r0, y, q0);
-  const double r1 = __builtin_fma(-q1, b, a);
-  return __builtin_fma(r1, y, q1);
-}
+// The sweep's divisions: div_markstein (lld_device.hpp) with the reciprocals of the host table (sw_rec: d1, RN(1 / d1), d2, RN(1 / d2))
+// instead of the ~14 operations of v_div_scale / v_rcp_f64 / refinement / v_div_fmas / v_div_fixup. Inside its domain: the operands
+// are differences of spectrum magnitudes (floats widened; equal values give +0) and products of octave-axis distances, 1e-5 .. 2.
+// tests/test_gpu_device_math.py runs it on the device with this table's divisors.
 
 // One frame per thread, one 64-frame tile per wave (see the overview above). A round is one 16-bin block: the lane's
 // 64-byte line of magnitudes; the next block's line is requested before the current block's arithmetic. The blocks that
@@ -945,7 +932,7 @@ __global__ void __launch_bounds__(kSweepWaves * 64) lld_f0_sweep(F0Params Q) {
       const int i = 16 * bb + e;
       if (!decltype(edge)::value || (i >= 1 && i <= kK - 2)) {
         const ConstD r = sw + 8 * i;
-        const double s6 = 6.0 * (f0_div_by(yv[e + 2] - yv[e + 1], r[3], r[4]) - f0_div_by(yv[e + 1] - yv[e], r[5], r[6]));
+        const double s6 = 6.0 * (div_markstein(yv[e + 2] - yv[e + 1], r[3], r[4]) - div_markstein(yv[e + 1] - yv[e], r[5], r[6]));
         up = r[1] * (s6 - r[0] * up);
         u[e] = up;
       } else {

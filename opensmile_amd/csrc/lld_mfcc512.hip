@@ -423,17 +423,12 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
     return num;
   };
   // straight-line form for a pass none of whose indices is clamped: own registers and the two neighbour groups; the quotient by
-  // Markstein's sequence (see lld_ooura_quad.hpp; tests/helpers/markstein_f32.c checks the divisor 10). `plain`: a numerator
+  // Markstein's sequence (div_markstein, lld_device.hpp; tests/test_gpu_device_math.py checks the divisor 10 on the device). `plain`: a numerator
   // outside the range the sequence is safe for (zero keeps its sign only under the division) -> the pass takes delta_exact.
   const auto div10 = [](float a, bool &plain) {
     const float y = 0.1f, b = 10.0f;              // y = RN(1 / 10); norm = 2 (1 + 4), deltaRegression.cpp:77-79
-    const float m = fabsf(a);
-    plain |= !(m > 0x1p-60f && m < 0x1p60f);
-    const float q0 = a * y;
-    const float r0 = __builtin_fmaf(-q0, b, a);
-    const float q1 = __builtin_fmaf(r0, y, q0);
-    const float r1 = __builtin_fmaf(-q1, b, a);
-    return __builtin_fmaf(r1, y, q1);
+    plain |= div_needs_division(a);
+    return div_markstein(a, b, y);
   };
   const auto delta_fast = [&](float s_cur, float dp, float &dn, float &ddn, float &drow, bool &plain) {
     const float s1 = from_group((g + 1) & 3, g == 0 ? s_cur : s_prev);     // (the SOURCE lane chooses: group 0 holds frame btp, the others btp - 3 ..)

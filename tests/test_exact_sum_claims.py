@@ -98,8 +98,7 @@ def test_float_division_by_a_known_divisor_in_five_operations(tmp_path):
 def test_float_division_by_the_number_of_harmonics_in_five_operations(tmp_path):
     """lld_f0_cand's f0_shs (round 6) divides the summation spectrum by nHarmonics the same way -- y = RN(1 / b), a product, two residual
     corrections -- when no value of the frame lies in (0, 2^-100). Every dividend significand for every divisor 1 .. 32 (the same
-    statement on the device's own instructions, with ten exponents of the dividend: tools/ubench/div_f32_by_const_check.hip,
-    profiles/r06_div_f32_by_const_check.json)."""
+    statement on the device, for the kernels' own helper behind its guard and every normal exponent: tests/test_gpu_device_math.py)."""
     import os
     import subprocess
     src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers", "markstein_f32.c")
@@ -108,3 +107,50 @@ def test_float_division_by_the_number_of_harmonics_in_five_operations(tmp_path):
     out = subprocess.run([exe] + [str(b) for b in range(1, 33)], check=True, capture_output=True, text=True).stdout
     assert int(out) == 0
 
+
+def test_float_quotient_guards_agree_on_what_takes_the_division(tmp_path):
+    """The three kernels that divide floats by div_markstein (lld_device.hpp) choose between the sequence and the division with two
+    guards: div_needs_division (cAcf's normalisation and the delta regression: |a| outside (2^-60, 2^60)) and
+    div_needs_division_nonneg (f0_shs, whose values are never negative and often +0: (0, 2^-100), or not finite). The header is
+    compiled for the host and both are applied to a table of boundary values: each answers what its range says; neither lets an
+    infinity or a NaN through; and wherever a guard lets a value of its domain through, the sequence returns the division's bits
+    for the chains' divisors (so the guards may differ only where both forms are right)."""
+    import os
+    import struct
+    import subprocess
+    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers", "div_guard_check.cpp")
+    exe = str(tmp_path / "div_guard_check")
+    subprocess.run(["/opt/rocm/bin/hipcc", "--cuda-host-only", "-x", "hip", "-O2", "-std=c++17", "-ffp-contract=off", "-o", exe, src], check=True)
+
+    def bits(x):
+        return struct.unpack("<I", struct.pack("<f", x))[0]
+
+    def nxt(u, d):
+        return u + d
+    p100, m60, p60, inf = bits(2.0 ** -100), bits(2.0 ** -60), bits(2.0 ** 60), 0x7f800000
+    # value -> (any-sign guard says division, never-negative guard says division)
+    table = {
+        0x00000000: (1, 0), 0x00000001: (1, 1), 0x007fffff: (1, 1), 0x00800000: (1, 1),
+        nxt(p100, -1): (1, 1), p100: (1, 0), nxt(p100, 1): (1, 0),
+        nxt(m60, -1): (1, 0), m60: (1, 0), nxt(m60, 1): (0, 0), bits(1e-5): (0, 0), bits(1.0): (0, 0), bits(32768.0): (0, 0),
+        nxt(p60, -1): (0, 0), p60: (1, 0), nxt(p60, 1): (1, 0), 0x7f7fffff: (1, 0),
+        inf: (1, 1), 0x7fc00000: (1, 1), 0x7f800001: (1, 1),
+    }
+    for u, (g0, _) in list(table.items()):
+        if u <= inf:
+            table[u | 0x80000000] = (g0, 1)              # the sign bit: the same answer by magnitude / always the division
+    divisors = [str(b) for b in range(1, 33)] + ["10", "129", "257", "513", "1025", "2049", "3", "16777215", "1.9999999", "1.0000001"]
+    out = subprocess.run([exe] + divisors + ["-"] + [f"{u:08x}" for u in table], check=True, capture_output=True, text=True).stdout
+    rows = {int(f[0], 16): tuple(int(v) for v in f[1:]) for f in (line.split() for line in out.splitlines())}
+    assert set(rows) == set(table)
+    for u, (g0, g1) in table.items():
+        any_sign, nonneg, seq_ok = rows[u]
+        assert (any_sign, nonneg) == (g0, g1), f"{u:#010x}: guards say {(any_sign, nonneg)}, their ranges say {(g0, g1)}"
+        if (u & 0x7fffffff) >= inf:
+            assert any_sign and nonneg, f"{u:#010x}: a non-finite value must take the division under every guard"
+        if not any_sign:
+            assert seq_ok, f"{u:#010x}: passed by div_needs_division, but the sequence differs from the division"
+        if not nonneg and not (u & 0x80000000):
+            assert seq_ok, f"{u:#010x}: passed by div_needs_division_nonneg, but the sequence differs from the division"
+    # and the guards are needed: the sequence is wrong for -0 and for the infinities
+    assert not rows[0x80000000][2] and not rows[inf][2] and not rows[inf | 0x80000000][2]

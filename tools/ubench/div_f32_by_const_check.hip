@@ -3,6 +3,8 @@
 // the division instruction sequence (IEEE, correctly rounded): every one of the 2^23 mantissas of a at the exponents given (a
 // quotient's rounding does not depend on a's exponent as long as nothing under- or overflows; -100 is the guard of the kernel, the
 // others are ordinary), every divisor 1 .. 32. Prints the number of differing results (must be 0).
+// (Historical: it checks a COPY of the sequence at ten exponents. tests/test_gpu_device_math.py supersedes it -- the product's own
+// div_markstein behind its guards, every normal exponent, special values.)
 // Build: hipcc --offload-arch=gfx950 -O2 -ffp-contract=off div_f32_by_const_check.hip -o div_f32_by_const_check
 #include <hip/hip_runtime.h>
 #include <cstdio>

@@ -1,5 +1,6 @@
 // Exhaustive check of sqrt_rn_normal (lld_device.hpp: v_sqrt_f32 + the library's two residual tests, WITHOUT its scaling of small
 // arguments and its zero / infinity test) against sqrtf for every float in [2^-96, infinity): prints the number of differing results.
+// (Historical: a copy of the sequence. tests/test_gpu_device_math.py supersedes it: sqrt_rn_batch itself over all 2^32 patterns.)
 // Build: hipcc --offload-arch=gfx950 -O2 -ffp-contract=off sqrt_f32_normal_check.hip -o sqrt_f32_normal_check
 #include <hip/hip_runtime.h>
 #include <cstdio>
