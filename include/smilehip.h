@@ -990,6 +990,55 @@ int smilehip_jitter_stream_push_frames(smilehip_jitter_stream *s, const float *f
                                        int64_t pcm_start, int64_t n_pcm, float *out5, int64_t *last_idx, int64_t *last_mis);
 int smilehip_jitter_stream_destroy(smilehip_jitter_stream *s);
 
+/* ---- cSpecScale on every target scale (src/dsp/specScale.cpp): log with any base, semitone, linear, bark, bao (the pre-2.0 bark
+ * approximation) and mel, any number of target points, an explicit maxF, each of the three switches. smilehip_specscale_frames
+ * above keeps serving the octave axis of the F0 chains (its plan's tables); this operator takes everything else -- and the octave
+ * axis too, with the same bits. `scale` uses the reference's SPECTSCALE_* values (src/include/smileutil/smileUtil.h:330-337). The
+ * options are the configuration's own: logScaleBase <= 0 or == 1 becomes 2 and the auditory weighting is dropped on anything but
+ * log base 2 (myFetchConfig, specScale.cpp:100-127, 164-170), minF < 1 becomes 1 (:173-177), maxF <= minF or above the spectrum's
+ * top becomes the top (dataProcessorCustomFinalise, :254-258). */
+#define SMILEHIP_SPECSCALE_LINEAR 0
+#define SMILEHIP_SPECSCALE_LOG 1
+#define SMILEHIP_SPECSCALE_BARK 2
+#define SMILEHIP_SPECSCALE_MEL 3
+#define SMILEHIP_SPECSCALE_SEMITONE 4
+#define SMILEHIP_SPECSCALE_BARK_OLD 7
+typedef struct smilehip_specscale_opts {
+  int32_t scale;            /* SMILEHIP_SPECSCALE_LOG / SEMITONE / LINEAR / BARK / BARK_OLD / MEL */
+  double  param;            /* logScaleBase or firstNote */
+  double  min_f, max_f;     /* as the conf gives them (max_f -1 = the spectrum's top) */
+  int32_t n_points_target;  /* <= 0: n_src */
+  int32_t spec_enhance, spec_smooth, auditory_weighting;
+} smilehip_specscale_opts;
+typedef struct smilehip_specscale_op smilehip_specscale_op;
+/* cSpecScale::dataProcessorCustomFinalise (specScale.cpp:248-321) with smileMath_cspline_init / smileMath_csplint_init
+ * (src/smileutil/smileUtilSpline.c:138-153, 295-342) for n_src (4 .. 8193) magnitudes of a level whose frameSizeSec is
+ * frame_size_sec; 2 .. 16384 target points. SMILEHIP_ERR_INVALID, with the cause in smilehip_last_error, where the reference's own
+ * setup is undefined: a source axis that does not increase on the target scale, an interval of width zero, a failed
+ * smileMath_csplint_init (the reference then dereferences a null cache), nPointsTarget = 1. */
+int smilehip_specscale_op_create(smilehip_context *ctx, const smilehip_specscale_opts *opts, int64_t n_src, double frame_size_sec,
+                                 smilehip_specscale_op **out);
+int smilehip_specscale_op_n_out(const smilehip_specscale_op *op);     /* nPointsTarget (setupNewNames, specScale.cpp:215-217) */
+/* cSpecScale::processVector (specScale.cpp:326-377: smileDsp_specEnhanceSHS / smileDsp_specSmoothSHS, src/smileutil/smileUtil.c:
+ * 1965-2014; smileMath_cspline / smileMath_csplint, smileUtilSpline.c:155-211, 344-357; the auditory weighting) on n_frames
+ * independent rows of n_src magnitudes -> rows of n_out values; every operation the reference's double operation in its order. The
+ * operator keeps a scratch of two doubles per source bin for the rows of one chunk (at most 512 MiB; longer batches are walked in
+ * chunks). It is allocated by the first call for that call's rows, not at create, where the caller's batch size is not known: a
+ * component instance inside the binary moves a few hundred rows, a batch run 65 536. A later call with more rows than the scratch
+ * holds replaces it by one at least twice as large, behind a device-wide synchronise (so at most ~log2 of the largest batch
+ * reallocations per operator; callers that know their largest batch make it their first call). Calls on one operator go one after
+ * the other. */
+int smilehip_specscale_op_frames(smilehip_specscale_op *op, const float *d_src, int64_t ld_src, float *d_dst, int64_t ld_dst,
+                                 int64_t n_frames, void *stream);
+int smilehip_specscale_op_destroy(smilehip_specscale_op *op);
+/* The operator's host tables without a device (what smilehip_specscale_op_create uploads), for callers that want the axis and for
+ * the tests: returns nPointsTarget, or a negative value where smilehip_specscale_op_create refuses. Every output is optional:
+ * f_t [n_src] the source bins on the target axis; spline [n_src x 5] sigma, diff1, diff2 of smileMath_cspline_init and p, y2 of
+ * smileMath_cspline's forward sweep (smileUtilSpline.c:181-184: they do not depend on the spectrum), rows 1 .. n_src-2; k [n_tgt]
+ * and rec [n_tgt x 4] = a, c, d of smileMath_csplint_init and the auditory weight (1 where the weighting is off). */
+int smilehip_specscale_tables(const smilehip_specscale_opts *opts, int64_t n_src, double frame_size_sec, double *f_t, double *spline,
+                              int32_t *k, double *rec);
+
 #ifdef __cplusplus
 }
 #endif

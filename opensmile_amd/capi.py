@@ -112,6 +112,24 @@ def spectral_opts(bands, rolloff=(0.25, 0.5, 0.75, 0.9), slopes=(), **flags):
     return o
 
 
+class SpecScaleOpts(C.Structure):
+    """smilehip_specscale_opts (include/smilehip.h): cSpecScale on any target scale"""
+    _fields_ = [("scale", C.c_int32), ("param", C.c_double), ("min_f", C.c_double), ("max_f", C.c_double), ("n_points_target", C.c_int32),
+                ("spec_enhance", C.c_int32), ("spec_smooth", C.c_int32), ("auditory_weighting", C.c_int32)]
+
+
+# SMILEHIP_SPECSCALE_*: the reference's SPECTSCALE_* values, by the configuration's name for the scale
+SPECSCALE = {"lin": 0, "log": 1, "bark": 2, "mel": 3, "sem": 4, "bao": 7}
+
+
+def specscale_opts(scale, param=0.0, min_f=25.0, max_f=-1.0, n_points_target=0, spec_enhance=0, spec_smooth=0, auditory_weighting=0):
+    o = SpecScaleOpts()
+    o.scale = SPECSCALE[scale] if isinstance(scale, str) else int(scale)
+    o.param, o.min_f, o.max_f, o.n_points_target = float(param), float(min_f), float(max_f), int(n_points_target)
+    o.spec_enhance, o.spec_smooth, o.auditory_weighting = int(spec_enhance), int(spec_smooth), int(auditory_weighting)
+    return o
+
+
 class Geometry(C.Structure):
     """smilehip_geometry"""
     _fields_ = [("frame_size", C.c_int64), ("frame_step", C.c_int64), ("fft_size", C.c_int64),
@@ -272,6 +290,11 @@ SYMBOLS = {
     "smilehip_intensity_frames": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _vp]),
     "smilehip_vecop_frames": (C.c_int, [_vp, _i32, _f32, _f32, _vp, _i64, _i32, _vp, _i64, _i64, _vp]),
     "smilehip_pitch_smoother_rows": (C.c_int, [_vp, _i32, _f32, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _i64, _vp, _i32, _vp, _i64, _vp, _vp]),
+    "smilehip_specscale_op_create": (C.c_int, [_vp, _vp, _i64, _dbl, _vp]),
+    "smilehip_specscale_op_n_out": (C.c_int, [_vp]),
+    "smilehip_specscale_op_frames": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp]),
+    "smilehip_specscale_op_destroy": (C.c_int, [_vp]),
+    "smilehip_specscale_tables": (C.c_int, [_vp, _i64, _dbl, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

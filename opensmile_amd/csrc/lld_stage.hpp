@@ -78,6 +78,19 @@ struct SpectralGeneral {
   int32_t n_slopes, sl_iL[16], sl_iR[16];               // slopes[]: edge bins, their weights, idxR - idxL (:872-943)
   double sl_wL[16], sl_wR[16], sl_Nind[16];
 };
+// cSpecScale, any target scale (lld_specscale.hip): the device tables of make_specscale_tables and the operator's scratch
+struct SpecScaleDev {
+  int32_t n_src, n_tgt, nb8;                            // nb8: 8-bin blocks of a row, ceil(n_src / 8)
+  int32_t enhance, smooth, weighting;
+  const double *spline;                                 // [n_src x 5] sigma, diff1, diff2, p, y2 of the forward sweep
+  const int32_t *ip_k;                                  // [n_tgt]
+  const double *ip_rec;                                 // [n_tgt x 4] a, c, d, auditory weight
+  double *y, *u;                                        // scratch, [rows of a chunk, rounded up to 64][8 nb8] each, blocked (lld_specscale.hip)
+  int64_t chunk_rows;                                   // rows the scratch holds (a multiple of 64)
+};
+hipError_t stage_specscale_general_prepare(const SpecScaleDev &S);   // once per operator, before the first rows
+hipError_t stage_specscale_general(const SpecScaleDev &S, const float *src, int64_t ld_src, float *dst, int64_t ld_dst, int64_t n_frames,
+                                   hipStream_t s);
 hipError_t stage_mfcc_inverse(const float *src, int64_t lds, float *dst, int64_t ldd, int64_t nF, int n_bands, int first, int last, int htk,
                               int do_log, const float *rows, const float *lifter, hipStream_t s);
 hipError_t stage_spectral_general(const SpectralGeneral &G, const float *mag, int64_t ld_src, float *state, int first, float *dst,

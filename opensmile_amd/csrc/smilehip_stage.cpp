@@ -149,6 +149,77 @@ extern "C" int smilehip_spectral_op_frames(smilehip_spectral_op *op, const float
   STAGE_RET(stage_spectral_general(op->G, d_mag, ld_src, d_state, first, d_dst, ld_dst, n_frames, (hipStream_t)stream), "spectral (general)");
 }
 
+// ---- cSpecScale on any target scale: an operator object (the axes and the spline's caches are functions of the options and the
+// level's geometry alone: cSpecScale::dataProcessorCustomFinalise, src/dsp/specScale.cpp:248-321)
+struct smilehip_specscale_op {
+  smilehip_context *ctx = nullptr;
+  SpecScaleDev S{};
+  DevBuf<double> d_spline, d_rec, d_scratch;
+  DevBuf<int32_t> d_k;
+  int64_t max_chunk_rows = 64;
+};
+// the scratch (two doubles per source bin and row) holds at most this much; longer batches are walked in chunks
+static constexpr size_t kSpecScaleScratchBytes = (size_t)512 << 20;
+extern "C" int smilehip_specscale_op_destroy(smilehip_specscale_op *op) {
+  delete op;
+  return SMILEHIP_OK;
+}
+extern "C" int smilehip_specscale_op_n_out(const smilehip_specscale_op *op) { return op ? op->S.n_tgt : -1; }
+extern "C" int smilehip_specscale_tables(const smilehip_specscale_opts *o, int64_t n_src, double frame_size_sec, double *f_t, double *spline,
+                                         int32_t *k, double *rec) {
+  if (!o) return fail(SMILEHIP_ERR_INVALID, "smilehip_specscale_tables: null argument");
+  SpecScaleHost h;
+  const char *why = "";
+  const int rc = make_specscale_tables(*o, n_src, frame_size_sec, h, &why);
+  if (rc) return fail(rc, "cSpecScale (%lld bins, frame size %g s): %s", (long long)n_src, frame_size_sec, why);
+  if (f_t) std::memcpy(f_t, h.f_t.data(), h.f_t.size() * sizeof(double));
+  if (spline) std::memcpy(spline, h.spline.data(), h.spline.size() * sizeof(double));
+  if (k) std::memcpy(k, h.ip_k.data(), h.ip_k.size() * sizeof(int32_t));
+  if (rec) std::memcpy(rec, h.ip_rec.data(), h.ip_rec.size() * sizeof(double));
+  return h.n_tgt;
+}
+extern "C" int smilehip_specscale_op_create(smilehip_context *ctx, const smilehip_specscale_opts *o, int64_t n_src, double frame_size_sec,
+                                            smilehip_specscale_op **out) {
+  if (!ctx || !o || !out) return fail(SMILEHIP_ERR_INVALID, "smilehip_specscale_op_create: null argument");
+  SpecScaleHost h;
+  const char *why = "";
+  int rc = make_specscale_tables(*o, n_src, frame_size_sec, h, &why);
+  if (rc) return fail(rc, "cSpecScale (%lld bins, frame size %g s): %s", (long long)n_src, frame_size_sec, why);
+  std::unique_ptr<smilehip_specscale_op> op(new smilehip_specscale_op);
+  op->ctx = ctx;
+  if ((rc = op->d_spline.upload(h.spline)) || (rc = op->d_rec.upload(h.ip_rec)) || (rc = op->d_k.upload(h.ip_k))) return rc;
+  SpecScaleDev &S = op->S;
+  S.n_src = h.n_src; S.n_tgt = h.n_tgt; S.nb8 = (h.n_src + 7) / 8;
+  S.enhance = o->spec_enhance != 0; S.smooth = o->spec_smooth != 0; S.weighting = h.weighting;
+  S.spline = op->d_spline.p; S.ip_k = op->d_k.p; S.ip_rec = op->d_rec.p;
+  const size_t row_bytes = (size_t)S.nb8 * 8 * 2 * sizeof(double);
+  op->max_chunk_rows = std::max<int64_t>(64, std::min<int64_t>(65536, (int64_t)(kSpecScaleScratchBytes / row_bytes) / 64 * 64));
+  HIP_TRY(stage_specscale_general_prepare(S));
+  *out = op.release();
+  return SMILEHIP_OK;
+}
+extern "C" int smilehip_specscale_op_frames(smilehip_specscale_op *op, const float *d_src, int64_t ld_src, float *d_dst, int64_t ld_dst,
+                                            int64_t n_frames, void *stream) {
+  if (!op) return fail(SMILEHIP_ERR_INVALID, "smilehip_specscale_op_frames: null operator");
+  int rc = check_frames(d_src, d_dst, ld_src, ld_dst, n_frames, op->S.n_src, op->S.n_tgt, "smilehip_specscale_op_frames");
+  if (rc) return rc;
+  if (n_frames == 0) return SMILEHIP_OK;
+  // the scratch: allocated with the first rows; a later call with more rows than it holds replaces it by one at least twice as
+  // large (up to the limit), after the device has finished whatever still reads the old block
+  const int64_t need = std::min<int64_t>(op->max_chunk_rows, (n_frames + 63) / 64 * 64);
+  if (need > op->S.chunk_rows) {
+    const int64_t want = std::min<int64_t>(op->max_chunk_rows, std::max<int64_t>(need, 2 * op->S.chunk_rows));
+    if (op->S.chunk_rows > 0) HIP_TRY(hipDeviceSynchronize());
+    const size_t per = (size_t)want * op->S.nb8 * 8;
+    op->S.chunk_rows = 0;
+    if ((rc = op->d_scratch.alloc(2 * per))) return rc;
+    op->S.y = op->d_scratch.p;
+    op->S.u = op->d_scratch.p + per;
+    op->S.chunk_rows = want;
+  }
+  STAGE_RET(stage_specscale_general(op->S, d_src, ld_src, d_dst, ld_dst, n_frames, (hipStream_t)stream), "specscale (general)");
+}
+
 extern "C" int smilehip_preemphasis_frames(smilehip_context *ctx, const float *d_src, int64_t ld_src, float *d_dst,
                                            int64_t ld_dst, int64_t n_frames, int64_t N, float k, int de, void *stream) {
   if (!ctx || N < 1) return fail(SMILEHIP_ERR_INVALID, "smilehip_preemphasis_frames: bad argument");

@@ -317,4 +317,141 @@ int make_f0_tables(int64_t K, double fft_frame_size_sec, int n_harmonics, float 
   return SMILEHIP_OK;
 }
 
+// smileDsp_specScaleTransfFwd (src/smileutil/smileUtil.c:1097-1147) for the scales cSpecScale::myFetchConfig can select
+static double specscale_fwd(double x, int scale, double param) {
+  switch (scale) {
+    case SMILEHIP_SPECSCALE_LOG:
+      if (x > 0) return std::log(x) / std::log(param);
+      return 0.0;
+    case SMILEHIP_SPECSCALE_SEMITONE:
+      if (x / param > 1.0) return 12.0 * (std::log(x / param) / std::log(2.0));
+      return 0.0;
+    case SMILEHIP_SPECSCALE_BARK_OLD:
+      if (x > 0) return (26.81 / (1.0 + 1960.0 / x)) - 0.53;
+      return 0.0;
+    case SMILEHIP_SPECSCALE_BARK:
+      if (x > 0) {
+        const double zz = (26.81 / (1.0 + 1960.0 / x)) - 0.53;
+        if (zz < 2) return (0.85 * zz + 0.3);
+        else if (zz > 20.1) return (1.22 * zz - 0.22 * 20.1);
+        return zz;
+      }
+      return 0.0;
+    case SMILEHIP_SPECSCALE_MEL:
+      if (x > 0.0) return 1127.0 * std::log(1.0 + x / 700.0);
+      return 0.0;
+    default:
+      return x;
+  }
+}
+
+// cSpecScale::myFetchConfig's clamps (src/dsp/specScale.cpp:151-186), setupNewNames' deltaF and nPointsTarget (:214-217),
+// dataProcessorCustomFinalise (:248-321), smileMath_cspline_init / smileMath_csplint_init (src/smileutil/smileUtilSpline.c:138-153,
+// 295-342) and the data-independent half of smileMath_cspline (:172-184: y2 of the forward sweep never sees the spectrum). Where
+// the reference's own setup is undefined -- a source axis that does not increase, NaN tables, a failed csplint_init whose null
+// cache processVector then dereferences, one target point -- the geometry is refused by name.
+int make_specscale_tables(const smilehip_specscale_opts &o, int64_t n_src, double frame_size_sec, SpecScaleHost &h, const char **why) {
+  const char *dummy;
+  if (!why) why = &dummy;
+  *why = "";
+  const int scale = o.scale;
+  if (scale != SMILEHIP_SPECSCALE_LOG && scale != SMILEHIP_SPECSCALE_SEMITONE && scale != SMILEHIP_SPECSCALE_LINEAR &&
+      scale != SMILEHIP_SPECSCALE_BARK && scale != SMILEHIP_SPECSCALE_BARK_OLD && scale != SMILEHIP_SPECSCALE_MEL) {
+    *why = "unknown target scale";
+    return SMILEHIP_ERR_INVALID;
+  }
+  if (n_src < 4 || n_src > 8193) { *why = "4 .. 8193 source bins are built"; return SMILEHIP_ERR_INVALID; }
+  if (!(frame_size_sec > 0.0)) { *why = "the level's frameSizeSec must be positive"; return SMILEHIP_ERR_INVALID; }
+  const int64_t n_tgt = o.n_points_target <= 0 ? n_src : (int64_t)o.n_points_target;
+  if (n_tgt == 1) { *why = "nPointsTarget = 1: the target axis' step is a division by zero"; return SMILEHIP_ERR_INVALID; }
+  if (n_tgt > 16384) { *why = "2 .. 16384 target points are built"; return SMILEHIP_ERR_INVALID; }
+  double param = 0.0;
+  if (scale == SMILEHIP_SPECSCALE_LOG) {
+    param = o.param;
+    if ((param <= 0.0) || (param == 1.0)) param = 2.0;
+  } else if (scale == SMILEHIP_SPECSCALE_SEMITONE) {
+    param = o.param;
+  }
+  const int nMag = (int)n_src, nPointsTarget = (int)n_tgt;
+  const double deltaF = 1.0 / (double)(float)frame_size_sec;
+  double minF = o.min_f, maxF = o.max_f;
+  if (minF < 1.0) minF = 1.0;
+  const double samplF = deltaF * (double)(nMag - 1);
+  if ((maxF <= minF) || (maxF > samplF)) maxF = samplF;
+  const double fmin_t = specscale_fwd(minF, scale, param);
+  const double fmax_t = specscale_fwd(maxF, scale, param);
+  const double deltaF_t = (fmax_t - fmin_t) / (nPointsTarget - 1);
+  h.n_src = nMag; h.n_tgt = nPointsTarget;
+  h.min_f = minF; h.max_f = maxF; h.fmin_t = fmin_t; h.fmax_t = fmax_t;
+  std::vector<double> &x = h.f_t;
+  x.assign((size_t)nMag, 0.0);
+  if (scale == SMILEHIP_SPECSCALE_LOG) {
+    for (int i = 1; i < nMag; i++) x[i] = specscale_fwd((double)i * (double)deltaF, scale, param);
+    x[0] = 2.0 * x[1] - x[2];
+  } else {
+    for (int i = 0; i < nMag; i++) x[i] = specscale_fwd((double)i * (double)deltaF, scale, param);
+  }
+  for (int i = 1; i < nMag; i++)
+    if (!(x[i] > x[i - 1])) {                             // (also catches NaN / Inf axes: a log base whose logarithm underflows, ...)
+      *why = "the source bins do not increase on the target axis (sem: firstNote at or above the bin spacing; bao: a bin spacing below about 39.5 Hz)";
+      return SMILEHIP_ERR_INVALID;
+    }
+  h.spline.assign((size_t)nMag * 5, 0.0);
+  double y2_prev = 0.0;                                   // y2[0] = 0 (natural boundary, y1p = 1e30)
+  for (int i = 1; i < nMag - 1; i++) {
+    const double sigma = (x[i] - x[i - 1]) / (x[i + 1] - x[i - 1]);
+    const double diff1 = (x[i + 1] - x[i]) * (x[i + 1] - x[i - 1]);
+    const double diff2 = (x[i] - x[i - 1]) * (x[i + 1] - x[i - 1]);
+    if (diff1 == 0.0 || diff2 == 0.0 || !std::isfinite(diff1) || !std::isfinite(diff2)) {
+      *why = "the source bins lie too close on the target axis: a spline interval's width underflows";
+      return SMILEHIP_ERR_INVALID;
+    }
+    const double p = 1.0 / (sigma * y2_prev + 2.0);
+    const double y2 = (sigma - 1.0) * p;
+    double *r = &h.spline[(size_t)i * 5];
+    r[0] = sigma; r[1] = diff1; r[2] = diff2; r[3] = p; r[4] = y2;
+    y2_prev = y2;
+  }
+  h.ip_k.assign((size_t)nPointsTarget, 0);
+  h.ip_rec.assign((size_t)nPointsTarget * 4, 0.0);
+  const double xt_first = fmin_t + (double)0 * deltaF_t, xt_last = fmin_t + (double)(nPointsTarget - 1) * deltaF_t;
+  if (!std::isfinite(xt_first) || !std::isfinite(xt_last)) { *why = "the target axis is not finite"; return SMILEHIP_ERR_INVALID; }
+  if (xt_first < x[0] || xt_last > x[nMag - 1]) {
+    *why = "smileMath_csplint_init fails in the reference: a target point lies outside the source axis";
+    return SMILEHIP_ERR_INVALID;
+  }
+  long kupper = 1;
+  for (int i = 0; i < nPointsTarget; i++) {
+    const double xt = fmin_t + (double)i * deltaF_t;
+    while (kupper < nMag && x[kupper] < xt) kupper++;
+    if (kupper == nMag) {
+      *why = "smileMath_csplint_init fails in the reference: a target point lies outside the source axis";
+      return SMILEHIP_ERR_INVALID;
+    }
+    const long klower = kupper - 1;
+    const double range = x[kupper] - x[klower];
+    if (range == 0.0) { *why = "smileMath_csplint_init fails in the reference: a source interval of width zero"; return SMILEHIP_ERR_INVALID; }
+    const double a = (x[kupper] - xt) / range;
+    const double b = 1.0 - a;
+    const double range2 = range * range / 6.0;
+    h.ip_k[(size_t)i] = (int32_t)klower;
+    h.ip_rec[(size_t)i * 4 + 0] = a;
+    h.ip_rec[(size_t)i * 4 + 1] = (a * a * a - a) * range2;
+    h.ip_rec[(size_t)i * 4 + 2] = (b * b * b - b) * range2;
+    h.ip_rec[(size_t)i * 4 + 3] = 1.0;
+  }
+  h.weighting = (o.auditory_weighting && scale == SMILEHIP_SPECSCALE_LOG && param == 2.0) ? 1 : 0;
+  if (h.weighting) {
+    const double nOctaves = std::log(maxF / minF) / std::log(2.0);
+    const double nPointsPerOctave = nPointsTarget / nOctaves;
+    const double atan_s = nPointsPerOctave * (std::log(65.0 / 50.0) / std::log(2.0)) - 1.0;
+    for (int i = 0; i < nPointsTarget; i++) {
+      const double w = 0.5 + std::atan(3.0 * (i + 1 - atan_s) / nPointsPerOctave) / M_PI;
+      if (!std::isfinite(w)) { *why = "the auditory weighting is not finite (a target range of zero octaves)"; return SMILEHIP_ERR_INVALID; }
+      h.ip_rec[(size_t)i * 4 + 3] = w;
+    }
+  }
+  return SMILEHIP_OK;
+}
+
 }  // namespace smilehip

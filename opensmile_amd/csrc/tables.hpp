@@ -55,6 +55,21 @@ struct F0Host {
 // K bins of a spectrum level whose frameSizeSec is fft_frame_size_sec; 0 on success
 int  make_f0_tables(int64_t K, double fft_frame_size_sec, int n_harmonics, float compression, double min_f, F0Host &h);
 
+// cSpecScale on any target scale (log / semitone / bark / bao / mel / linear), any number of target points and an explicit maxF:
+// the source axis, smileMath_cspline_init's and smileMath_csplint_init's caches and the data-independent half of
+// smileMath_cspline's recurrences, as lld_specscale.hip reads them
+struct SpecScaleHost {
+  int32_t n_src = 0, n_tgt = 0;
+  int32_t weighting = 0;          // the auditory weighting survives myFetchConfig (log scale with base exactly 2)
+  double min_f = 0.0, max_f = 0.0, fmin_t = 0.0, fmax_t = 0.0;
+  std::vector<double> f_t;        // [n_src] the source bins on the target axis
+  std::vector<double> spline;     // [n_src x 5] sigma, diff1, diff2, p = 1 / (sigma y2[i-1] + 2), y2[i] of the forward sweep (bins 1 .. n_src-2)
+  std::vector<int32_t> ip_k;      // [n_tgt] lower source bin of target point i (non-decreasing)
+  std::vector<double> ip_rec;     // [n_tgt x 4] a, c, d, auditory weight (1 where the weighting is off)
+};
+// n_src bins of a spectrum level whose frameSizeSec is frame_size_sec; 0 on success, otherwise `why` names the cause
+int  make_specscale_tables(const smilehip_specscale_opts &o, int64_t n_src, double frame_size_sec, SpecScaleHost &h, const char **why);
+
 int  make_geometry(const smilehip_lld_config &c, Geometry &g);
 int  make_window(const smilehip_lld_config &c, int64_t N, std::vector<float> &w);
 int  make_mel(const smilehip_lld_config &c, const Geometry &g, MelBank &m);

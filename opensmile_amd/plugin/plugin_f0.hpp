@@ -29,39 +29,100 @@ static smilehip_plan *f0_component_plan(long K, double frame_size_sec, double mi
   return pl;
 }
 
-// cSpecScale::processVector (src/dsp/specScale.cpp:305-357) for the option set the F0 chains use (octave target scale,
-// spline interpolation, minF 25, maxF -1, nPointsTarget 0, smoothing + enhancement + auditory weighting); anything else
-// stays on the reference's CPU code. Names, frequency-axis info and the level meta data cPitchShs reads are inherited.
+// cSpecScale::processVector (src/dsp/specScale.cpp:326-377). The option set the F0 chains use (octave target scale, minF > 0,
+// maxF -1, nPointsTarget 0, on the 257 / 513 / 1025 / 2049 bins of 512 .. 4096-point transforms) runs on an F0-chain plan's tables (smilehip_specscale_frames); every
+// other one -- log with another base, semitone, bark, bao, mel, linear, a chosen number of target points, an explicit maxF, any
+// spectrum length -- on the general operator (smilehip_specscale_op_*). sourceScale and interpMethod are read by the reference and
+// never used (:128-149; dataProcessorCustomFinalise and processVector do not look at them): ignored here as there. Names,
+// frequency-axis info and the level meta data cPitchShs reads are inherited.
 class cHipSpecScale : public BlockVP<cSpecScale> {
   FrameIO io_;
   bool cpu_warned_ = false;
   smilehip_plan *pl_ = nullptr;
-  int usable_ = -1;
+  smilehip_specscale_op *op_ = nullptr;
+  long mag_start_ = 0, n_mag_ = 0;
+  std::string why_;
+  int usable_ = -1;                                       // 1: the plan path, 2: the general operator, 0: refused (why_)
+  // the general operator for this instance's options, as myFetchConfig reads them (specScale.cpp:100-127, 158-186), on the level's
+  // '*Mag*' field, found as setupNewNames finds it (:196-212: nMag / magStart are private to the base class)
+  void setup_general(long Nsrc, long Ndst) {
+    smilehip_specscale_opts o;
+    memset(&o, 0, sizeof(o));
+    const char *sc = getStr("scale");
+    if (sc && !strncasecmp(sc, "log", 3)) { o.scale = SMILEHIP_SPECSCALE_LOG; o.param = getDouble("logScaleBase"); if (o.param <= 0.0 || o.param == 1.0) o.param = 2.0; }
+    else if (sc && !strncasecmp(sc, "oct", 3)) { o.scale = SMILEHIP_SPECSCALE_LOG; o.param = 2.0; }
+    else if (sc && !strncasecmp(sc, "sem", 3)) { o.scale = SMILEHIP_SPECSCALE_SEMITONE; o.param = getDouble("firstNote"); }
+    else if (sc && !strncasecmp(sc, "lin", 3)) o.scale = SMILEHIP_SPECSCALE_LINEAR;
+    else if (sc && !strncasecmp(sc, "bar", 3)) o.scale = SMILEHIP_SPECSCALE_BARK;
+    else if (sc && !strncasecmp(sc, "bao", 3)) o.scale = SMILEHIP_SPECSCALE_BARK_OLD;
+    else if (sc && !strncasecmp(sc, "mel", 3)) o.scale = SMILEHIP_SPECSCALE_MEL;
+    else { why_ = "cSpecScale: unknown target scale"; return; }
+    o.min_f = getDouble("minF");
+    o.max_f = getDouble("maxF");
+    o.n_points_target = (int32_t)getInt("nPointsTarget");
+    o.spec_enhance = getInt("specEnhance") ? 1 : 0;
+    o.spec_smooth = getInt("specSmooth") ? 1 : 0;
+    o.auditory_weighting = (getInt("auditoryWeighting") && o.scale == SMILEHIP_SPECSCALE_LOG && o.param == 2.0) ? 1 : 0;
+    const FrameMetaInfo *fmeta = reader_->getFrameMetaInfo();
+    int ri = 0;
+    const long idx = fmeta ? fmeta->findFieldByPartialName("Mag", &ri) : -1;
+    if (idx < 0) { why_ = "cSpecScale: the input level has no '*Mag*' field (the reference then reads field -1's axis info)"; return; }
+    mag_start_ = ri;
+    n_mag_ = fmeta->field[idx].N;
+    if (n_mag_ + mag_start_ > Nsrc) n_mag_ = Nsrc - mag_start_;
+    if (mag_start_ < 0) mag_start_ = 0;
+    if (smilehip_specscale_op_create(context(), &o, n_mag_, reader_->getLevelConfig()->frameSizeSec, &op_) != SMILEHIP_OK) {
+      why_ = smilehip_last_error();
+      op_ = nullptr;
+      return;
+    }
+    if (smilehip_specscale_op_n_out(op_) != Ndst) {
+      why_ = "cSpecScale: the output level's width is not nPointsTarget";
+      smilehip_specscale_op_destroy(op_);
+      op_ = nullptr;
+      usable_ = 0;
+      return;
+    }
+    usable_ = 2;
+  }
  protected:
   int processVector(const FLOAT_DMEM *src, FLOAT_DMEM *dst, long Nsrc, long Ndst, int idxi) override {
     if (usable_ < 0) {
       const char *sc = getStr("scale"), *ss = getStr("sourceScale"), *im = getStr("interpMethod");
       // the octave axis: scale = octave, or scale = log with logScaleBase 2 (specScale.cpp:100-111)
       const bool octave = sc && (!strncasecmp(sc, "oct", 3) || (!strncasecmp(sc, "log", 3) && getDouble("logScaleBase") == 2.0));
-      usable_ = octave && ss && !strncasecmp(ss, "lin", 3) && im && !strncasecmp(im, "spl", 3) &&
+      // ... on the spectra the F0-chain plans are instantiated for (512 .. 4096-point transforms: smilehip_plan_create fails for any
+      // other length, and a failed plan must not end the run here -- those levels are the general operator's)
+      const bool plan_size = Nsrc == 257 || Nsrc == 513 || Nsrc == 1025 || Nsrc == 2049;
+      usable_ = octave && plan_size && ss && !strncasecmp(ss, "lin", 3) && im && !strncasecmp(im, "spl", 3) &&
                 getDouble("minF") > 0.0 && getDouble("maxF") == -1.0 && getInt("nPointsTarget") <= 0 && Nsrc == Ndst;
       if (usable_) {
         const int off = (getInt("specEnhance") ? 0 : 1) | (getInt("specSmooth") ? 0 : 2) | (getInt("auditoryWeighting") ? 0 : 4);
         pl_ = f0_component_plan(Nsrc, (double)(float)reader_->getLevelConfig()->frameSizeSec, 52.0, 620.0, 0.7, 15, 0.85, getDouble("minF"), 6, 0, off);
         if (!pl_) usable_ = 0;
       }
+      if (!usable_) setup_general(Nsrc, Ndst);
     }
-    if (!usable_) { HIP_FALLTHROUGH(15, "cSpecScale: only the octave (log2) target scale from a linear source by spline interpolation, minF > 0, maxF -1, on spectra of 512 .. 4096 points is built"); return cSpecScale::processVector(src, dst, Nsrc, Ndst, idxi); }
-    io_.ensure(Nsrc, Ndst);
-    io_.up(src, Nsrc);
-    check(smilehip_specscale_frames(pl_, io_.d_in, Nsrc, io_.d_out, Ndst, g_blk.n, nullptr));
+    if (!usable_) { HIP_FALLTHROUGH(15, why_.c_str()); return cSpecScale::processVector(src, dst, Nsrc, Ndst, idxi); }
+    if (usable_ == 2) {
+      io_.ensure(n_mag_, Ndst);
+      io_.up(src + mag_start_, n_mag_);
+      check(smilehip_specscale_op_frames(op_, io_.d_in, n_mag_, io_.d_out, Ndst, g_blk.n, nullptr));
+    } else {
+      io_.ensure(Nsrc, Ndst);
+      io_.up(src, Nsrc);
+      check(smilehip_specscale_frames(pl_, io_.d_in, Nsrc, io_.d_out, Ndst, g_blk.n, nullptr));
+    }
     io_.down(dst, Ndst);
     g_frames[15] += g_blk.n;
     return (int)Ndst;
   }
  public:
   explicit cHipSpecScale(const char *n) : BlockVP<cSpecScale>(n) {}
-  ~cHipSpecScale() override { if (pl_) smilehip_plan_destroy(pl_); }
+  ~cHipSpecScale() override {
+    if (pl_) smilehip_plan_destroy(pl_);
+    if (op_) smilehip_specscale_op_destroy(op_);
+  }
   static cSmileComponent *create(const char *n) {
     cSmileComponent *c = new cHipSpecScale(n);
     c->setComponentInfo(scname, sdescription);
