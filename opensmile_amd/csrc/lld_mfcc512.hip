@@ -21,6 +21,12 @@
 //           layers, constants only), twiddle by w256^(j*k1) (LDS table), ONE
 //           16x16 transpose of (re,im) pairs through LDS (b64 stores and loads,
 //           conflict-free interleaved layout), radix-16 DFT over j
+//           Order of the transposition traffic (round 8): the first DFT's last layer finishes its outputs in groups of four --
+//           k1 = 0, 4, 8, 12, then 1, 5, 9, 13, .. -- and each is twiddled and stored at once, so the sixteen stores are spread
+//           over that layer and the twiddles instead of standing in one block in front of the sixteen loads (which are issued
+//           in index order jj = 0 .. 15; the order of the second DFT's first layer was measured and is no gain). LDS operations
+//           of a wave return in order: what a wave waits for is decided by the ORDER of its requests. No instruction is added,
+//           and an instruction's lane -> bank pattern does not depend on its position (tools/lds_bank_sim.py)
 //   spect.  lanes j and 16-j own mirror-image bins: the partner's half of Z
 //           arrives by two DPP steps (row shift + row mirror), BOTH X[k] and
 //           X[256-k] are untangled from one (Z[k], Z[256-k]) pair (R4), power
@@ -128,12 +134,15 @@ struct Dft16K {
 // forward DFT16, natural order in and out (registers, static indexing only).
 // x[m], m = m0 + 4 m1:  y[m0][q] = DFT4 over m1; y *= w16^(m0 q);
 // X[q + 4p] = DFT4 over m0.
-__device__ __forceinline__ void dft16(float (&re)[16], float (&im)[16], const Dft16K &K) {
-#pragma unroll
-  for (int m0 = 0; m0 < 4; ++m0)
-    dft4(re[m0], im[m0], re[m0 + 4], im[m0 + 4], re[m0 + 8], im[m0 + 8], re[m0 + 12], im[m0 + 12]);
-  // y[m0][q] now sits at index m0 + 4q. Twiddles w16^(m0*q), w16 = e^{-2 pi i/16}:
-  // (1,1)->e1 (1,2)->e2 (1,3)->e3 (2,1)->e2 (2,2)->e4 (2,3)->e6 (3,1)->e3 (3,2)->e6 (3,3)->e9
+// In three parts, so that the caller can put LDS traffic between them (round 8): dft16_first + dft16_last(q = 0 .. 3) + dft16_rename
+// is dft16 -- one implementation of the arithmetic.
+// first layer, group m0: needs the inputs m0, m0 + 4, m0 + 8, m0 + 12 only
+__device__ __forceinline__ void dft16_first(float (&re)[16], float (&im)[16], int m0) {
+  dft4(re[m0], im[m0], re[m0 + 4], im[m0 + 4], re[m0 + 8], im[m0 + 8], re[m0 + 12], im[m0 + 12]);
+}
+// y[m0][q] sits at index m0 + 4q. Twiddles w16^(m0*q), w16 = e^{-2 pi i/16}:
+// (1,1)->e1 (1,2)->e2 (1,3)->e3 (2,1)->e2 (2,2)->e4 (2,3)->e6 (3,1)->e3 (3,2)->e6 (3,3)->e9
+__device__ __forceinline__ void dft16_twiddles(float (&re)[16], float (&im)[16], const Dft16K &K) {
   cmul_ns(re[1 + 4], im[1 + 4], K.c1, K.ns1, K.s1);                       // e1
   { const float a = re[1 + 8], b = im[1 + 8]; re[1 + 8] = K.r2 * (a + b); im[1 + 8] = K.r2 * (b - a); }    // e2
   cmul_ns(re[1 + 12], im[1 + 12], K.s1, K.nc1, K.c1);                     // e3
@@ -143,11 +152,13 @@ __device__ __forceinline__ void dft16(float (&re)[16], float (&im)[16], const Df
   cmul_ns(re[3 + 4], im[3 + 4], K.s1, K.nc1, K.c1);                       // e3
   { const float a = re[3 + 8], b = im[3 + 8]; re[3 + 8] = K.r2 * (b - a); im[3 + 8] = K.nr2 * (a + b); }   // e6
   cmul_ns(re[3 + 12], im[3 + 12], K.nc1, K.s1, K.ns1);                    // e9
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-    dft4(re[4 * q], im[4 * q], re[4 * q + 1], im[4 * q + 1], re[4 * q + 2], im[4 * q + 2], re[4 * q + 3],
-         im[4 * q + 3]);
-  // X[q + 4p] sits at index 4q + p: undo the digit reversal (register renaming)
+}
+// last layer, group q: leaves the final X[q + 4p] at index 4q + p
+__device__ __forceinline__ void dft16_last(float (&re)[16], float (&im)[16], int q) {
+  dft4(re[4 * q], im[4 * q], re[4 * q + 1], im[4 * q + 1], re[4 * q + 2], im[4 * q + 2], re[4 * q + 3], im[4 * q + 3]);
+}
+// X[q + 4p] sits at index 4q + p: undo the digit reversal (register renaming)
+__device__ __forceinline__ void dft16_rename(float (&re)[16], float (&im)[16]) {
   float tr[16], ti[16];
 #pragma unroll
   for (int q = 0; q < 4; ++q)
@@ -155,6 +166,14 @@ __device__ __forceinline__ void dft16(float (&re)[16], float (&im)[16], const Df
     for (int p = 0; p < 4; ++p) { tr[q + 4 * p] = re[4 * q + p]; ti[q + 4 * p] = im[4 * q + p]; }
 #pragma unroll
   for (int k = 0; k < 16; ++k) { re[k] = tr[k]; im[k] = ti[k]; }
+}
+__device__ __forceinline__ void dft16(float (&re)[16], float (&im)[16], const Dft16K &K) {
+#pragma unroll
+  for (int m0 = 0; m0 < 4; ++m0) dft16_first(re, im, m0);
+  dft16_twiddles(re, im, K);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) dft16_last(re, im, q);
+  dft16_rename(re, im);
 }
 
 // DPP move with a compile-time control word (row_shl:n = 0x100 + n, row_ror:n = 0x120 + n, row_mirror = 0x140)
@@ -200,6 +219,43 @@ constexpr bool kPredLoads = false;
 constexpr bool kB16Samples = true;
 #else
 constexpr bool kB16Samples = false;
+#endif
+// (round 8) LDS latency out of the wave's critical path without one more LDS, vector-memory or vector-ALU instruction: three changes
+// of ORDER, each behind a switch (A/B aids, make MFCC512_EXTRA=-D...). The bits are the parent's in every combination
+// (tests/test_gpu_mfcc512_bits_r8.py). Figures: DESIGN.md 4.1, profiles/r08_ab.txt, profiles/r08_mfcc512_phases.txt.
+// KEPT: the transposition writes index by index behind the first DFT's last layer (-DSMILEHIP_MFCC512_WRITES_IN_ONE_BLOCK restores the
+// parent's form): 0.3808 -> 0.3756 ms per bench step on one box (faster in each of three interleaved rounds), 0.3663 -> 0.3581 on a
+// second one (four rounds; the kernel under the profiler 0.3632 -> 0.3555 ms).
+#ifdef SMILEHIP_MFCC512_WRITES_IN_ONE_BLOCK
+constexpr bool kWritesEarly = false;          // DFT, fifteen twiddle products, sixteen transposition writes
+#else
+constexpr bool kWritesEarly = true;           // last DFT layer, twiddle product and write index by index
+#endif
+// (round 8, measured and NOT taken) -DSMILEHIP_MFCC512_READS_IN_DFT_ORDER: the transposition reads in the order in which the second
+// DFT's first layer takes them (0, 4, 8, 12 | 1, 5, 9, 13 | ..): its four dft4 then wait for lgkmcnt(13, 12) / (9, 8) / (5, 4) / (1, 0)
+// where the index order makes the first one wait for (7), (3) -- thirteen of the sixteen reads. Alone on top of the parent it was not
+// faster in each of three rounds (0.3816 against 0.3808 ms, -0.7 % / -0.1 % / +1.4 %); on top of the early writes it changes nothing
+// (0.3582 against 0.3581 ms, four rounds; kernel 0.3557 against 0.3555 ms): with four waves per SIMD the other waves' instructions
+// fill the ~9 further reads' worth of waiting.
+#ifdef SMILEHIP_MFCC512_READS_IN_DFT_ORDER
+constexpr bool kReadsInDftOrder = true;
+#else
+constexpr bool kReadsInDftOrder = false;      // the transposition reads jj = 0 .. 15
+#endif
+// (round 8, measured and NOT taken) -DSMILEHIP_MFCC512_MIRROR_OPERAND: the untangle's row_mirror step as the DPP operand of the four
+// additions it feeds (written next to them, the compiler's DPP combiner folds it: it looks no further than 20 instructions ahead of a
+// move) instead of 16 moves of their own: 815 -> 797 VALU instructions per pass, but the 32 additions become 64-bit encoded (155 ->
+// 171 such instructions) and the launch is SLOWER: 0.3849 against 0.3808 ms per bench step (+1.1 %, slower in each of three
+// interleaved rounds on one box, alone on top of the parent).
+#ifdef SMILEHIP_MFCC512_MIRROR_OPERAND
+constexpr bool kMirrorOperand = true;
+#else
+constexpr bool kMirrorOperand = false;
+#endif
+#ifdef SMILEHIP_MFCC512_BPERMUTE_PARTNER
+constexpr bool kMirrorAtUse = false;          // (the crossbar form has no mirror step)
+#else
+constexpr bool kMirrorAtUse = kMirrorOperand;
 #endif
 template <int MP, bool ALIGNED, bool PREEMPH>
 struct FrameRegs {
@@ -547,27 +603,60 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
     }
 
     // ------------------------------------------------------------ 256-point complex FFT
-    dft16(re, im, dk);                                       // over m  -> index k1
-#pragma unroll
-    for (int k1 = 1; k1 < 16; ++k1) {
-      const float2 w = s_tw256[k1 * 16 + j];
-      cmul(re[k1], im[k1], w.x, w.y);
-    }
-    PHASE(3);                                   // dft16 + twiddles
     // 16x16 transpose of (re, im) pairs: 16 ds_write_b64 + 16 ds_read_b64 through a buffer that
     // overlays the whole per-wave region (band vector and power buffers are dead here).
     // Element (row r, column c) of group g sits at byte g*128 + r*520 + c*8: the four groups'
     // rows are interleaved and each 4-group row is padded by 8 bytes, which makes both the
     // row-wise b64 stores (16-lane groups) and the column-wise b64 loads (32-lane groups)
     // bank-conflict free with immediate offsets only (tools/lds_bank_sim.py).
-    {
-      float2 *tbw = reinterpret_cast<float2 *>(wbase) + g * 16 + j;
-      const float2 *tbr = reinterpret_cast<const float2 *>(wbase) + g * 16 + j * kTB2Row;
+    float2 *tbw = reinterpret_cast<float2 *>(wbase) + g * 16 + j;
+    const float2 *tbr = reinterpret_cast<const float2 *>(wbase) + g * 16 + j * kTB2Row;
+    if constexpr (kWritesEarly) {
+      // (round 8) The last layer of the DFT hands out final values group by group -- q = 0 gives k1 = 0, 4, 8, 12 -- so the twiddle
+      // product and the ds_write_b64 of an index follow its dft4 at once: the sixteen writes are spread over the last layer and the
+      // twiddles instead of standing in one block in front of the reads. The twiddle pairs of group q + 1 are requested before group
+      // q's last layer (those of group 0 before the whole DFT): no table read stands behind a transposition write that the compiler
+      // cannot tell apart from it, and each has ~30 vector instructions to arrive in.
+      float2 w[4], wn[4];
+#pragma unroll
+      for (int p = 1; p < 4; ++p) w[p] = s_tw256[(4 * p) * 16 + j];
+      w[0] = make_float2(1.0f, 0.0f);              // k1 = 0: no product
+#pragma unroll
+      for (int m0 = 0; m0 < 4; ++m0) dft16_first(re, im, m0);
+      dft16_twiddles(re, im, dk);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (q < 3) {
+#pragma unroll
+          for (int p = 0; p < 4; ++p) wn[p] = s_tw256[(q + 1 + 4 * p) * 16 + j];
+        }
+        dft16_last(re, im, q);
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+          const int k1 = q + 4 * p;
+          if (k1 > 0) cmul(re[4 * q + p], im[4 * q + p], w[p].x, w[p].y);
+          tbw[k1 * kTB2Row] = make_float2(re[4 * q + p], im[4 * q + p]);
+        }
+#pragma unroll
+        for (int p = 0; p < 4; ++p) w[p] = wn[p];
+      }
+    } else {
+      dft16(re, im, dk);                                       // over m  -> index k1
+#pragma unroll
+      for (int k1 = 1; k1 < 16; ++k1) {
+        const float2 w = s_tw256[k1 * 16 + j];
+        cmul(re[k1], im[k1], w.x, w.y);
+      }
 #pragma unroll
       for (int k1 = 0; k1 < 16; ++k1) tbw[k1 * kTB2Row] = make_float2(re[k1], im[k1]);
+    }
+    PHASE(3);                                   // dft16 + twiddles (+ transposition writes)
+    {
       wave_lds_fence();
+      // (SMILEHIP_MFCC512_READS_IN_DFT_ORDER: in the order in which the second DFT's first layer takes them, see the switch)
 #pragma unroll
-      for (int jj = 0; jj < 16; ++jj) {          // one ds_read_b64 each (2 LDS cycles); paired into ds_read2_b64 they would take 8 per pair
+      for (int i = 0; i < 16; ++i) {             // one ds_read_b64 each (2 LDS cycles); paired into ds_read2_b64 they would take 8 per pair
+        const int jj = kReadsInDftOrder ? (i >> 2) + 4 * (i & 3) : i;
         typedef const volatile __attribute__((address_space(3))) unsigned long long *LdsU64;
         const unsigned long long v = ((LdsU64)tbr)[jj];
         re[jj] = __int_as_float((int)(uint32_t)v); im[jj] = __int_as_float((int)(uint32_t)(v >> 32));
@@ -608,8 +697,10 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
       const float pi = q > 0 ? dpp_f<0x12f>(im[(16 - q) & 15]) : im[15];
       const float tr = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(pr), __float_as_int(re[15 - q]), 0x101, 0xf, 0xf, false));
       const float ti = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(pi), __float_as_int(im[15 - q]), 0x101, 0xf, 0xf, false));
-      zr[q] = dpp_f<0x140>(tr);
-      zi[q] = dpp_f<0x140>(ti);
+      // (SMILEHIP_MFCC512_MIRROR_OPERAND: the row_mirror step is taken next to its four additions below and zr / zi hold the
+      // shifted values until then)
+      zr[q] = kMirrorOperand ? tr : dpp_f<0x140>(tr);
+      zi[q] = kMirrorOperand ? ti : dpp_f<0x140>(ti);
     }
 #endif
     float2 tw5[8];                                // e^{-2 pi i k/512} of my eight bins, all read before the first store to the
@@ -618,7 +709,8 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const float2 w = tw5[q];
-      const float a = re[q], b = im[q], c = zr[q], d = zi[q];
+      const float a = re[q], b = im[q];
+      const float c = kMirrorAtUse ? dpp_f<0x140>(zr[q]) : zr[q], d = kMirrorAtUse ? dpp_f<0x140>(zi[q]) : zi[q];
       const float sr = a + c, si = b - d, dr = a - c, di = b + d;
       const float ur = fmaf(w.x, dr, -w.y * di);
       const float ui = fmaf(w.x, di, w.y * dr);

@@ -1,13 +1,27 @@
 #!/usr/bin/env python3
-"""LDS bank-conflict model of the fast MFCC kernel's wave-level access patterns
-(rules from /opt/skills/guides/MI355X_MICROARCH.md, LDS section). Prints the extra
-(conflict) cycles per DS instruction class for one pass of one wave."""
+"""LDS bank-conflict model of the fast MFCC kernel's wave-level access patterns (opensmile_amd/csrc/lld_mfcc512.hip, the layout
+of its `LDS layout` comment; bank rules of the gfx950 LDS: 64 banks of 4 bytes, a b64 load served per half wave, a b64 store and
+a b128 access per group of 16 lanes). Prints the extra (conflict) cycles per DS instruction class for one pass of one wave.
+
+The transposition is modelled per instruction and in issue order (`transposition`): an instruction's lane -> bank pattern depends
+on its own row / column index only, so the ORDER in which the sixteen stores and the sixteen loads are issued cannot change the
+conflict count -- the function checks that and returns the count for any order (since round 8 the stores are issued in the order of
+the first DFT's last layer, TRANSPOSE_ORDER_R8, and the loads can be, -DSMILEHIP_MFCC512_READS_IN_DFT_ORDER; the parent commit issued
+both in index order)."""
 import numpy as np
 
-H, MP, U = 160, 13, 6
-shared = 512 + MP * 32 + 512 + U * 144 + 448 + 64
-stage_alloc = 896
-wave_floats = stage_alloc + 4 + 4 * 272
+MP, UC = 13, 6                       # the bench's instance
+K_TB2_ROW = 65                       # float2 per 4-group row of the transpose buffer
+K_LMEL, K_OCTET, K_PB, K_WAVE = 64, 12, 448, 2080
+SHARED = 256 * 2 + MP * 16 * 2 + 256 * 2 + UC * 16 * 8 + 16 * 28 + 48      # floats in front of the per-wave regions
+OFF_TW512, OFF_WIN = 0, 512
+OFF_TW256 = OFF_WIN + MP * 32
+OFF_MELW0 = OFF_TW256 + 512
+OFF_MELW1 = OFF_MELW0 + UC * 64
+OFF_DCT = OFF_MELW1 + UC * 64
+
+TRANSPOSE_ORDER_PARENT = list(range(16))
+TRANSPOSE_ORDER_R8 = [q + 4 * p for q in range(4) for p in range(4)]       # 0, 4, 8, 12 | 1, 5, 9, 13 | ...
 
 
 def groups(kind):
@@ -44,67 +58,74 @@ def cost(kind, addr_bytes, active=None):
 
 lane = np.arange(64)
 g, j = lane >> 4, lane & 15
-wbase = shared  # wave 0
-stage = wbase
-gb = wbase + stage_alloc + 4 + g * 272
-pb = gb + ((g & 1) << 2)
-ps = stage + g * 128
-tot = {}
 
 
-def add(name, c):
-    tot[name] = tot.get(name, 0) + c
+def wave_base(wave=0):
+    return SHARED + wave * K_WAVE
 
 
-for r in range(7):
-    add("stage write b64", cost("w64", 4 * (stage + 2 * (lane + 64 * r))))
-for m in range(MP):
-    add("frame read b64", cost("r64", 4 * (stage + g * H + 2 * j + 32 * m)))
-    add("window read b64", cost("r64", 4 * (512 + 2 * (m * 16 + j))))
-for k1 in range(1, 16):
-    add("tw256 read b64", cost("r64", 4 * (512 + MP * 32 + 2 * (k1 * 16 + j))))
-for k1 in range(16):
-    add("TB write b32", 2 * cost("w32", 4 * (gb + k1 * 17 + j)))   # re and im
-for jj in range(16):
-    add("TB read b32", 2 * cost("r32", 4 * (gb + j * 17 + jj)))
-for k2 in range(8):
-    add("ZX write b64", cost("w64", 4 * (gb + 2 * (k2 * 16 + j))))
-pj, zrow = (16 - j) & 15, np.where(j == 0, 16, 0)
-for q in range(8):
-    add("ZX read b64", cost("r64", 4 * (gb + 2 * ((7 - q) * 16 + pj + zrow))))
-    add("tw512 read b64", cost("r64", 4 * (2 * (j + 16 * q))))
-    add("PB write b32", cost("w32", 4 * (pb + j + 16 * q)) + cost("w32", 4 * (pb + 256 - j - 16 * q)))
-# mel units: octets per unit from the real bank would need the table; model consecutive octets
-rng = np.random.default_rng(0)
-import ctypes, os, sys
-sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
-try:
-    from opensmile_amd import capi
-    p = capi.Plan(None)
-    chan = p.mel_chanmap()
-    # rebuild units as fast512_build_host does
-    nb = 26
-    units = []
-    for b in range(nb):
-        rise = np.where(chan == b - 1)[0]
-        fall = np.where(chan == b)[0]
-        bins = np.concatenate([rise, fall]) if b > 0 else fall
-        lo, hi = bins.min(), bins.max() + 1
-        for o in range(lo // 8, (hi - 1) // 8 + 1):
-            units.append(o)
-    print("mel units:", len(units))
-    for i in range((len(units) + 15) // 16):
-        octs = np.array([units[i * 16 + jj] if i * 16 + jj < len(units) else 0 for jj in range(16)])
-        a = 4 * (pb) + 32 * octs[j]
-        add("mel p read b128", cost("r128", a) + cost("r128", a + 16))
-        add("mel w read b128", 2 * cost("r128", 4 * (512 + MP * 32 + 512 + 4 * (i * 16 + j))))
-        add("PS write b32", cost("w32", 4 * (ps + (i * 16 + j))))
-except Exception as e:  # pragma: no cover
-    print("mel model skipped:", e)
-for q in range(7):
+def transposition(store_order=TRANSPOSE_ORDER_R8, load_order=TRANSPOSE_ORDER_R8, wave=0):
+    """The 16 ds_write_b64 (row k1 of group g: float2 index g*16 + j + k1*65) and the 16 ds_read_b64 (column jj: g*16 + j*65 + jj)
+    in the given issue orders -> (extra cycles of the stores, of the loads, order_independent). `order_independent`: every
+    instruction has the conflict count it has in index order (its addresses do not depend on its position)."""
+    assert sorted(store_order) == list(range(16)) and sorted(load_order) == list(range(16))
+    wb = wave_base(wave)
+    st = {k1: cost("w64", 4 * wb + 8 * (g * 16 + j + k1 * K_TB2_ROW)) for k1 in range(16)}
+    ld = {jj: cost("r64", 4 * wb + 8 * (g * 16 + j * K_TB2_ROW + jj)) for jj in range(16)}
+    st_seq = [cost("w64", 4 * wb + 8 * (g * 16 + j + k1 * K_TB2_ROW)) for k1 in store_order]
+    ld_seq = [cost("r64", 4 * wb + 8 * (g * 16 + j * K_TB2_ROW + jj)) for jj in load_order]
+    same = st_seq == [st[k] for k in store_order] and ld_seq == [ld[k] for k in load_order]
+    return sum(st_seq), sum(ld_seq), same
+
+
+def pb_pos(k):
+    return k + (K_OCTET - 8) * (k >> 3)
+
+
+def model(wave=0):
+    tot = {}
+
+    def add(name, c):
+        tot[name] = tot.get(name, 0) + c
+
+    wb = wave_base(wave)
+    lmel = wb + g * K_LMEL
+    pb = wb + 4 * K_LMEL + g * K_PB
+    for m in range(MP):
+        add("window read b64", cost("r64", 4 * (OFF_WIN + 2 * (m * 16 + j))))
+    for k1 in range(1, 16):
+        add("tw256 read b64", cost("r64", 4 * (OFF_TW256 + 2 * (k1 * 16 + j))))
+    s, l, _ = transposition(wave=wave)
+    add("transpose write b64", s)
+    add("transpose read b64", l)
+    for q in range(8):
+        add("tw512 read b64", cost("r64", 4 * (OFF_TW512 + 2 * (j + 16 * q))))
+        add("power write b32", cost("w32", 4 * (pb + pb_pos(j) + 2 * K_OCTET * q)) + cost("w32", 4 * (pb + pb_pos(256 - j) - 2 * K_OCTET * q)))
+    for i in range(UC):
+        # the octets of a step are the host's choice (fast512_build_host orders every lane's units so that the 16 lanes of a frame
+        # touch 16 different bank quads and prints its own count with SMILEHIP_DEBUG_TABLES=1); the weights are table rows
+        add("mel weight read b128", cost("r128", 4 * (OFF_MELW0 + 4 * (i * 16 + j))) + cost("r128", 4 * (OFF_MELW1 + 4 * (i * 16 + j))))
     act = j < 13
-    add("lmel read b128", cost("r128", 4 * (ps + 96 + 4 * q + 0 * j), act))
-    add("dct read b128", cost("r128", 4 * (shared - 64 - 448 + j * 28 + 4 * q), act))
-for name, c in tot.items():
-    print(f"{name:20s} extra cycles {c}")
-print("total extra", sum(tot.values()))
+    for q in range(7):
+        add("log-mel read b128", cost("r128", 4 * (lmel + 4 * q), act))
+        add("dct read b128", cost("r128", 4 * (OFF_DCT + j * 28 + 4 * q), act))
+    return tot
+
+
+def main():
+    tot = model()
+    for name, c in tot.items():
+        print(f"{name:22s} extra cycles {c}")
+    print("total extra", sum(tot.values()))
+    for name, order in (("index order (parent)", TRANSPOSE_ORDER_PARENT), ("DFT-layer order (round 8)", TRANSPOSE_ORDER_R8)):
+        worst_s = worst_l = 0
+        for wave in range(8):
+            s, l, same = transposition(order, order, wave)
+            assert same
+            worst_s, worst_l = max(worst_s, s), max(worst_l, l)
+        print(f"transposition, {name}: stores {worst_s}, loads {worst_l} extra cycles (worst of the 8 waves of a block); "
+              "the per-instruction lane -> bank pattern does not depend on the issue order")
+
+
+if __name__ == "__main__":
+    main()

@@ -35,7 +35,7 @@ SRC = os.path.join(ROOT, "opensmile_amd", "csrc", "lld_mfcc512.hip")
 KERNEL = "_ZN8smilehip11lld_mfcc512ILi13ELb1ELb1ELb1ELb0ELi6ELb1EEEvNS_9LldParamsENS_13Fast512TablesE"
 FLAGS = ("--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-slp-vectorize -Xclang -target-feature "
          "-Xclang -load-store-opt --cuda-device-only -gline-tables-only -S").split()
-DFT_LINES = set(range(93, 104)) | set(range(111, 142))   # dft4 / dft16 of lld_mfcc512.hip (innermost inlined location); cmul (105-109) is left
+DFT_LINES = set(range(99, 110)) | set(range(118, 123)) | set(range(140, 160))   # dft4, cmul_ns, dft16_first / _twiddles / _last of lld_mfcc512.hip (innermost inlined location); cmul (111-115) is left
 # in: the line tables cannot tell the 4 cmul inside a dft16 from the 15 twiddle products between the stages, which stay on the vector ALU
 
 
