@@ -533,6 +533,8 @@ int  smilehip_plan_create(smilehip_context *ctx, const smilehip_lld_config *cfg,
  * validation on a host without a GPU). Every compute entry point refuses such
  * a plan with SMILEHIP_ERR_NO_DEVICE. */
 int  smilehip_plan_create_host_only(const smilehip_lld_config *cfg, smilehip_plan **plan);
+/* The FFT is built for 64 .. 8192 points: a plan of a shorter frame windows, frames and pre-emphasises; every entry point that would
+ * transform on it (rfft / fftmag / acf / irfft frames, batch creation) returns SMILEHIP_ERR_INVALID and names the length. */
 void smilehip_plan_destroy(smilehip_plan *plan);
 int  smilehip_plan_geometry(const smilehip_plan *plan, smilehip_geometry *g);
 /* cWinToVecProcessor framing rule: T = floor((S-N)/H)+1, 0 if S<N

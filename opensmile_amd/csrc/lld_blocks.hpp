@@ -158,58 +158,6 @@ __device__ __forceinline__ double block_max(double v, double *scr) { return Bloc
 __device__ __forceinline__ int block_sum_i(int v, int *scr) { return BlockG::sum_i(v, scr); }
 __device__ __forceinline__ int block_min_i(int v, int *scr) { return BlockG::min_i(v, scr); }
 
-// R4 core: in-place radix-2 DIT complex FFT of length M in LDS (re/im loaded in bit-reversed order)
-template <class G>
-__device__ __forceinline__ void group_cfft_radix2(float *re, float *im, int M, const float2 *tw_half) {
-  for (int len = 2; len <= M; len <<= 1) {
-    const int half = len >> 1;
-    const int tstep = M / len;
-    for (int b = G::tid(); b < (M >> 1); b += G::size()) {
-      const int j = b & (half - 1);
-      const int i0 = ((b - j) << 1) + j;
-      const int i1 = i0 + half;
-      const float2 w = tw_half[j * tstep];
-      const float xr = re[i1], xi = im[i1];
-      const float tr = fmaf(xr, w.x, -xi * w.y);
-      const float ti = fmaf(xr, w.y, xi * w.x);
-      const float ar = re[i0], ai = im[i0];
-      re[i1] = ar - tr; im[i1] = ai - ti;
-      re[i0] = ar + tr; im[i0] = ai + ti;
-    }
-    G::sync();
-  }
-}
-
-// Inverse of the packed real FFT for a purely real spectrum R[0..M] (what cAcf feeds
-// Ooura's rdft(n,-1), fftsg.c:103-135):  a[k] = R0/2 + R_M (-1)^k / 2 + sum_j R_j cos(2 pi jk/n).
-// Computed as half the forward DFT of the even extension s[j] = s[n-j] = R_j, through the
-// same half-length complex FFT + untangle the forward transform uses.
-template <class G>
-__device__ __forceinline__ void group_irfft_even(const float *R, float *re, float *im, int M, int logM, const float2 *tw_half,
-                                                 const float2 *tw_full, float *out, float inv_norm, bool take_abs) {
-  const int n = 2 * M;
-  for (int i = G::tid(); i < M; i += G::size()) {
-    const int n0 = 2 * i, n1 = 2 * i + 1;
-    const float v0 = R[n0 <= M ? n0 : n - n0];
-    const float v1 = R[n1 <= M ? n1 : n - n1];
-    const int r = (int)(__brev((unsigned)i) >> (32 - logM));
-    re[r] = v0;
-    im[r] = v1;
-  }
-  G::sync();
-  group_cfft_radix2<G>(re, im, M, tw_half);
-  for (int k = G::tid(); k < M; k += G::size()) {
-    const float a = 0.5f * untangle_bin(re, im, M, k, tw_full).x;
-    const float v = a / inv_norm;                       // acf.cpp:321-325: (FLOAT_DMEM)data / (FLOAT_DMEM)Nsrc
-    out[k] = take_abs ? fabsf(v) : v;
-  }
-  G::sync();
-}
-__device__ __forceinline__ void irfft_even(const float *R, float *re, float *im, int M, int logM, const float2 *tw_half,
-                                           const float2 *tw_full, float *out, float inv_norm, bool take_abs) {
-  group_irfft_even<BlockG>(R, re, im, M, logM, tw_half, tw_full, out, inv_norm, take_abs);
-}
-
 // R10 cPitchACF::processVector, per-frame part (pitchACF.cpp:137-192): voicing probability from
 // the ACF (voicingProb, :249-284) and the index of the first cepstral peak above
 // 0.6 * (max + mean|.|) (pitchPeak, :286-310). acf / cep: n values each, in LDS or global.

@@ -19,7 +19,6 @@
 
 #include "batch_layout.hpp"
 #include "lld_blocks.hpp"
-#include "lld_fft.hpp"
 #include "lld_blocks_compare.hpp"
 #include "lld_compare_quad.hpp"
 #include "lld_device.hpp"
@@ -54,16 +53,15 @@ extern "C" int smilehip_debug_phase_cmp(unsigned long long *out16, int reset) {
 #define PHASE_FLUSH
 #endif
 
-// LDS: yv[N] | re[M] | im[M] | mg[K] | pw[K] | prev[K] | mel[32] | aud[32] | lmel[32] | double red[64] | double cum[256] | peaks
+// LDS: yv[N] | z[M] pairs | mg[K] | pw[K] | prev[K] | mel[32] | aud[32] | lmel[32] | double red[64] | double cum[256] | peaks
 // Nfft = 512 only: thread i of the 256 owns bin i+1 in the descriptor section.
 __global__ void __launch_bounds__(256) lld_compare_frame(LldParams P, CompareParams Q) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int M = P.Nfft >> 1, K = P.K;
   const int Npad = (P.N + 3) & ~3, Kpad = (K + 3) & ~3;
   float *yv = smem;
-  float *re = yv + Npad;
-  float *im = re + M;
-  float *mg = im + M;
+  float2 *z = reinterpret_cast<float2 *>(yv + Npad);     // the transform's (re, im) pairs
+  float *mg = reinterpret_cast<float *>(z + M);
   float *pw = mg + Kpad;
   float *prev = pw + Kpad;
   float *melv = prev + Kpad;
@@ -81,8 +79,6 @@ __global__ void __launch_bounds__(256) lld_compare_frame(LldParams P, ComparePar
   for (int i = threadIdx.x; i < K; i += blockDim.x) s_coef[i] = P.mel_coef[i];
   for (int i = threadIdx.x; i < 4 * P.n_bands; i += blockDim.x) s_rng[i] = P.mel_rng[i];
   for (int i = threadIdx.x; i < P.n_mfcc * P.n_bands; i += blockDim.x) s_dct[i] = P.dct_rows[i];
-  int logM = 0;
-  while ((1 << logM) < M) ++logM;
 
   const int u = Q.run_utt[blockIdx.x];
   const int t0 = Q.run_t0[blockIdx.x];
@@ -119,22 +115,14 @@ __global__ void __launch_bounds__(256) lld_compare_frame(LldParams P, ComparePar
       const int n0 = 2 * i - P.pad_left, n1 = n0 + 1;
       const float v0 = (n0 >= 0 && n0 < P.N) ? yv[n0] * P.window[n0] + P.win_offset : 0.0f;
       const float v1 = (n1 >= 0 && n1 < P.N) ? yv[n1] * P.window[n1] + P.win_offset : 0.0f;
-      if (P.oo.tw) {
-        reinterpret_cast<float2 *>(re)[i] = make_float2(v0, v1);
-      } else {
-        const int r = (int)(__brev((unsigned)i) >> (32 - logM));
-        re[r] = v0;
-        im[r] = v1;
-      }
+      z[i] = make_float2(v0, v1);
     }
     __syncthreads();
     PHASE(0);   // load + window
-    if (P.oo.tw) ooura_levels<BlockG, false>(reinterpret_cast<float2 *>(re), P.oo);   // the reference's rdft network
-    else block_cfft_radix2(re, im, M, P.tw_half);
+    ooura_levels<BlockG, false>(z, P.oo);               // the reference's rdft network
     PHASE(1);   // FFT
     for (int k = threadIdx.x; k <= M; k += blockDim.x) {
-      const float2 X = P.oo.tw ? ooura_bin(reinterpret_cast<const float2 *>(re), P.oo, k) : untangle_bin(re, im, M, k, P.tw_full);
-      const float m = bin_magnitude(X, k == 0 || k == M);
+      const float m = bin_magnitude(ooura_bin(z, P.oo, k), k == 0 || k == M);
       mg[k] = m;
       pw[k] = m * m;                                    // squareInput (spectral.cpp:676-683) == melspec usePower
     }
@@ -192,13 +180,11 @@ __global__ void __launch_bounds__(256) lld_compare_frame(LldParams P, ComparePar
 // The same frame pipeline with ONE wave per frame and four independent runs per workgroup: no workgroup barriers after
 // the table staging, the thinly parallel sections (26 mel bands, 14 cepstra, scalar tails) of four frames overlap. Every sum
 // keeps the block kernel's order (lld_blocks_compare.hpp), so the two kernels give bit-identical rows.
-// LDS: shared coef[Kpad] | rng[128] | dct[16 x 32]; per wave z[fft_pairs(M)] pairs | mg[Kpad] | pw[Kpad] | prev[Kpad] |
+// LDS: shared coef[Kpad] | rng[128] | dct[16 x 32]; per wave z[2 Kpad] | mg[Kpad] | pw[Kpad] | prev[Kpad] |
 // mel[32] | aud[32] | lmel[32]
-// the wave's z region: the transform's pairs, then the mel terms (two rows of Kpad floats), then the descriptors' chains
-__host__ __device__ inline int compare_z_floats(int M, int Kpad) { return 2 * fft_pairs(M) > 2 * Kpad ? 2 * fft_pairs(M) : 2 * Kpad; }
+// the wave's z region: the transform's M pairs, then the mel terms (two rows of Kpad floats, Kpad > M), then the descriptors' chains
 // TUNED: the shipped geometry -- 16 kHz, 20 ms frames (N = 320, hop 160, FFT 512, symmetric padding: 96 zeros in front), the 60 ms
-// window of the zero-crossing rate 960 samples, reference-order transform tables present -- as compile-time facts: the range tests of
-// the loads and the own-order transform's code path go, the staged tables are LDS pointers on every path (no flat loads)
+// window of the zero-crossing rate 960 samples -- as compile-time facts: the range tests of the loads go
 template <int W, bool TUNED = false>                   // K = 64 W + 1 bins: W = 4 at 16 kHz (FFT 512), 2 / 8 for FFT 256 / 1024
 __device__ __forceinline__ void compare_frame_wave_body(const LldParams &P, const CompareParams &Q_in, int n_runs, float *smem) {
   struct Geo { int N, H, pad_left, N60; };
@@ -216,15 +202,14 @@ __device__ __forceinline__ void compare_frame_wave_body(const LldParams &P, cons
   for (int i = threadIdx.x; i < K; i += blockDim.x) s_coef[i] = P.mel_coef[i];
   for (int i = threadIdx.x; i < 4 * P.n_bands; i += blockDim.x) s_rng[i] = P.mel_rng[i];
   for (int i = threadIdx.x; i < P.n_mfcc * P.n_bands; i += blockDim.x) s_dct[i] = P.dct_rows[i];
-  const OouraTab OO = oo_stage_tables<TUNED>(P.oo, s_dct + 16 * 32, threadIdx.x, blockDim.x);   // reference-order FFT tables (or none)
+  const OouraTab OO = oo_stage_tables(P.oo, s_dct + 16 * 32, threadIdx.x, blockDim.x);   // reference-order FFT tables
   __syncthreads();                                       // the only workgroup barrier
   const int run = blockIdx.x * 4 + wave;
   if (run >= n_runs) return;
   const int rawpad = (Gq.N60 + 3) & ~3;
-  const int per_wave = compare_z_floats(M, Kpad) + 3 * Kpad + 96 + rawpad;
+  const int per_wave = 2 * Kpad + 3 * Kpad + 96 + rawpad;
   float2 *z = reinterpret_cast<float2 *>(s_dct + 16 * 32 + oo_table_floats(P.oo) + wave * per_wave);   // the transform's (re, im) pairs
-  const int zpad = fft_pad(M);
-  float *mg = reinterpret_cast<float *>(z) + compare_z_floats(M, Kpad);
+  float *mg = reinterpret_cast<float *>(z) + 2 * Kpad;
   float *yv = mg;                                        // the raw frame lives in mg | pw (N <= 2 M < 2 Kpad) until the transform has read it
   float *pw = mg + Kpad;
   float *prev = pw + Kpad;
@@ -236,8 +221,6 @@ __device__ __forceinline__ void compare_frame_wave_body(const LldParams &P, cons
   // the int16 / float accessor -- 45 dependent loads per lane and frame, 28 % of the kernel.)
   float *raw = lmel + 32;
   (void)yv;
-  int logM = 0;
-  while ((1 << logM) < M) ++logM;
 
   const int u = Q.run_utt[run];
   const int t0 = Q.run_t0[run];
@@ -298,11 +281,10 @@ __device__ __forceinline__ void compare_frame_wave_body(const LldParams &P, cons
       return make_float2((n0 >= 0 && n0 < Gq.N) ? R(n0) * P.window[n0] + P.win_offset : 0.0f,
                          (n1 >= 0 && n1 < Gq.N) ? R(n1) * P.window[n1] + P.win_offset : 0.0f);
     };
-    if (TUNED || OO.tw) oo_wave_forward<TUNED ? 256 : 0>(z, OO, lane, load_pair);  // the reference's rdft network, register form (lld_ooura_wave.hpp)
-    else wave_cfft(z, M, P.tw_half, lane, load_pair);
+    oo_wave_forward<TUNED ? 256 : 0>(z, OO, lane, load_pair);  // the reference's rdft network, register form (lld_ooura_wave.hpp)
     PHASE(1);
     for (int k = lane; k <= M; k += 64) {
-      const float m = bin_magnitude((TUNED || OO.tw) ? oo_wave_bin<TUNED ? 256 : 0>(z, OO, k) : wave_untangle(z, M, zpad, k, P.tw_full), k == 0 || k == M);
+      const float m = bin_magnitude(oo_wave_bin<TUNED ? 256 : 0>(z, OO, k), k == 0 || k == M);
       mg[k] = m;
       pw[k] = m * m;
     }
@@ -418,7 +400,7 @@ __global__ void __launch_bounds__(kCmpQuadWaves * 64) __attribute__((amdgpu_wave
   for (int i = threadIdx.x; i < cq::kK; i += NT) s_coef[i] = P.mel_coef[i];
   for (int i = threadIdx.x; i < 4 * cq::kBands; i += NT) s_rng[i] = P.mel_rng[i];
   for (int i = threadIdx.x; i < cq::kMfcc * cq::kBands; i += NT) s_dct[i] = P.dct_rows[i];
-  const OouraTab OO = oo_stage_tables<true>(P.oo, smem + cq::kTableFloats, threadIdx.x, NT);
+  const OouraTab OO = oo_stage_tables(P.oo, smem + cq::kTableFloats, threadIdx.x, NT);
   __syncthreads();                                       // the only workgroup barrier
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int first_run = (blockIdx.x * kCmpQuadWaves + wave) * 4;
@@ -576,10 +558,10 @@ hipError_t launch_compare(const LldParams &P, const CompareParams &Q, int n_runs
   const int M = P.Nfft / 2;
   const int Npad = (P.N + 3) & ~3, Kpad = (P.K + 3) & ~3;
   if ((P.Nfft != 256 && P.Nfft != 512 && P.Nfft != 1024) || P.K != M + 1 || P.N > P.Nfft) return hipErrorInvalidValue;   // 20 ms at 8 .. 48 kHz
+  if (!P.oo.tw) return hipErrorInvalidValue;              // every form runs the reference-order transform
   static const bool use_block = getenv("SMILEHIP_COMPARE_BLOCK") != nullptr;      // the one-workgroup-per-run kernel (A/B checks, FFT 512)
   if (P.Nfft != 512) {
-    const size_t lds = sizeof(float) * (size_t)(512 + Kpad + 128 + 16 * 32 + oo_table_floats(P.oo) + 4 * (compare_z_floats(M, Kpad) + 3 * Kpad + 96 + ((Q.N60 + 3) & ~3)));
-    if (!P.oo.tw) return hipErrorInvalidValue;            // (the own-order A/B transform exists for the tuned geometry only)
+    const size_t lds = sizeof(float) * (size_t)(512 + Kpad + 128 + 16 * 32 + oo_table_floats(P.oo) + 4 * (2 * Kpad + 3 * Kpad + 96 + ((Q.N60 + 3) & ~3)));
     const void *fn = P.Nfft == 256 ? reinterpret_cast<const void *>(&lld_compare_frame_wave_g<2>) : reinterpret_cast<const void *>(&lld_compare_frame_wave_g<8>);
     hipError_t ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (ea != hipSuccess) return ea;
@@ -590,7 +572,7 @@ hipError_t launch_compare(const LldParams &P, const CompareParams &Q, int n_runs
                        sizeof(float) * (size_t)(Kpad + 128 + 16 * 32);
     SMILEHIP_KLAUNCH(lld_compare_frame, dim3((unsigned)n_runs), dim3(256), lds, s, P, Q);
   } else {
-    const size_t lds = sizeof(float) * (size_t)(512 + Kpad + 128 + 16 * 32 + oo_table_floats(P.oo) + 4 * (compare_z_floats(M, Kpad) + 3 * Kpad + 96 + ((Q.N60 + 3) & ~3)));
+    const size_t lds = sizeof(float) * (size_t)(512 + Kpad + 128 + 16 * 32 + oo_table_floats(P.oo) + 4 * (2 * Kpad + 3 * Kpad + 96 + ((Q.N60 + 3) & ~3)));
     if (P.N > Q.N60) return hipErrorInvalidValue;
     if (lds > 48 * 1024) {
       hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(&lld_compare_frame_wave), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -603,7 +585,7 @@ hipError_t launch_compare(const LldParams &P, const CompareParams &Q, int n_runs
     // (the quad form first: it is short enough not to crowd out a small batch's jitter pass, the reason for the two-wave build below)
     // ONE statement of when the sixteen-lanes-per-frame form runs (the condition used to be written twice and the two
     // copies differed -- with SMILEHIP_COMPARE_WAVE=1 on a small batch the launch went to wave3t instead of the two-wave kernel)
-    const bool tuned_geo = P.oo.tw && P.N == 320 && P.H == 160 && P.pad_left == 96 && Q.N60 == 960 && P.K == 257;
+    const bool tuned_geo = P.N == 320 && P.H == 160 && P.pad_left == 96 && Q.N60 == 960 && P.K == 257;
     const bool use_quad = tuned_geo && P.n_bands == 26 && P.n_mfcc == 14 && P.pcm && !P.pcm_f32 && !(force && force[0] == '2') &&
                           P.total_frames < (int64_t(1) << 31) && Q.max_utt_samples < (int64_t(1) << 31) &&
                           Q.band_iL[0] >= 0 && Q.band_iL[0] < Q.band_iR[0] && Q.band_iR[0] <= 256 &&

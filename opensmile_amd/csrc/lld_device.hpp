@@ -88,42 +88,6 @@ __device__ __forceinline__ float mel_band_from_terms(const float *a, const float
   return acc * scale;
 }
 
-// R4 core: in-place radix-2 DIT complex FFT of length M in LDS (re/im already
-// loaded in bit-reversed order), executed by the whole workgroup.
-__device__ __forceinline__ void block_cfft_radix2(float *re, float *im, int M, const float2 *tw_half) {
-  for (int len = 2; len <= M; len <<= 1) {
-    const int half = len >> 1;
-    const int tstep = M / len;
-    for (int b = threadIdx.x; b < (M >> 1); b += blockDim.x) {
-      const int j = b & (half - 1);
-      const int i0 = ((b - j) << 1) + j;
-      const int i1 = i0 + half;
-      const float2 w = tw_half[j * tstep];
-      const float xr = re[i1], xi = im[i1];
-      const float tr = fmaf(xr, w.x, -xi * w.y);
-      const float ti = fmaf(xr, w.y, xi * w.x);
-      const float ar = re[i0], ai = im[i0];
-      re[i1] = ar - tr; im[i1] = ai - ti;
-      re[i0] = ar + tr; im[i0] = ai + ti;
-    }
-    __syncthreads();
-  }
-}
-
-// Real-FFT untangle of bin k (0 <= k <= M) from the half-length complex FFT Z
-// of z[i] = x[2i] + i x[2i+1]:
-//   X[k] = 1/2 [ (Z[k] + conj Z[M-k]) - i w^k (Z[k] - conj Z[M-k]) ],  w = e^{-2 pi i/(2M)}
-// Returns the standard DFT X[k] = sum x[n] e^{-2 pi i nk/Nfft}.
-__device__ __forceinline__ float2 untangle_bin(const float *re, const float *im, int M, int k,
-                                               const float2 *tw_full) {
-  if (k == 0) return make_float2(re[0] + im[0], 0.0f);
-  if (k == M) return make_float2(re[0] - im[0], 0.0f);
-  const float a = re[k], b = im[k], c = re[M - k], d = im[M - k];
-  const float2 w = (k <= (M >> 1)) ? tw_full[k] : make_float2(-tw_full[M - k].x, tw_full[M - k].y);
-  const float sr = a + c, si = b - d, dr = a - c, di = b + d;
-  return make_float2(0.5f * fmaf(w.x, di, fmaf(w.y, dr, sr)), 0.5f * fmaf(w.y, di, fmaf(-w.x, dr, si)));
-}
-
 // R5: cFFTmagphase magnitude (fftmagphase.cpp:215-221). sqrtf() compiles to the
 // correctly rounded sequence (v_sqrt_f32 + two FMA fix-ups); __fsqrt_rn is the
 // bare 1-ulp instruction on gfx950 and must not be used where bit-parity counts.

@@ -27,7 +27,6 @@
 #include <type_traits>
 
 #include "lld_blocks.hpp"
-#include "lld_fft.hpp"
 #include "lld_device.hpp"
 #include "lld_launch.hpp"
 #include "lld_params.hpp"
@@ -51,7 +50,7 @@ struct F0G {
   static constexpr bool kRegFft = LOGM <= 9;                // register-resident transform (lld_ooura_wave.hpp: M = 256 / 512)
   static constexpr bool kLdsTables = LOGM <= 9;             // per-bin tables staged in LDS (above: read through the caches)
   static constexpr int kSpecWaves = LOGM <= 9 ? 4 : (LOGM == 10 ? 2 : 1);   // frames (waves) per workgroup of spec / cand
-  // LDS bytes of the transform's tables: radix-2 order twh | twf = 4128 B (M = 512), reference order <= 12 M (6016 B for M = 512)
+  // LDS bytes kept for the reference-order transform's tables: <= 12 M (6016 B for M = 512)
   static constexpr size_t kTwBytes = (size_t)12 * kM;
   // one frame's LDS region: A[kKP] B[kKP] doubles | ci[8] ints (ci[7]: number of candidates) | cf[3][8] floats | double
   static constexpr size_t kFrameBytes = (size_t)kKP * 16 + 8 * 4 + 24 * 4 + 16;   // + the frame's sum of squares
@@ -64,9 +63,7 @@ struct F0Tbl {
   const double *dec, *d1, *d2, *a, *c, *d, *audw;   // [kKP] each
   const int *k;          // [kKP]
   const float *win;      // [NP]
-  const float2 *twh;     // [kM/2]
-  const float2 *twf;     // [kM/2+4]
-  OouraTab oo;           // reference-order transform: its tables take the place of twh | twf (kF0TwBytes)
+  OouraTab oo;           // the reference-order transform's tables (kTwBytes)
 };
 template <class G>
 __host__ __device__ inline size_t f0_shared_bytes(int N) {
@@ -130,18 +127,18 @@ extern "C" int smilehip_debug_phase_sweep(unsigned long long *out8, int reset) {
 // enh_store (optional): a functor (bin, float) that takes the enhanced magnitudes -- they are floats widened, or zero -- and
 // ends the function there (the chain's lld_f0_spec: smoothing and the spline are lld_f0_sweep's work, one frame per lane)
 // raw_store (optional): a functor (bin, float) that takes the magnitudes as cFFTmagphase writes them (the level's other readers)
-template <class G, bool OO, class XIn = PcmIn, class EnhStore = std::nullptr_t, class RawStore = std::nullptr_t>   // OO: the reference-order transform (one form per kernel instance: register budget)
+template <class G, class XIn = PcmIn, class EnhStore = std::nullptr_t, class RawStore = std::nullptr_t>
 __device__ __forceinline__ double f0_spectrum(const F0Tbl &T, const F0Params &Q, const XIn x, const float *mag_in, int lane,
                                               double *A, double *B, EnhStore enh_store = nullptr, RawStore raw_store = nullptr) {
   F0_GEO;
-  float2 *z = reinterpret_cast<float2 *>(A);             // WaveFft<9>::kZ pairs: A and the first 480 bytes of B (B == A + kKP)
+  float2 *z = reinterpret_cast<float2 *>(A);             // the transform's kM pairs: inside A (kKP doubles)
   double esum = 0.0;
   double mg[kPer];
   if (mag_in) {                                          // per-component mode: cSpecScale on a given magnitude spectrum
     F0_FOR_BINS(m, k) mg[m] = (k < kK) ? (double)mag_in[k] : 0.0;
   } else {
   // R0 + R3 (gauss) + R12 energy of the windowed frame ([is13_energy60], energy.cpp:152-168); the transform's first pass
-  // asks for the inputs it needs (lld_fft.hpp)
+  // asks for the inputs it needs
   // (branch-free: a sample outside the frame is read at index 0 and replaced by +0 -- its square adds +0.0 to the sum, which changes
   //  nothing --, so that the transform's sixteen loads per lane are in flight together instead of each behind its own branch and wait)
   const auto load_pair = [&](int i) {
@@ -155,20 +152,9 @@ __device__ __forceinline__ double f0_spectrum(const F0Tbl &T, const F0Params &Q,
     { const float sq = b * b; esum += (double)sq; }
     return make_float2(a, b);
   };
-  if constexpr (OO && !G::kRegFft) {                     // the reference's rdft network in place in LDS (lld_ooura.hpp): any length
-    ooura_forward<WaveG>(z, T.oo, load_pair);
-    esum = WaveG::sum(esum, nullptr);
-  } else if constexpr (OO) {                             // the same network register-resident (lld_ooura_wave.hpp); lane l holds l + 64 m
-    oo_wave_forward<kM>(z, T.oo, lane, load_pair);
-    esum = WaveG::sum(esum, nullptr);
-  } else {
-    static_assert(OO || G::kLogM == 9, "the radix-2 order transform exists for FFT 1024 only");
-    WaveFft<9>::forward(z, T.twh, lane, load_pair);
-    // (lane l summed the inputs brev6(l) + 64 k: low offsets first is the tree the sum had when lane l held l + 64 m)
-    esum += wave_down_d<1>(esum); esum += wave_down_d<2>(esum); esum += wave_down_d<4>(esum);     // (lane 0's tree of the xor
-    esum += wave_down_d<8>(esum); esum += wave_down_d<16>(esum); esum += wave_down_d<32>(esum);  //  butterfly, lld_blocks.hpp)
-    esum = wave_first_d(esum);
-  }
+  if constexpr (!G::kRegFft) ooura_forward<WaveG>(z, T.oo, load_pair);   // the reference's rdft network in place in LDS (lld_ooura.hpp): any length
+  else oo_wave_forward<kM>(z, T.oo, lane, load_pair);    // the same network register-resident (lld_ooura_wave.hpp); lane l holds l + 64 m
+  esum = WaveG::sum(esum, nullptr);
   {
     // rows m < kPer - 1 are inner bins (sqrt(re^2 + im^2): sqrt_rn_batch, lld_device.hpp) except bin 0 (lane 0, m = 0); the last row
     // is bin kM for lane 0 alone: |re|
@@ -177,9 +163,8 @@ __device__ __forceinline__ double f0_spectrum(const F0Tbl &T, const F0Params &Q,
     F0_FOR_BINS(m, k) {
       float2 X = make_float2(0.0f, 0.0f);
       if (k < kK) {
-        if constexpr (OO && !G::kRegFft) X = ooura_bin(z, T.oo, k);
-        else if constexpr (OO) X = oo_wave_bin<kM>(z, T.oo, k);
-        else X = fft_untangle<WaveFft<9>>(z, k, T.twf);
+        if constexpr (!G::kRegFft) X = ooura_bin(z, T.oo, k);
+        else X = oo_wave_bin<kM>(z, T.oo, k);
       }
       mf[m] = (m < kPer - 1) ? X.x * X.x + X.y * X.y : ((k < kK) ? fabsf(X.x) : 0.0f);
       if (m == 0) edge0 = fabsf(X.x);
@@ -192,7 +177,7 @@ __device__ __forceinline__ double f0_spectrum(const F0Tbl &T, const F0Params &Q,
       if constexpr (!std::is_same<RawStore, std::nullptr_t>::value) { if (k < kK) raw_store(k, mf[m]); }
     }
   }
-  WaveG::sync();                                         // the transform's buffer reaches into B
+  WaveG::sync();                                         // every lane has read its bins of z
   }
   F0_FOR_BINS(m, k) if (k < kK) B[k] = mg[m];
   WaveG::sync();
@@ -607,7 +592,7 @@ __device__ __forceinline__ void f0_candidates(const F0Params &Q, int lane, int64
   WaveG::sync();
 }
 
-template <int LOGM, bool OO>
+template <int LOGM>
 __global__ void __launch_bounds__(kWaves * 64) lld_f0_frame(LldParams P, F0Params Q) {
   using G = F0G<LOGM>;
   F0_GEO;
@@ -621,8 +606,6 @@ __global__ void __launch_bounds__(kWaves * 64) lld_f0_frame(LldParams P, F0Param
   double *c_d1 = c_dec + kKP, *c_d2 = c_d1 + kKP, *c_a = c_d2 + kKP, *c_c = c_a + kKP, *c_d = c_c + kKP, *c_audw = c_d + kKP;
   int *c_k = reinterpret_cast<int *>(c_audw + kKP);
   float *c_win = reinterpret_cast<float *>(c_k + kKP);
-  float2 *c_twh = reinterpret_cast<float2 *>(c_win + NP);
-  float2 *c_twf = c_twh + kM / 2;
   for (int i = threadIdx.x; i < kK; i += blockDim.x) {
     c_sp[i] = make_double2(Q.sp_rec[4 * i], Q.sp_rec[4 * i + 1]);
     c_dec[i] = Q.sp_rec[4 * i + 2];
@@ -632,17 +615,12 @@ __global__ void __launch_bounds__(kWaves * 64) lld_f0_frame(LldParams P, F0Param
     c_k[i] = Q.ip_k[i];
   }
   for (int i = threadIdx.x; i < Q.N; i += blockDim.x) c_win[i] = Q.window[i];
-  OouraTab c_oo = OouraTab{};
-  if (Q.oo.tw) c_oo = oo_stage_tables(Q.oo, reinterpret_cast<float *>(c_twh), threadIdx.x, blockDim.x);
-  else {
-    for (int i = threadIdx.x; i < kM / 2; i += blockDim.x) c_twh[i] = Q.tw_half[i];
-    for (int i = threadIdx.x; i <= kM / 2; i += blockDim.x) c_twf[i] = Q.tw_full[i];
-  }
+  const OouraTab c_oo = oo_stage_tables(Q.oo, c_win + NP, threadIdx.x, blockDim.x);
   __syncthreads();                                       // the only workgroup barrier
   F0Tbl T;
   T.oo = c_oo;
   T.sp = c_sp; T.dec = c_dec; T.d1 = c_d1; T.d2 = c_d2; T.a = c_a; T.c = c_c; T.d = c_d; T.audw = c_audw;
-  T.k = c_k; T.win = c_win; T.twh = c_twh; T.twf = c_twf;
+  T.k = c_k; T.win = c_win;
   unsigned char *base = smem_f0 + f0_shared_bytes<G>(Q.N) + (size_t)wave * (kW * kFrameBytes);
   PHASE_DECL
   // persistent waves: work item = up to kTileFrames consecutive frames of one utterance (TileRec), kW at a time
@@ -659,7 +637,7 @@ __global__ void __launch_bounds__(kWaves * 64) lld_f0_frame(LldParams P, F0Param
       for (int w = 0; w < n_act; ++w) {
         double *A = reinterpret_cast<double *>(base + w * kFrameBytes);
         if (mode == 2) break;
-        const double es = f0_spectrum<G, OO>(T, Q, pcm_in(P) + (samp0 + (int64_t)(tf + w) * Q.H),
+        const double es = f0_spectrum<G>(T, Q, pcm_in(P) + (samp0 + (int64_t)(tf + w) * Q.H),
                                       mode == 1 ? Q.in_rows + (row0 + tf + w) * Q.ld_in : nullptr, lane, A, A + kKP);
         if (lane == 0) *reinterpret_cast<double *>(reinterpret_cast<int *>(A + 2 * kKP) + 8 + 24) = es;
       }
@@ -737,12 +715,12 @@ __device__ __forceinline__ F0Scratch f0_scratch(const F0Params &Q) {
   return S;
 }
 template <class G>
-__host__ __device__ inline size_t f0_spec_shared_bytes(int N) {      // win | twh | twf
+__host__ __device__ inline size_t f0_spec_shared_bytes(int N) {      // win | the transform's tables
   const size_t np = (size_t)((N + 3) & ~3);
   return np * 4 + G::kTwBytes;
 }
 
-template <int LOGM, bool OO, bool S16 = false>         // S16: the instance for 16-bit input (the tuned geometry's fast path)
+template <int LOGM, bool S16 = false>                  // S16: the instance for 16-bit input (the tuned geometry's fast path)
 __device__ __forceinline__ void f0_spec_body(const LldParams &P, const F0Params &Q) {
   using G = F0G<LOGM>;
   F0_GEO;
@@ -752,19 +730,12 @@ __device__ __forceinline__ void f0_spec_body(const LldParams &P, const F0Params 
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int NP = (Q.N + 3) & ~3;
   float *c_win = reinterpret_cast<float *>(smem_f0);
-  float2 *c_twh = reinterpret_cast<float2 *>(c_win + NP);
-  float2 *c_twf = c_twh + kM / 2;
   for (int i = threadIdx.x; i < Q.N; i += blockDim.x) c_win[i] = Q.window[i];
-  OouraTab c_oo = OouraTab{};
-  if (Q.oo.tw) c_oo = oo_stage_tables(Q.oo, reinterpret_cast<float *>(c_twh), threadIdx.x, blockDim.x);
-  else {
-    for (int i = threadIdx.x; i < kM / 2; i += blockDim.x) c_twh[i] = Q.tw_half[i];
-    for (int i = threadIdx.x; i <= kM / 2; i += blockDim.x) c_twf[i] = Q.tw_full[i];
-  }
+  const OouraTab c_oo = oo_stage_tables(Q.oo, c_win + NP, threadIdx.x, blockDim.x);
   __syncthreads();
   F0Tbl T = {};
   T.oo = c_oo;
-  T.win = c_win; T.twh = c_twh; T.twf = c_twf;
+  T.win = c_win;
   double *A = reinterpret_cast<double *>(smem_f0 + f0_spec_shared_bytes<G>(Q.N)) + (size_t)wave * 2 * kKP;
   const int tile = Q.tile0 + blockIdx.x * kSpecWaves + wave;
   if (tile >= Q.tile0 + Q.n_tiles_chunk) return;
@@ -780,21 +751,21 @@ __device__ __forceinline__ void f0_spec_body(const LldParams &P, const F0Params 
     float *keep = Q.mag_keep ? Q.mag_keep + (P.tile_rec[tile].row0 + w) * Q.mag_ld : nullptr;      // (wave-uniform)
     const auto raw = [&](int i, float v) { if (keep) keep[i] = v; };
     double es;
-    if constexpr (S16) es = f0_spectrum<G, OO, Pcm16In>(T, Q, Pcm16In{P.pcm} + (samp0 + (int64_t)w * Q.H), nullptr, lane, A, A + kKP, store, raw);
-    else if (P.pcm_f32) es = f0_spectrum<G, OO, PcmF32In>(T, Q, PcmF32In{P.pcm_f32} + (samp0 + (int64_t)w * Q.H), nullptr, lane, A, A + kKP, store, raw);
-    else es = f0_spectrum<G, OO, Pcm16In>(T, Q, Pcm16In{P.pcm} + (samp0 + (int64_t)w * Q.H), nullptr, lane, A, A + kKP, store, raw);
+    if constexpr (S16) es = f0_spectrum<G, Pcm16In>(T, Q, Pcm16In{P.pcm} + (samp0 + (int64_t)w * Q.H), nullptr, lane, A, A + kKP, store, raw);
+    else if (P.pcm_f32) es = f0_spectrum<G, PcmF32In>(T, Q, PcmF32In{P.pcm_f32} + (samp0 + (int64_t)w * Q.H), nullptr, lane, A, A + kKP, store, raw);
+    else es = f0_spectrum<G, Pcm16In>(T, Q, Pcm16In{P.pcm} + (samp0 + (int64_t)w * Q.H), nullptr, lane, A, A + kKP, store, raw);
     if (lane == 0) S.es[fr] = es;
     WaveG::sync();
   }
 }
 // (the register budget of the tuned geometry is pinned; the other geometries take what the compiler gives them)
-template <bool OO, bool S16>
+template <bool S16>
 __global__ void __launch_bounds__(F0G<9>::kSpecWaves * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) lld_f0_spec(LldParams P, F0Params Q) {
-  f0_spec_body<9, OO, S16>(P, Q);
+  f0_spec_body<9, S16>(P, Q);
 }
 template <int LOGM>
 __global__ void __launch_bounds__(F0G<LOGM>::kSpecWaves * 64) lld_f0_spec_g(LldParams P, F0Params Q) {
-  f0_spec_body<LOGM, true>(P, Q);
+  f0_spec_body<LOGM>(P, Q);
 }
 
 // The sweep's divisions: div_markstein (lld_device.hpp) with the reciprocals of the host table (sw_rec: d1, RN(1 / d1), d2, RN(1 / d2))
@@ -1118,7 +1089,7 @@ __global__ void __launch_bounds__(64) lld_f0_rows_big(F0Params Q) {
   F0Tbl T = {};
   T.d1 = Q.sp_d1; T.d2 = Q.sp_d2; T.audw = Q.audw; T.k = Q.ip_k; T.oo = Q.oo;
   if (Q.mode == 1) {
-    f0_spectrum<G, true>(T, Q, PcmIn{nullptr, nullptr}, Q.in_rows + row * Q.ld_in, lane, A, B);
+    f0_spectrum<G>(T, Q, PcmIn{nullptr, nullptr}, Q.in_rows + row * Q.ld_in, lane, A, B);
     if (lane == 0) {                                     // smileMath_cspline's two recurrences (see lld_f0_sweep)
       const double *sp = Q.sp_rec;
       double up = 0.0;
@@ -1497,15 +1468,11 @@ hipError_t launch_f0_chunks(const LldParams &P, const F0Params &Q0, hipStream_t 
   constexpr int kSpecWaves = G::kSpecWaves;
   const size_t lds_spec = f0_spec_shared_bytes<G>(Q0.N) + (size_t)kSpecWaves * 2 * G::kKP * sizeof(double);
   const size_t lds_cand = (size_t)kSpecWaves * G::kFrameBytes;
-  if (!Q0.ip_rec || !Q0.ip_cnt || !Q0.sw_rec) return hipErrorInvalidValue;
-  const bool oo = Q0.oo.tw != nullptr;
-  if (!oo && LOGM != 9) return hipErrorInvalidValue;     // SMILEHIP_FFT=radix2 (the A/B switch) exists for FFT 1024 only
+  if (!Q0.ip_rec || !Q0.ip_cnt || !Q0.sw_rec || !Q0.oo.tw) return hipErrorInvalidValue;
   const void *spec;
   const bool s16 = P.pcm_f32 == nullptr;
-  if constexpr (LOGM == 9) {
-    if (oo) spec = s16 ? reinterpret_cast<const void *>(&lld_f0_spec<true, true>) : reinterpret_cast<const void *>(&lld_f0_spec<true, false>);
-    else spec = s16 ? reinterpret_cast<const void *>(&lld_f0_spec<false, true>) : reinterpret_cast<const void *>(&lld_f0_spec<false, false>);
-  } else spec = reinterpret_cast<const void *>(&lld_f0_spec_g<LOGM>);
+  if constexpr (LOGM == 9) spec = s16 ? reinterpret_cast<const void *>(&lld_f0_spec<true>) : reinterpret_cast<const void *>(&lld_f0_spec<false>);
+  else spec = reinterpret_cast<const void *>(&lld_f0_spec_g<LOGM>);
   hipError_t e = hipFuncSetAttribute(spec, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_spec);
   if (e != hipSuccess) return e;
   e = hipFuncSetAttribute(LOGM == 9 ? reinterpret_cast<const void *>(&lld_f0_cand9) : reinterpret_cast<const void *>(&lld_f0_cand<LOGM>),
@@ -1535,10 +1502,8 @@ hipError_t launch_f0_chunks(const LldParams &P, const F0Params &Q0, hipStream_t 
     }
     const unsigned grid = (unsigned)((Q.n_tiles_chunk + kSpecWaves - 1) / kSpecWaves);
     if constexpr (LOGM == 9) {
-      if (oo && s16) SMILEHIP_KLAUNCH((lld_f0_spec<true, true>), dim3(grid), dim3(kSpecWaves * 64), lds_spec, s_spec, P, Q);
-      else if (oo) SMILEHIP_KLAUNCH((lld_f0_spec<true, false>), dim3(grid), dim3(kSpecWaves * 64), lds_spec, s_spec, P, Q);
-      else if (s16) SMILEHIP_KLAUNCH((lld_f0_spec<false, true>), dim3(grid), dim3(kSpecWaves * 64), lds_spec, s_spec, P, Q);
-      else SMILEHIP_KLAUNCH((lld_f0_spec<false, false>), dim3(grid), dim3(kSpecWaves * 64), lds_spec, s_spec, P, Q);
+      if (s16) SMILEHIP_KLAUNCH(lld_f0_spec<true>, dim3(grid), dim3(kSpecWaves * 64), lds_spec, s_spec, P, Q);
+      else SMILEHIP_KLAUNCH(lld_f0_spec<false>, dim3(grid), dim3(kSpecWaves * 64), lds_spec, s_spec, P, Q);
     } else {
       SMILEHIP_KLAUNCH(lld_f0_spec_g<LOGM>, dim3(grid), dim3(kSpecWaves * 64), lds_spec, s_spec, P, Q);
     }
@@ -1613,11 +1578,8 @@ hipError_t launch_f0_rows_g(const F0Params &Q, int max_blocks, hipStream_t s) {
   using G = F0G<LOGM>;
   if (!f0_shifts_fit<G>(Q)) return hipErrorInvalidValue;
   const size_t lds = f0_shared_bytes<G>(Q.N) + G::kFrameBytes * kW * kWaves;
-  const bool oo = Q.oo.tw != nullptr;
-  if (!oo && LOGM != 9) return hipErrorInvalidValue;
-  const void *fn;
-  if constexpr (LOGM == 9) fn = oo ? reinterpret_cast<const void *>(&lld_f0_frame<9, true>) : reinterpret_cast<const void *>(&lld_f0_frame<9, false>);
-  else fn = reinterpret_cast<const void *>(&lld_f0_frame<LOGM, true>);
+  if (!Q.oo.tw) return hipErrorInvalidValue;
+  const void *fn = reinterpret_cast<const void *>(&lld_f0_frame<LOGM>);
   hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
   const int64_t tiles = (Q.n_rows + kTileFrames - 1) / kTileFrames;
@@ -1625,12 +1587,7 @@ hipError_t launch_f0_rows_g(const F0Params &Q, int max_blocks, hipStream_t s) {
   if (grid > (unsigned)max_blocks) grid = (unsigned)max_blocks;
   LldParams P;
   std::memset(&P, 0, sizeof(P));
-  if constexpr (LOGM == 9) {
-    if (oo) SMILEHIP_KLAUNCH((lld_f0_frame<9, true>), dim3(grid), dim3(kWaves * 64), lds, s, P, Q);
-    else SMILEHIP_KLAUNCH((lld_f0_frame<9, false>), dim3(grid), dim3(kWaves * 64), lds, s, P, Q);
-  } else {
-    SMILEHIP_KLAUNCH((lld_f0_frame<LOGM, true>), dim3(grid), dim3(kWaves * 64), lds, s, P, Q);
-  }
+  SMILEHIP_KLAUNCH(lld_f0_frame<LOGM>, dim3(grid), dim3(kWaves * 64), lds, s, P, Q);
   return hipGetLastError();
 }
 }  // namespace

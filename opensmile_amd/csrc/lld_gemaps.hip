@@ -25,7 +25,6 @@
 #include <cstring>
 
 #include "lld_blocks.hpp"
-#include "lld_fft.hpp"
 #include "lld_blocks_compare.hpp"
 #include "lld_gemaps_quad.hpp"
 #include "lld_device.hpp"
@@ -177,9 +176,10 @@ __device__ __forceinline__ void gemaps_spectral_wave(const float *mg, const floa
 }
 
 // ------------------------------------------------------------------------------------------------ 20 ms frames
-// LDS: shared coef[Kpad] | rng[128] | dct[16 x 32]; per wave z[fft_pairs(M)] pairs | mg[Kpad] | pw[Kpad] | prev[Kpad] |
+// LDS: shared coef[Kpad] | rng[128] | dct[16 x 32]; per wave z[2 Kpad] | mg[Kpad] | pw[Kpad] | prev[Kpad] |
 // lg[64] | mel[32] | aud[32] | lmel[32]
-__global__ void __launch_bounds__(256) lld_gemaps_frame20(LldParams P, GemapsParams G, int n_runs) {
+// (the register budget of seven waves per SIMD is pinned: left alone the allocator takes 74 VGPRs, two above that step; 70 and no scratch with it)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) lld_gemaps_frame20(LldParams P, GemapsParams G, int n_runs) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int M = P.Nfft >> 1, K = P.K;
   const int Kpad = (K + 3) & ~3;
@@ -191,14 +191,13 @@ __global__ void __launch_bounds__(256) lld_gemaps_frame20(LldParams P, GemapsPar
   for (int i = threadIdx.x; i < K; i += blockDim.x) s_coef[i] = P.mel_coef[i];
   for (int i = threadIdx.x; i < 4 * P.n_bands; i += blockDim.x) s_rng[i] = P.mel_rng[i];
   for (int i = threadIdx.x; i < P.n_mfcc * P.n_bands; i += blockDim.x) s_dct[i] = P.dct_rows[i];
-  const OouraTab OO = oo_stage_tables(P.oo, s_dct + 16 * 32, threadIdx.x, blockDim.x);   // reference-order FFT tables (or none)
+  const OouraTab OO = oo_stage_tables(P.oo, s_dct + 16 * 32, threadIdx.x, blockDim.x);   // reference-order FFT tables
   __syncthreads();                                       // the only workgroup barrier
   const int run = blockIdx.x * 4 + wave;
   if (run >= n_runs) return;
-  const int zf = 2 * fft_pairs(M) > 2 * Kpad ? 2 * fft_pairs(M) : 2 * Kpad;     // the transform's pairs, then the mel terms (two rows of Kpad floats)
+  const int zf = 2 * Kpad;                               // the transform's M pairs, then the mel terms (two rows of Kpad floats, Kpad > M)
   const int per_wave = zf + 3 * Kpad + 64 + 96;
   float2 *z = reinterpret_cast<float2 *>(s_dct + 16 * 32 + oo_table_floats(P.oo) + wave * per_wave);   // the transform's (re, im) pairs
-  const int zpad = fft_pad(M);
   float *mg = reinterpret_cast<float *>(z) + zf;
   float *yv = mg;                                        // the raw frame lives in mg | pw (N <= 2 M < 2 Kpad) until the transform has read it
   float *pw = mg + Kpad;
@@ -207,8 +206,6 @@ __global__ void __launch_bounds__(256) lld_gemaps_frame20(LldParams P, GemapsPar
   float *melv = lg + 64;
   float *aud = melv + 32;
   float *lmel = aud + 32;
-  int logM = 0;
-  while ((1 << logM) < M) ++logM;
 
   const int u = G.run_utt[run];
   const int t0 = G.run_t0[run];
@@ -254,12 +251,11 @@ __global__ void __launch_bounds__(256) lld_gemaps_frame20(LldParams P, GemapsPar
       return make_float2((n0 >= 0 && n0 < P.N) ? yv[n0] * P.window[n0] + P.win_offset : 0.0f,
                          (n1 >= 0 && n1 < P.N) ? yv[n1] * P.window[n1] + P.win_offset : 0.0f);
     };
-    if (OO.tw) oo_wave_forward(z, OO, lane, load_pair);  // the reference's rdft network, register form (lld_ooura_wave.hpp)
-    else wave_cfft(z, M, P.tw_half, lane, load_pair);
+    oo_wave_forward(z, OO, lane, load_pair);             // the reference's rdft network, register form (lld_ooura_wave.hpp)
     GPHASE(1);   // FFT
     float *spec = G.spec220 + (f0 + t) * kRsI;
     for (int k = lane; k <= M; k += 64) {
-      const float2 X = OO.tw ? oo_wave_bin(z, OO, k) : wave_untangle(z, M, zpad, k, P.tw_full);
+      const float2 X = oo_wave_bin(z, OO, k);
       const float m = bin_magnitude(X, k == 0 || k == M);
       mg[k] = m;
       pw[k] = m * m;                                     // squareInput (spectral.cpp:677-684) == melspec usePower
@@ -325,7 +321,7 @@ __global__ void __launch_bounds__(kGmQuadWaves * 64) __attribute__((amdgpu_waves
   for (int i = threadIdx.x; i < gq::kK; i += NT) s_coef[i] = P.mel_coef[i];
   for (int i = threadIdx.x; i < 4 * gq::kBands; i += NT) s_rng[i] = P.mel_rng[i];
   for (int i = threadIdx.x; i < gq::kMfcc * gq::kBands; i += NT) s_dct[i] = P.dct_rows[i];
-  const OouraTab OO = oo_stage_tables<true>(P.oo, smem + gq::kTableFloats, threadIdx.x, NT);
+  const OouraTab OO = oo_stage_tables(P.oo, smem + gq::kTableFloats, threadIdx.x, NT);
   __syncthreads();                                       // the only workgroup barrier
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int first_run = (blockIdx.x * kGmQuadWaves + wave) * 4;
@@ -478,7 +474,7 @@ struct ZsMat {
 #define ZM(m, i, j) ((m).a[(i) - 1][(j) - 1])             // 1-based like the reference's MATF; i, j compile-time after unrolling
 
 __device__ __forceinline__ void zs_balance_reg(ZsMat &m) {   // zerosolveBalanceCmatrix, zerosolve.cpp:22-84
-  const double radix = 2.0, radix2 = 4.0;
+  const double radix = 2.0, radix_sq = 4.0;
   bool converged = false;
   while (__any(!converged)) {
     const bool active = !converged;                        // lanes that are done go through the sweep without effect
@@ -498,9 +494,9 @@ __device__ __forceinline__ void zs_balance_reg(ZsMat &m) {   // zerosolveBalance
       if (!active || ncol == 0.0 || nrow == 0.0) continue;
       double t2 = 1.0, t1 = nrow / radix;
       const double t3 = ncol + nrow;
-      while (ncol < t1) { t2 *= radix; ncol *= radix2; }
+      while (ncol < t1) { t2 *= radix; ncol *= radix_sq; }
       t1 = nrow * radix;
-      while (ncol > t1) { t2 /= radix; ncol /= radix2; }
+      while (ncol > t1) { t2 /= radix; ncol /= radix_sq; }
       if ((nrow + ncol) < 0.95 * t3 * t2) {
         converged = false;
         t1 = 1.0 / t2;
@@ -808,18 +804,18 @@ __global__ void __launch_bounds__(64) lld_gemaps_formants_fix(GemapsParams G, in
 // The 60 ms magnitude spectrum is the level cSpecScale reads (gemapsv01b_fftmagG60): the batch keeps lld_f0_spec's magnitudes
 // (G.mag60, 2 KB per frame: 58 ms less here for 14 ms more there per 37 M frames) when they fit; without them -- batches near the
 // memory limit, the per-component operator's rows come in by G.op_in -- the frame is windowed and transformed here.
-// LDS: shared win[NP] | twh[256] | twf[260]; per wave z[576 pairs] (later hbin[128] | hfi[128] | hmag[128] | hlr[128]) |
-// mg[516] | acf[516]
+// LDS (M = 512): shared win[NP] | reference-order tables (12 M bytes kept for them); per wave z[512 pairs] (later hbin[128] |
+// hfi[128] | hmag[128] | hlr[128]) | mg[516] | acf[516]
 namespace {
 // Geometry of the 60 ms spectrum by sample rate (as in lld_f0.hip): FFT 512 (8 kHz), 1024 (11.025 / 16 kHz: the tuned case),
 // 2048 (22.05 .. 32 kHz), 4096 (44.1 / 48 kHz)
 template <int LOGM>
 struct HarmG {
   static constexpr int kHM = 1 << LOGM, kHK = kHM + 1, kHKP = kHM + 4;
-  static constexpr size_t kTwBytes = (size_t)12 * kHM;    // twh | twf (4128 B for M = 512) or the reference-order tables (<= 12 M, lld_ooura.hpp)
-  // M = 512: 8.7 KB of LDS per wave + 7.9 KB of tables per workgroup: two workgroups = 16 waves per CU
+  static constexpr size_t kTwBytes = (size_t)12 * kHM;    // the reference-order tables (<= 12 M bytes, lld_ooura.hpp)
+  // M = 512: 8.0 KB of LDS per wave + 9.8 KB of window and tables per workgroup: two workgroups = 16 waves per CU
   static constexpr int kWaves = LOGM <= 9 ? 8 : (LOGM == 10 ? 4 : 2);
-  static constexpr int kZ = LOGM == 9 ? WaveFft<9>::kZ : kHM + 64;   // (re, im) pairs of the transform's buffer (>= 256: the harmonics' arrays live there)
+  static constexpr int kZ = kHM > 256 ? kHM : 256;        // (re, im) pairs of the transform's buffer (>= 256: the harmonics' arrays live there)
   static constexpr int kMC = LOGM <= 9 ? kHM : -1;        // register-resident transform for M = 256 / 512, in place in LDS above
 };
 __device__ __forceinline__ int harm_is_peak(const float *x, int N, int n) {  // cHarmonics::isPeak, :369-390
@@ -855,19 +851,12 @@ __global__ void __launch_bounds__(HarmG<LOGM>::kWaves * 64) lld_gemaps_harm(LldP
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int NP = (Q.N + 3) & ~3;
   float *c_win = reinterpret_cast<float *>(smem_h);
-  float2 *c_twh = reinterpret_cast<float2 *>(c_win + NP);
-  float2 *c_twf = c_twh + kHM / 2;
+  float *c_tab = c_win + NP;                             // the reference-order transform's tables
   for (int i = threadIdx.x; i < Q.N; i += blockDim.x) c_win[i] = Q.window[i];
-  OouraTab OO = OouraTab{};                              // reference-order transform: its tables take the place of twh | twf
-  if (Q.oo.tw) OO = oo_stage_tables(Q.oo, reinterpret_cast<float *>(c_twh), threadIdx.x, blockDim.x);
-  else {
-    for (int i = threadIdx.x; i < kHM / 2; i += blockDim.x) c_twh[i] = Q.tw_half[i];
-    for (int i = threadIdx.x; i <= kHM / 2; i += blockDim.x) c_twf[i] = Q.tw_full[i];
-  }
+  const OouraTab OO = oo_stage_tables(Q.oo, c_tab, threadIdx.x, blockDim.x);
   __syncthreads();                                       // the only workgroup barrier
-  using Fft = WaveFft<9>;                                // kHM == 512, own-order A/B build: fused passes on (re, im) pairs, lld_fft.hpp
   constexpr int per_wave = 2 * HG::kZ + 2 * kHKP;
-  float2 *z = reinterpret_cast<float2 *>(reinterpret_cast<unsigned char *>(c_twh) + HG::kTwBytes) + (size_t)wave * (per_wave / 2);
+  float2 *z = reinterpret_cast<float2 *>(reinterpret_cast<unsigned char *>(c_tab) + HG::kTwBytes) + (size_t)wave * (per_wave / 2);
   float *mg = reinterpret_cast<float *>(z + HG::kZ);
   float *acf = mg + kHKP;
   int *hbin = reinterpret_cast<int *>(z);                // the harmonics' arrays live in the transform's buffer (dead after the ACF)
@@ -953,40 +942,20 @@ __global__ void __launch_bounds__(HarmG<LOGM>::kWaves * 64) lld_gemaps_harm(LldP
           const float a = x[c0] * c_win[c0], b = x[c1] * c_win[c1];
           return make_float2(v0 ? a : 0.0f, v1 ? b : 0.0f);
         };
-        if constexpr (LOGM == 9) {
-          if (OO.tw) oo_wave_forward<kMC>(z, OO, lane, load_pair);
-          else Fft::forward(z, c_twh, lane, load_pair);
-          for (int k = lane; k <= kHM; k += 64)
-            mg[k] = bin_magnitude(OO.tw ? oo_wave_bin<kMC>(z, OO, k) : fft_untangle<Fft>(z, k, c_twf), k == 0 || k == kHM);
-        } else {
-          oo_wave_forward<kMC>(z, OO, lane, load_pair);
-          for (int k = lane; k <= kHM; k += 64) mg[k] = bin_magnitude(oo_wave_bin<kMC>(z, OO, k), k == 0 || k == kHM);
-        }
+        oo_wave_forward<kMC>(z, OO, lane, load_pair);
+        for (int k = lane; k <= kHM; k += 64) mg[k] = bin_magnitude(oo_wave_bin<kMC>(z, OO, k), k == 0 || k == kHM);
       }
       WaveG::sync();
       GPHASE(0);   // load, window, FFT, magnitudes
       // computeAcf (:590-630): inverse real FFT of the squared magnitudes, |.| / nBins, lags 0 .. nBins-1
-      if (LOGM != 9 || OO.tw) {                          // rdft(N, -1) on the packed squares (harmonics.cpp:609-627)
-        oo_wave_inverse<kMC>(z, OO, lane, [&](int e) {
-          if (e == 0) { const float m0 = mg[0], m1 = mg[kHM]; return make_float2(m0 * m0, m1 * m1); }
-          const float m = mg[e];
-          return make_float2(m * m, 0.0f);
-        });
-        for (int k = lane; k <= kHM; k += 64) acf[k] = fabsf(oo_wave_inverse_out<kMC>(z, OO, k)) / (float)kHK;
-        WaveG::sync();
-      } else if constexpr (LOGM == 9) {
-        const int n = 2 * kHM;
-        Fft::forward(z, c_twh, lane, [&](int i) {        // the squared magnitudes, formed as they are asked for
-          const int n0 = 2 * i, n1 = 2 * i + 1;
-          const float m0 = mg[n0 <= kHM ? n0 : n - n0], m1 = mg[n1 <= kHM ? n1 : n - n1];
-          return make_float2(m0 * m0, m1 * m1);
-        });
-        for (int k = lane; k <= kHM; k += 64) {
-          const float a = 0.5f * fft_untangle<Fft>(z, k, c_twf).x;
-          acf[k] = fabsf(a) / (float)kHK;
-        }
-        WaveG::sync();
-      }
+      // rdft(N, -1) on the packed squares (harmonics.cpp:609-627)
+      oo_wave_inverse<kMC>(z, OO, lane, [&](int e) {
+        if (e == 0) { const float m0 = mg[0], m1 = mg[kHM]; return make_float2(m0 * m0, m1 * m1); }
+        const float m = mg[e];
+        return make_float2(m * m, 0.0f);
+      });
+      for (int k = lane; k <= kHM; k += 64) acf[k] = fabsf(oo_wave_inverse_out<kMC>(z, OO, k)) / (float)kHK;
+      WaveG::sync();
       GPHASE(1);   // ACF
       // HNR at the ACF peak closest to the F0 lag (freqToAcfBinLin :393-401, getClosestPeak :632-665, computeAcfHnr_dB :690-712)
       float hnr_db = 0.0f;
@@ -1327,12 +1296,12 @@ hipError_t launch_gemaps_formant_rows(const GemapsParams &G, hipStream_t s) {
 
 hipError_t launch_gemaps_frames(const LldParams &P, const GemapsParams &G, int n_runs, hipStream_t s) {
   if (n_runs <= 0) return hipSuccess;
-  if ((P.Nfft != 256 && P.Nfft != 512 && P.Nfft != 1024) || P.N > P.Nfft || P.n_mfcc > 16 || P.n_bands > 32) return hipErrorInvalidValue;   // 20 ms at 8 .. 48 kHz
-  const int M = P.Nfft / 2;
+  if ((P.Nfft != 256 && P.Nfft != 512 && P.Nfft != 1024) || P.K != P.Nfft / 2 + 1 || P.N > P.Nfft || P.n_mfcc > 16 || P.n_bands > 32) return hipErrorInvalidValue;   // 20 ms at 8 .. 48 kHz
+  if (!P.oo.tw) return hipErrorInvalidValue;              // every form runs the reference-order transform
   const int Kpad = (P.K + 3) & ~3;
-  const size_t lds = sizeof(float) * (size_t)(Kpad + 128 + 16 * 32 + oo_table_floats(P.oo) + 4 * ((2 * fft_pairs(M) > 2 * Kpad ? 2 * fft_pairs(M) : 2 * Kpad) + 3 * Kpad + 64 + 96));
+  const size_t lds = sizeof(float) * (size_t)(Kpad + 128 + 16 * 32 + oo_table_floats(P.oo) + 4 * (2 * Kpad + 3 * Kpad + 64 + 96));
   // sixteen lanes per frame for the shipped geometry (lld_gemaps_quad.hpp); SMILEHIP_GEMAPS_WAVE=1: the wave-per-frame form (A/B switch)
-  const bool quad_ok = P.oo.tw && P.N == 320 && P.H == 160 && P.Nfft == 512 && (P.pad_left == 0 || P.pad_left == 96) && P.K == 257 && P.n_bands == 26 && P.n_mfcc == 4 &&
+  const bool quad_ok = P.N == 320 && P.H == 160 && P.Nfft == 512 && (P.pad_left == 0 || P.pad_left == 96) && P.K == 257 && P.n_bands == 26 && P.n_mfcc == 4 &&
                        P.pcm && !P.pcm_f32 && P.total_frames < (int64_t(1) << 31) && G.sl_iL[0] >= 0 && G.sl_iR[0] <= 63 && G.sl_iL[1] >= 0 &&
                        G.sl_iR[1] <= 63 && G.ar_n1 >= 0 && G.ar_n1 <= G.ar_n2 && G.ar_n2 <= 257 && G.rng_lo >= 0 && !getenv("SMILEHIP_GEMAPS_WAVE");
   if (quad_ok) {
@@ -1361,14 +1330,13 @@ template <int LOGM>
 hipError_t launch_harm_g(const LldParams &P, const F0Params &Q, const GemapsParams &G, int64_t n_tiles, int max_blocks, hipStream_t s) {
   using HG = HarmG<LOGM>;
   const int NP = (Q.N + 3) & ~3;
-  if (sizeof(float) * (size_t)oo_table_floats(Q.oo) > HG::kTwBytes) return hipErrorInvalidValue;
-  if (LOGM != 9 && !Q.oo.tw) return hipErrorInvalidValue;             // the own-order A/B build exists for FFT 1024 only
+  if (!Q.oo.tw || sizeof(float) * (size_t)oo_table_floats(Q.oo) > HG::kTwBytes) return hipErrorInvalidValue;
   const size_t lds = sizeof(float) * (size_t)NP + HG::kTwBytes + sizeof(float) * HG::kWaves * (size_t)(2 * HG::kZ + 2 * HG::kHKP);
   const void *fn = reinterpret_cast<const void *>(&lld_gemaps_harm<LOGM>);
   hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
   unsigned grid = (unsigned)((n_tiles + HG::kWaves - 1) / HG::kWaves);
-  if (grid > (unsigned)(2 * max_blocks)) grid = (unsigned)(2 * max_blocks);   // M = 512: 78 KB of LDS per workgroup, two per CU
+  if (grid > (unsigned)(2 * max_blocks)) grid = (unsigned)(2 * max_blocks);   // M = 512: 74 KB of LDS per workgroup, two per CU
   // (the tile counter starts from zero at every launch, whatever an earlier launch left behind)
   if (G.harm_ctl && (e = hipMemsetAsync(G.harm_ctl, 0, 2 * sizeof(int32_t), s)) != hipSuccess) return e;
   SMILEHIP_KLAUNCH(lld_gemaps_harm<LOGM>, dim3(grid), dim3(HG::kWaves * 64), lds, s, P, Q, G);

@@ -16,7 +16,6 @@
 #include <vector>
 
 #include "lld_blocks.hpp"
-#include "lld_fft.hpp"
 #include "lld_ooura_quad.hpp"
 #include "lld_device.hpp"
 #include "lld_launch.hpp"
@@ -54,7 +53,6 @@ namespace smilehip {
 // (143 global loads per frame and wave before: the kernel waited on them)
 struct Is09Tbl {
   const float *window;
-  const float2 *tw_half, *tw_full;
   const float *mel_coef;
   const int32_t *mel_rng;
   const float *dct_rows;
@@ -62,8 +60,8 @@ struct Is09Tbl {
   const double2 *log_tab;                                  // kLogTab's copy in LDS (the quad form), else null
 };
 
-// LDS, workgroup form: xr[N] | yv[N] | re[M] | im[M] | mg[K+3] | sp[K+3] | acf[M] | cep[M] | lmel[32] | scr (4 doubles)
-// wave form: xr[N] | z[fft_pairs(M)] pairs | mg[K+3] (yv first) | sp[K+3] (yv, later cep) | acf[M] | lmel[32] | scr
+// LDS, workgroup form: xr[N] | yv[N] | z[M] pairs | mg[K+3] | sp[K+3] | acf[M] | cep[M] | lmel[32] | scr (4 doubles)
+// wave form: xr[N] | z[M] pairs | mg[K+3] (yv first) | sp[K+3] (yv, later cep) | acf[M] | lmel[32] | scr
 // MC: M = Nfft / 2 when known at compile time (256: the 25 ms / 16 kHz geometry of the shipped configs), 0 = run-time
 template <class G, int MC = 0>
 __device__ __forceinline__ void is09_frame_body(const LldParams &P, const Is09Params &Q, const Is09Tbl &T, int64_t row, float *smem) {
@@ -71,12 +69,9 @@ __device__ __forceinline__ void is09_frame_body(const LldParams &P, const Is09Pa
   const int Npad = (P.N + 3) & ~3;
   constexpr bool kWave = std::is_same<G, WaveG>::value;
   const int Kpad = MC > 0 ? ((MC + 1 + 3) & ~3) : ((P.K + 3) & ~3);
-  const int zpad = fft_pad(M);
   float *xr = smem;
-  float *re = kWave ? xr + Npad : xr + 2 * Npad;         // wave form: fft_pairs(M) (re, im) pairs, lld_fft.hpp
-  float *im = re + M;
-  float2 *z = reinterpret_cast<float2 *>(re);
-  float *mg = re + 2 * fft_pairs(M);
+  float2 *z = reinterpret_cast<float2 *>(kWave ? xr + Npad : xr + 2 * Npad);   // the transform's M (re, im) pairs
+  float *mg = reinterpret_cast<float *>(z + M);
   float *sp = mg + Kpad;
   float *yv = kWave ? mg : xr + Npad;                    // wave form: the windowed frame lives in mg | sp until the transform has read it
   float *acf = sp + Kpad;
@@ -95,8 +90,6 @@ __device__ __forceinline__ void is09_frame_body(const LldParams &P, const Is09Pa
   const int64_t t = row - P.frame_off[lo];
   const PcmIn x = pcm_in(P) + (P.samp_off[lo] + t * (int64_t)P.H);
   float *out = Q.raw16 + row * 16;
-  int logM = 0;
-  while ((1 << logM) < M) ++logM;
 
   IPHASE_DECL
   for (int n = G::tid(); n < P.N; n += G::size()) xr[n] = x[n];                      // R0 (or already done: float input)
@@ -127,37 +120,17 @@ __device__ __forceinline__ void is09_frame_body(const LldParams &P, const Is09Pa
     if (G::tid() == 0) out[0] = (float)sqrt(d / (float)P.N) * 1.0f + 0.0f;
   }
   IPHASE(2);   // pre-emphasis, window, RMS energy
-  // R4 forward real FFT
-  if (T.oo.tw) {                                         // the reference's operation order (lld_ooura.hpp / lld_ooura_wave.hpp)
-    const auto load_pair = [&](int i) {
-      const int n0 = 2 * i - P.pad_left, n1 = n0 + 1;
-      return make_float2((n0 >= 0 && n0 < P.N) ? yv[n0] : 0.0f, (n1 >= 0 && n1 < P.N) ? yv[n1] : 0.0f);
-    };
-    if constexpr (kWave) {
-      oo_wave_forward<MC>(z, T.oo, G::tid(), load_pair);
-      for (int k = G::tid(); k <= M; k += 64) mg[k] = bin_magnitude(oo_wave_bin<MC>(z, T.oo, k), k == 0 || k == M);  // R5
-    } else {
-      ooura_forward<G>(z, T.oo, load_pair);
-      for (int k = G::tid(); k <= M; k += G::size()) mg[k] = bin_magnitude(ooura_bin(z, T.oo, k), k == 0 || k == M);   // R5
-    }
-  } else if constexpr (kWave) {
-    wave_cfft(z, M, T.tw_half, G::tid(), [&](int i) {
-      const int n0 = 2 * i - P.pad_left, n1 = n0 + 1;
-      return make_float2((n0 >= 0 && n0 < P.N) ? yv[n0] : 0.0f, (n1 >= 0 && n1 < P.N) ? yv[n1] : 0.0f);
-    });
-    for (int k = G::tid(); k <= M; k += 64)
-      mg[k] = bin_magnitude(wave_untangle(z, M, zpad, k, T.tw_full), k == 0 || k == M);   // R5
+  // R4 forward real FFT: the reference's operation order (lld_ooura.hpp / lld_ooura_wave.hpp)
+  const auto load_pair = [&](int i) {
+    const int n0 = 2 * i - P.pad_left, n1 = n0 + 1;
+    return make_float2((n0 >= 0 && n0 < P.N) ? yv[n0] : 0.0f, (n1 >= 0 && n1 < P.N) ? yv[n1] : 0.0f);
+  };
+  if constexpr (kWave) {
+    oo_wave_forward<MC>(z, T.oo, G::tid(), load_pair);
+    for (int k = G::tid(); k <= M; k += 64) mg[k] = bin_magnitude(oo_wave_bin<MC>(z, T.oo, k), k == 0 || k == M);  // R5
   } else {
-    for (int i = G::tid(); i < M; i += G::size()) {
-      const int n0 = 2 * i - P.pad_left, n1 = n0 + 1;
-      const int r = (int)(__brev((unsigned)i) >> (32 - logM));
-      re[r] = (n0 >= 0 && n0 < P.N) ? yv[n0] : 0.0f;
-      im[r] = (n1 >= 0 && n1 < P.N) ? yv[n1] : 0.0f;
-    }
-    G::sync();
-    group_cfft_radix2<G>(re, im, M, T.tw_half);
-    for (int k = G::tid(); k <= M; k += G::size())
-      mg[k] = bin_magnitude(untangle_bin(re, im, M, k, T.tw_full), k == 0 || k == M);     // R5
+    ooura_forward<G>(z, T.oo, load_pair);
+    for (int k = G::tid(); k <= M; k += G::size()) mg[k] = bin_magnitude(ooura_bin(z, T.oo, k), k == 0 || k == M);   // R5
   }
   G::sync();
   IPHASE(3);   // forward transform + magnitudes
@@ -175,17 +148,15 @@ __device__ __forceinline__ void is09_frame_body(const LldParams &P, const Is09Pa
   // R9 cAcf (acf.cpp:249-349): ACF of the power spectrum, then the cepstrum instance
   for (int k = G::tid(); k <= M; k += G::size()) sp[k] = mg[k] * mg[k];                // usePower=1 (:252-259)
   G::sync();
-  if (T.oo.tw) { if constexpr (kWave) oo_wave_irfft_even<MC>(sp, z, T.oo, acf, (float)P.K, true, G::tid()); else oo_irfft_even<G>(sp, z, T.oo, acf, (float)P.K, true); }
-  else if constexpr (kWave) wave_irfft_even(sp, z, M, T.tw_half, T.tw_full, acf, (float)P.K, true, G::tid());
-  else group_irfft_even<G>(sp, re, im, M, logM, T.tw_half, T.tw_full, acf, (float)P.K, true);
+  if constexpr (kWave) oo_wave_irfft_even<MC>(sp, z, T.oo, acf, (float)P.K, true, G::tid());
+  else oo_irfft_even<G>(sp, z, T.oo, acf, (float)P.K, true);
   for (int k = G::tid(); k <= M; k += G::size()) {
     const float p = mg[k] * mg[k];
     sp[k] = (p > 0.0f) ? (float)log_d((double)p + 1.0) : 0.0f;                              // :288-305
   }
   G::sync();
-  if (T.oo.tw) { if constexpr (kWave) oo_wave_irfft_even<MC>(sp, z, T.oo, cep, (float)P.K, false, G::tid()); else oo_irfft_even<G>(sp, z, T.oo, cep, (float)P.K, false); }
-  else if constexpr (kWave) wave_irfft_even(sp, z, M, T.tw_half, T.tw_full, cep, (float)P.K, false, G::tid());
-  else group_irfft_even<G>(sp, re, im, M, logM, T.tw_half, T.tw_full, cep, (float)P.K, false);
+  if constexpr (kWave) oo_wave_irfft_even<MC>(sp, z, T.oo, cep, (float)P.K, false, G::tid());
+  else oo_irfft_even<G>(sp, z, T.oo, cep, (float)P.K, false);
 
   IPHASE(5);   // ACF + cepstrum: two inverse transforms, 257 double logs
   // R10 cPitchACF::processVector, per-frame part (pitchACF.cpp:137-192)
@@ -207,13 +178,13 @@ __device__ __forceinline__ void is09_frame_body(const LldParams &P, const Is09Pa
 // one workgroup per frame (any FFT size the LDS holds)
 __global__ void __launch_bounds__(256) lld_is09_frame(LldParams P, Is09Params Q) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  const Is09Tbl T = {P.window, P.tw_half, P.tw_full, P.mel_coef, P.mel_rng, P.dct_rows, P.oo};
+  const Is09Tbl T = {P.window, P.mel_coef, P.mel_rng, P.dct_rows, P.oo};
   is09_frame_body<BlockG>(P, Q, T, (int64_t)blockIdx.x, smem);
 }
 
-// floats of LDS the wave kernel's shared tables take: window | tw_half | tw_full | mel_coef | mel_rng | dct_rows
-__host__ __device__ inline int is09_table_floats(int N, int M, int K) {
-  return ((N + 3) & ~3) + M + (M + 4) + ((K + 3) & ~3) + 128 + 16 * 32;
+// floats of LDS the wave kernel's shared tables take: window | mel_coef | mel_rng | dct_rows
+__host__ __device__ inline int is09_table_floats(int N, int K) {
+  return ((N + 3) & ~3) + ((K + 3) & ~3) + 128 + 16 * 32;
 }
 
 // one WAVE per frame, four frames per workgroup, no barriers after the table staging
@@ -221,23 +192,19 @@ __global__ void __launch_bounds__(256) lld_is09_frame_wave(LldParams P, Is09Para
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int M = P.Nfft >> 1, Npad = (P.N + 3) & ~3, Kpad = (P.K + 3) & ~3;
   float *s_win = smem;
-  float2 *s_twh = reinterpret_cast<float2 *>(s_win + Npad);
-  float2 *s_twf = s_twh + M / 2;
-  float *s_coef = reinterpret_cast<float *>(s_twf + M / 2 + 2);
+  float *s_coef = s_win + Npad;
   int32_t *s_rng = reinterpret_cast<int32_t *>(s_coef + Kpad);
   float *s_dct = reinterpret_cast<float *>(s_rng + 128);
   for (int i = threadIdx.x; i < P.N; i += 256) s_win[i] = P.window[i];
-  for (int i = threadIdx.x; i < M / 2; i += 256) s_twh[i] = P.tw_half[i];
-  for (int i = threadIdx.x; i <= M / 2; i += 256) s_twf[i] = P.tw_full[i];
   for (int i = threadIdx.x; i < P.K; i += 256) s_coef[i] = P.mel_coef[i];
   for (int i = threadIdx.x; i < 4 * P.n_bands; i += 256) s_rng[i] = P.mel_rng[i];
   for (int i = threadIdx.x; i < P.n_mfcc * P.n_bands; i += 256) s_dct[i] = P.dct_rows[i];
-  const OouraTab s_oo = oo_stage_tables(P.oo, smem + is09_table_floats(P.N, M, P.K), threadIdx.x, 256);
+  const OouraTab s_oo = oo_stage_tables(P.oo, smem + is09_table_floats(P.N, P.K), threadIdx.x, 256);
   __syncthreads();                                       // the only workgroup barrier
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= P.total_frames) return;
-  const Is09Tbl T = {s_win, s_twh, s_twf, s_coef, s_rng, s_dct, s_oo};
-  float *wave_mem = smem + is09_table_floats(P.N, M, P.K) + oo_table_floats(P.oo) + (threadIdx.x >> 6) * wave_floats;
+  const Is09Tbl T = {s_win, s_coef, s_rng, s_dct, s_oo};
+  float *wave_mem = smem + is09_table_floats(P.N, P.K) + oo_table_floats(P.oo) + (threadIdx.x >> 6) * wave_floats;
   if (M == 256) is09_frame_body<WaveG, 256>(P, Q, T, row, wave_mem);
   else is09_frame_body<WaveG>(P, Q, T, row, wave_mem);
 }
@@ -539,9 +506,9 @@ __global__ void __launch_bounds__(kQuadWaves * 64) __attribute__((amdgpu_waves_p
   for (int i = threadIdx.x; i < P.K; i += kQuadWaves * 64) s_coef[i] = P.mel_coef[i];
   for (int i = threadIdx.x; i < 4 * P.n_bands; i += kQuadWaves * 64) s_rng[i] = P.mel_rng[i];
   for (int i = threadIdx.x; i < P.n_mfcc * P.n_bands; i += kQuadWaves * 64) s_dct[i] = P.dct_rows[i];
-  const OouraTab s_oo = oo_stage_tables<true>(P.oo, smem + is09_quad_table_floats(P.N), threadIdx.x, kQuadWaves * 64);   // (launch_is09: P.oo.tw != null)
+  const OouraTab s_oo = oo_stage_tables(P.oo, smem + is09_quad_table_floats(P.N), threadIdx.x, kQuadWaves * 64);
   __syncthreads();                                       // the only workgroup barrier
-  const Is09Tbl T = {s_win, nullptr, nullptr, s_coef, s_rng, s_dct, s_oo, s_log};
+  const Is09Tbl T = {s_win, s_coef, s_rng, s_dct, s_oo, s_log};
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = (threadIdx.x & 63) >> 4;
   float *fmem = smem + is09_quad_table_floats(P.N) + oo_table_floats(P.oo) + (wave * 4) * kQuadFrameFloats;
@@ -618,18 +585,19 @@ hipError_t launch_pitch_contour_step(const double *d_voicing, const int32_t *d_m
 
 hipError_t launch_is09(const LldParams &P, const Is09Params &Q, hipStream_t s) {
   if (P.total_frames <= 0) return hipSuccess;
+  if (!P.oo.tw) return hipErrorInvalidValue;               // every form runs the reference-order transform
   const int M = P.Nfft / 2;
   const int Npad = (P.N + 3) & ~3, Kpad = (P.K + 3) & ~3;
-  const size_t lds = sizeof(float) * (size_t)(2 * Npad + 2 * fft_pairs(M) + 2 * Kpad + 2 * M + 32) + 4 * sizeof(double) + 8 * sizeof(int);
+  const size_t lds = sizeof(float) * (size_t)(2 * Npad + 2 * M + 2 * Kpad + 2 * M + 32) + 4 * sizeof(double) + 8 * sizeof(int);
   // wave form: no yv, no cep of their own
-  const size_t lds_wave = sizeof(float) * (size_t)(Npad + 2 * fft_pairs(M) + 2 * Kpad + M + 32) + 4 * sizeof(double) + 8 * sizeof(int);
+  const size_t lds_wave = sizeof(float) * (size_t)(Npad + 2 * M + 2 * Kpad + M + 32) + 4 * sizeof(double) + 8 * sizeof(int);
   hipError_t e;
-  const size_t tbl_floats = (size_t)is09_table_floats(P.N, M, P.K) + (size_t)oo_table_floats(P.oo);
+  const size_t tbl_floats = (size_t)is09_table_floats(P.N, P.K) + (size_t)oo_table_floats(P.oo);
   const size_t quad_bytes = sizeof(float) * ((size_t)is09_quad_table_floats(P.N) + (size_t)oo_table_floats(P.oo) +
                                              (size_t)kQuadWaves * 4 * (size_t)kQuadFrameFloats);
   // SMILEHIP_IS09 (A/B switch): "wave" = one wave per frame, "block" = one workgroup per frame (the forms before the quad one)
   const char *form = getenv("SMILEHIP_IS09");
-  if (P.oo.tw && M == 256 && P.K == 257 && P.N <= 512 && P.frame_utt && P.n_bands <= 32 && P.n_mfcc <= 16 && quad_bytes <= 160 * 1024 && !form) {
+  if (M == 256 && P.K == 257 && P.N <= 512 && P.frame_utt && P.n_bands <= 32 && P.n_mfcc <= 16 && quad_bytes <= 160 * 1024 && !form) {
     const bool n25 = P.N <= 400;                           // 25 ms at 16 kHz: 25 samples per lane
     const bool full = P.N == 400 && P.pad_left == 0;       // ... exactly 400 and the padding behind the frame: the shipped files
     const void *qfn = full ? reinterpret_cast<const void *>(&lld_is09_frame_quad<25, true>)

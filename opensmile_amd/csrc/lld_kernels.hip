@@ -25,12 +25,11 @@ namespace smilehip {
 // ---------------------------------------------------------------------------
 // generic path: one 256-thread workgroup per frame
 // ---------------------------------------------------------------------------
-// LDS: re[M] | im[M] | p[K] | lmel[n_bands]   (M = Nfft/2)
+// LDS: z[M] (re, im) pairs | p[K] | lmel[n_bands]   (M = Nfft/2)
 __global__ void __launch_bounds__(256) lld_mfcc_generic(LldParams P) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int M = P.Nfft >> 1;
-  float *re = smem;
-  float *im = smem + M;
+  float2 *z = reinterpret_cast<float2 *>(smem);
   float *pw = smem + 2 * M;
   float *lmel = pw + P.K + 1;
 
@@ -45,10 +44,7 @@ __global__ void __launch_bounds__(256) lld_mfcc_generic(LldParams P) {
   const int64_t t = row - P.frame_off[u];
   const PcmIn x = pcm_in(P) + (P.samp_off[u] + t * (int64_t)P.H);
 
-  int logM = 0;
-  while ((1 << logM) < M) ++logM;
-
-  // R0..R3 + zero padding + bit-reversed load of z[i] = y[2i] + i*y[2i+1]
+  // R0..R3 + zero padding + load of z[i] = y[2i] + i*y[2i+1] (natural order)
   for (int i = threadIdx.x; i < M; i += blockDim.x) {
     float v[2];
 #pragma unroll
@@ -68,24 +64,16 @@ __global__ void __launch_bounds__(256) lld_mfcc_generic(LldParams P) {
       }
       v[h] = y;
     }
-    if (P.oo.tw) {                                         // reference-order transform: natural order, (re, im) pairs
-      reinterpret_cast<float2 *>(smem)[i] = make_float2(v[0], v[1]);
-    } else {
-      const int r = (int)(__brev((unsigned)i) >> (32 - logM));
-      re[r] = v[0];
-      im[r] = v[1];
-    }
+    z[i] = make_float2(v[0], v[1]);
   }
   __syncthreads();
 
-  // R4: the reference's rdft network (lld_ooura.hpp), or the radix-2 DIT of round 2 (SMILEHIP_FFT=radix2)
-  if (P.oo.tw) ooura_levels<BlockG, false>(reinterpret_cast<float2 *>(smem), P.oo);
-  else block_cfft_radix2(re, im, M, P.tw_half);
+  // R4: the reference's rdft network (lld_ooura.hpp)
+  ooura_levels<BlockG, false>(z, P.oo);
 
   // real-FFT untangle + R5 magnitude (+ R6's squaring, melspec.cpp:520-527)
   for (int k = threadIdx.x; k <= M; k += blockDim.x) {
-    const float2 X = P.oo.tw ? ooura_bin(reinterpret_cast<const float2 *>(smem), P.oo, k) : untangle_bin(re, im, M, k, P.tw_full);
-    const float mag = bin_magnitude(X, k == 0 || k == M);
+    const float mag = bin_magnitude(ooura_bin(z, P.oo, k), k == 0 || k == M);
     pw[k] = P.use_power ? mag * mag : mag;
   }
   __syncthreads();
@@ -285,6 +273,7 @@ __global__ void __launch_bounds__(64) lld_chain_short(ChainParams P) {
 // launchers
 // ---------------------------------------------------------------------------
 hipError_t launch_mfcc_generic(const LldParams &P, hipStream_t s) {
+  if (!P.oo.tw) return hipErrorInvalidValue;
   const int M = P.Nfft / 2;
   const size_t lds = sizeof(float) * (size_t)(2 * M + P.K + 1 + P.n_bands + 24);
   SMILEHIP_KLAUNCH(lld_mfcc_generic, dim3((unsigned)P.total_frames), dim3(256), lds, s, P);

@@ -38,9 +38,7 @@ struct LldParams {
   float k, one_minus_k, win_offset;
   const float *window;         // [N]
   // R4: complex FFT of length M = Nfft/2 + real untangle
-  const float2 *tw_half;       // [M/2]  e^{-2 pi i j / M}
-  const float2 *tw_full;       // [M/2+1] e^{-2 pi i k / Nfft}
-  OouraTab oo;                 // reference-order transform (lld_ooura.hpp); oo.tw == nullptr: the radix-2 order above
+  OouraTab oo;                 // reference-order transform (lld_ooura.hpp) of Nfft points; every launch that transforms requires oo.tw
   // R6
   const float *mel_coef;       // [K]
   const int32_t *mel_rng;      // [4*n_bands] rise_lo, rise_hi, fall_lo, fall_hi per band
@@ -112,9 +110,7 @@ struct CompareParams {
 struct F0Params {
   int32_t N, H, Nfft, K, pad_left;  // 60 ms framing @ 16 kHz: 960, 160, 1024, 513, 32
   const float *window;              // [N]
-  const float2 *tw_half;            // [M/2], M = Nfft/2
-  const float2 *tw_full;            // [M/2+1]
-  OouraTab oo;                      // reference-order transform (lld_ooura.hpp); oo.tw == nullptr: the radix-2 order above
+  OouraTab oo;                      // reference-order transform (lld_ooura.hpp) of Nfft points; every launch that transforms requires oo.tw
   // cSpecScale: natural cubic spline over the octave-scaled bin positions (smileUtilSpline.c:139-212); the
   // decomposition part of the tridiagonal sweep does not depend on the data and is precomputed:
   const double *sp_rec;             // [K x 4] per bin i: sigma_i, p_i = 1/(sigma_i*dec_{i-1}+2), dec_i = (sigma_i-1)*p_i, 0

@@ -17,8 +17,6 @@ hipError_t stage_window(const float *src, int64_t lds, float *dst, int64_t ldd, 
                         const float *w, float off, hipStream_t s);
 hipError_t stage_rfft_oo(const float *src, int64_t lds, float *dst, int64_t ldd, int64_t nF, int N, int Nfft,
                          int pad_left, const OouraTab &T, hipStream_t s);
-hipError_t stage_rfft(const float *src, int64_t lds, float *dst, int64_t ldd, int64_t nF, int N, int Nfft,
-                      int pad_left, const float2 *twh, const float2 *twf, hipStream_t s);
 hipError_t stage_fftmag(const float *src, int64_t lds, float *dst, int64_t ldd, int64_t nF, int Nfft, hipStream_t s);
 hipError_t stage_melspec(const float *src, int64_t lds, float *dst, int64_t ldd, int64_t nF, int K, int n_bands,
                          int use_power, const float *coef, const int32_t *rng, float scale, hipStream_t s);
@@ -55,8 +53,7 @@ hipError_t stage_mzcr(const float *src, int64_t lds, int N, int64_t nF, int flag
 hipError_t stage_valbased(const float *src, int64_t lds, int N, int64_t nF, int idx, float threshold, int invert, int allow_equal,
                           int zerovec, int remove_idx, float output_val, float *dst, int64_t ldd, int32_t *keep, hipStream_t s);
 hipError_t stage_acf(const float *src, int64_t lds, float *dst, int64_t ldd, int64_t nF, int K, int n_out, int use_power,
-                     int cepstrum, int norm_output, int abs_cepstrum, const float2 *tw_half, const float2 *tw_full,
-                     const OouraTab &OO, hipStream_t s);
+                     int cepstrum, int norm_output, int abs_cepstrum, const OouraTab &OO, hipStream_t s);
 hipError_t stage_pitchacf(const float *src, int64_t lds, int64_t nF, int n, double fs_sec, double max_pitch, double *voicing,
                           int32_t *max_idx, hipStream_t s);
 struct PlpConsts { float melfloor, compression, iir, fir[5]; };

@@ -32,18 +32,15 @@ __global__ void __launch_bounds__(256) k_zcr_count(const float *src, int64_t lds
   if (threadIdx.x == 0) out[blockIdx.x] = cnt;
 }
 
-// R9 cAcf::processVector, forward path (acf.cpp:249-349). LDS: sp[K+3] | re[M] | im[M] | res[M]
+// R9 cAcf::processVector, forward path (acf.cpp:249-349). LDS: sp[K+3] | z[M pairs] | res[M]
 __global__ void __launch_bounds__(256) k_acf(const float *src, int64_t lds, float *dst, int64_t ldd, int K, int n_out,
                                              int use_power, int cepstrum, int norm_output, int abs_cepstrum,
-                                             const float2 *tw_half, const float2 *tw_full, const OouraTab OO) {
+                                             const OouraTab OO) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int M = K - 1;
   float *sp = smem;
-  float *re = sp + ((K + 3) & ~3);
-  float *im = re + M;
-  float *res = im + M;
-  int logM = 0;
-  while ((1 << logM) < M) ++logM;
+  float2 *z = reinterpret_cast<float2 *>(sp + ((K + 3) & ~3));
+  float *res = reinterpret_cast<float *>(z + M);
   const float *m = src + (int64_t)blockIdx.x * lds;
   for (int k = threadIdx.x; k < K; k += blockDim.x) {
     float p = m[k];
@@ -53,8 +50,7 @@ __global__ void __launch_bounds__(256) k_acf(const float *src, int64_t lds, floa
     sp[k] = p;
   }
   __syncthreads();
-  if (OO.tw) oo_irfft_even<BlockG>(sp, reinterpret_cast<float2 *>(re), OO, res, norm_output ? (float)K : 1.0f, cepstrum ? abs_cepstrum != 0 : true);
-  else irfft_even(sp, re, im, M, logM, tw_half, tw_full, res, norm_output ? (float)K : 1.0f, cepstrum ? abs_cepstrum != 0 : true);
+  oo_irfft_even<BlockG>(sp, z, OO, res, norm_output ? (float)K : 1.0f, cepstrum ? abs_cepstrum != 0 : true);
   for (int k = threadIdx.x; k < n_out; k += blockDim.x) dst[(int64_t)blockIdx.x * ldd + k] = res[k];
 }
 
@@ -438,11 +434,11 @@ hipError_t stage_zcr_count(const float *src, int64_t lds, int64_t N, int64_t nF,
   return hipGetLastError();
 }
 hipError_t stage_acf(const float *src, int64_t lds, float *dst, int64_t ldd, int64_t nF, int K, int n_out, int use_power,
-                     int cepstrum, int norm_output, int abs_cepstrum, const float2 *tw_half, const float2 *tw_full,
-                     const OouraTab &OO, hipStream_t s) {
+                     int cepstrum, int norm_output, int abs_cepstrum, const OouraTab &OO, hipStream_t s) {
   if (nF <= 0) return hipSuccess;
+  if (!OO.tw) return hipErrorInvalidValue;
   const int M = K - 1;
-  if (OO.tw && (M == 256 || M == 512)) {
+  if (M == 256 || M == 512) {
     const size_t lb = 4 * sizeof(float) * (size_t)(((K + 3) & ~3) + 2 * M);
     hipLaunchKernelGGL(k_acf_oo_wave, dim3((unsigned)((nF + 3) / 4)), dim3(256), lb, s, src, lds, dst, ldd, nF, K, n_out, use_power,
                        cepstrum, norm_output, abs_cepstrum, OO);
@@ -452,7 +448,7 @@ hipError_t stage_acf(const float *src, int64_t lds, float *dst, int64_t ldd, int
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_acf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_acf, dim3((unsigned)nF), dim3(256), lds_bytes, s, src, lds, dst, ldd, K, n_out, use_power, cepstrum,
-                     norm_output, abs_cepstrum, tw_half, tw_full, OO);
+                     norm_output, abs_cepstrum, OO);
   return hipGetLastError();
 }
 hipError_t stage_pitchacf(const float *src, int64_t lds, int64_t nF, int n, double fs_sec, double max_pitch, double *voicing,

@@ -48,35 +48,7 @@ __global__ void k_window(const float *src, int64_t lds, float *dst, int64_t ldd,
 // cTransformFFT::processVector forward (transformFft.cpp:165-223), packed as
 // Ooura's rdft does (fftsg.c:103-135): a[0]=Re X0, a[1]=Re X[n/2],
 // a[2k]=Re Xk, a[2k+1]=+sum x sin(2 pi jk/n) = -Im of the standard DFT.
-__global__ void __launch_bounds__(256) k_rfft(const float *src, int64_t lds, float *dst, int64_t ldd, int N,
-                                              int Nfft, int pad_left, const float2 *tw_half,
-                                              const float2 *tw_full) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int M = Nfft >> 1;
-  float *re = smem, *im = smem + M;
-  int logM = 0;
-  while ((1 << logM) < M) ++logM;
-  const float *x = src + (int64_t)blockIdx.x * lds;
-  for (int i = threadIdx.x; i < M; i += blockDim.x) {
-    const int n0 = 2 * i - pad_left, n1 = n0 + 1;
-    const float v0 = (n0 >= 0 && n0 < N) ? x[n0] : 0.0f;
-    const float v1 = (n1 >= 0 && n1 < N) ? x[n1] : 0.0f;
-    const int r = (int)(__brev((unsigned)i) >> (32 - logM));
-    re[r] = v0;
-    im[r] = v1;
-  }
-  __syncthreads();
-  block_cfft_radix2(re, im, M, tw_half);
-  float *o = dst + (int64_t)blockIdx.x * ldd;
-  for (int k = threadIdx.x; k <= M; k += blockDim.x) {
-    const float2 X = untangle_bin(re, im, M, k, tw_full);
-    if (k == 0) o[0] = X.x;
-    else if (k == M) o[1] = X.x;
-    else { o[2 * k] = X.x; o[2 * k + 1] = -X.y; }
-  }
-}
-
-// The same operator on the reference-order transform (lld_ooura.hpp): bit-identical to rdft() of fftsg.c:322-363.
+// On the reference-order transform (lld_ooura.hpp): bit-identical to rdft() of fftsg.c:322-363.
 __global__ void __launch_bounds__(256) k_rfft_oo(const float *src, int64_t lds, float *dst, int64_t ldd, int N,
                                                  int pad_left, const OouraTab T) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -312,13 +284,6 @@ hipError_t stage_rfft_oo(const float *src, int64_t lds, float *dst, int64_t ldd,
   else
     hipLaunchKernelGGL(k_rfft_oo, dim3((unsigned)nF), dim3(256), sizeof(float) * (size_t)Nfft, s, src, lds, dst, ldd,
                        N, pad_left, T);
-  return hipGetLastError();
-}
-hipError_t stage_rfft(const float *src, int64_t lds, float *dst, int64_t ldd, int64_t nF, int N, int Nfft,
-                      int pad_left, const float2 *twh, const float2 *twf, hipStream_t s) {
-  if (nF > 0)
-    hipLaunchKernelGGL(k_rfft, dim3((unsigned)nF), dim3(256), sizeof(float) * (size_t)Nfft, s, src, lds, dst, ldd,
-                       N, Nfft, pad_left, twh, twf);
   return hipGetLastError();
 }
 hipError_t stage_fftmag(const float *src, int64_t lds, float *dst, int64_t ldd, int64_t nF, int Nfft,

@@ -131,6 +131,7 @@ extern "C" int smilehip_batch_create(smilehip_plan *plan, const int64_t *h_off, 
   *out = nullptr;
   if (!plan->ctx) return fail(SMILEHIP_ERR_NO_DEVICE, "host-only plan: no device attached (tables only)");
   if (plan->stage_mask != SMILEHIP_STAGE_ALL) return fail(SMILEHIP_ERR_INVALID, "single-component plan cannot run the fused chain");
+  if (int rt = require_transform(plan, "smilehip_batch_create")) return rt;
   HIP_TRY(hipSetDevice(plan->ctx->device));
   std::unique_ptr<smilehip_batch> b(new (std::nothrow) smilehip_batch());
   if (!b) return fail(SMILEHIP_ERR_NOMEM, "out of host memory");
@@ -213,9 +214,7 @@ static void fill_params(const smilehip_plan *p, const smilehip_batch *b, const i
   P.one_minus_k = 1 - p->cfg.preemph_k;     // (1-k) in float, vectorPreemphasis.cpp:94
   P.win_offset = (float)p->cfg.win_offset;
   P.window = p->d_window.p;
-  P.tw_half = p->d_tw_half.p;
-  P.tw_full = p->d_tw_full.p;
-  P.oo = p->fft_radix2 ? OouraTab{} : p->oo.tab();
+  P.oo = p->oo.tab();
   P.mel_coef = p->d_mel_coef.p;
   P.mel_rng = p->d_mel_rng.p;
   P.mel_scale = p->mel.scale;
@@ -471,9 +470,7 @@ void fill_f0_params(const smilehip_plan *plan, F0Params &Q) {
   Q.N = (int32_t)plan->geo.N; Q.H = (int32_t)plan->geo.H; Q.Nfft = (int32_t)plan->geo.Nfft; Q.K = (int32_t)plan->geo.K;
   Q.pad_left = plan->cfg.zero_pad_symmetric ? (int32_t)((plan->geo.Nfft - plan->geo.N) / 2) : 0;
   Q.window = plan->d_window.p;
-  Q.tw_half = plan->d_tw_half.p;
-  Q.tw_full = plan->d_tw_full.p;
-  Q.oo = plan->fft_radix2 ? OouraTab{} : plan->oo.tab();
+  Q.oo = plan->oo.tab();
   Q.sp_rec = plan->d_f0_rec.p; Q.sp_d1 = plan->d_f0_d1.p; Q.sp_d2 = plan->d_f0_d2.p;
   Q.ip_k = plan->d_f0_k.p; Q.ip_co = plan->d_f0_co.p; Q.audw = plan->d_f0_audw.p;
   Q.ip_rec = plan->d_f0_iprec.p; Q.ip_cnt = plan->d_f0_ipcnt.p; Q.sw_rec = plan->d_f0_swrec.p;

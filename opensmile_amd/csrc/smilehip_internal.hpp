@@ -141,9 +141,8 @@ struct smilehip_plan {
   DctTables dct;
   DevBuf<float> d_window, d_mel_coef, d_dct_rows, d_dct_gain;
   DevBuf<int32_t> d_mel_rng;
-  DevBuf<float2> d_tw_half, d_tw_full, d_tw256, d_tw512, d_fwin;
-  OouraDev oo;                // the reference-order transform of length Nfft (every chain but the fast MFCC kernel)
-  int fft_radix2 = 0;         // SMILEHIP_FFT=radix2: the round-2 transforms (own butterfly order), kept for A/B timing
+  DevBuf<float2> d_tw256, d_tw512, d_fwin;
+  OouraDev oo;                // the reference-order transform of length Nfft (every chain but the fast MFCC kernel); unbuilt for Nfft < 64
   DevBuf<float4> d_melw;
   DevBuf<uint32_t> d_melo;
   DevBuf<float> d_dct28;
@@ -201,6 +200,13 @@ struct smilehip_plan {
         if (e) (void)hipEventDestroy(e);
   }
 };
+// The reference-order transform is built for 64 .. 8192 points. A plan of a shorter frame windows, frames and pre-emphasises;
+// every entry point that would transform on it refuses by name.
+inline int require_transform(const smilehip_plan *p, const char *who) {
+  if (p->oo.d_tw.p) return SMILEHIP_OK;
+  return fail(SMILEHIP_ERR_INVALID, "%s: FFT length %lld: the reference-order transform is built for 64 .. 8192 points", who,
+              (long long)p->geo.Nfft);
+}
 
 struct smilehip_batch {
   smilehip_plan *plan = nullptr;

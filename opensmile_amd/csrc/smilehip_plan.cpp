@@ -217,16 +217,6 @@ static int build_tables(smilehip_plan *p, bool upload = true) {
   if (p->cfg.n_delta > 0 && (p->cfg.delta_win < 1 || p->cfg.delta_win > 4))
     return fail(SMILEHIP_ERR_INVALID, "delta_win must be 1..4");
 
-  const int64_t M = p->geo.Nfft / 2;
-  std::vector<float2> twh(static_cast<size_t>(M / 2 > 0 ? M / 2 : 1)), twf(static_cast<size_t>(M / 2 + 1));
-  for (int64_t j = 0; j < M / 2; ++j) {
-    const double a = -2.0 * M_PI * double(j) / double(M);
-    twh[j] = make_float2(float(std::cos(a)), float(std::sin(a)));
-  }
-  for (int64_t k = 0; k <= M / 2; ++k) {
-    const double a = -2.0 * M_PI * double(k) / double(p->geo.Nfft);
-    twf[k] = make_float2(float(std::cos(a)), float(std::sin(a)));
-  }
   std::vector<int32_t> rng((mask & SMILEHIP_STAGE_MEL) ? size_t(4) * p->mel.n_bands : 0);
   for (int b = 0; b < p->mel.n_bands && (mask & SMILEHIP_STAGE_MEL); ++b) {
     rng[4 * b + 0] = p->mel.rise_lo[b];
@@ -275,10 +265,8 @@ static int build_tables(smilehip_plan *p, bool upload = true) {
   if ((rc = p->d_mel_rng.upload(rng))) return rc;
   if ((rc = p->d_dct_rows.upload(p->dct.cos_rows))) return rc;
   if ((rc = p->d_dct_gain.upload(p->dct.gain))) return rc;
-  if ((rc = p->d_tw_half.upload(twh))) return rc;
-  if ((rc = p->d_tw_full.upload(twf))) return rc;
-  if (p->geo.Nfft >= 64 && p->geo.Nfft <= 8192) { if ((rc = p->oo.build((int)p->geo.Nfft, true))) return rc; }
-  else p->fft_radix2 = 1;     // lengths the reference-order network is not built for: own radix-2 order (no BASELINE config)
+  // (shorter frames: a plan that windows, frames or pre-emphasises only; what would transform refuses it, require_transform)
+  if (p->geo.Nfft >= 64 && (rc = p->oo.build((int)p->geo.Nfft, true))) return rc;
   if (is_plp && ((rc = p->d_plp_eql.upload(plp_eql)) || (rc = p->d_plp_cos.upload(p->h_plp_cos)) || (rc = p->d_plp_sin.upload(plp_sin))))
     return rc;
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE_F0 &&
@@ -482,7 +470,6 @@ extern "C" int smilehip_plan_create(smilehip_context *ctx, const smilehip_lld_co
   p->cfg = *cfg;
   const char *fg = getenv("SMILEHIP_FORCE_GENERIC");
   p->force_generic = (fg && fg[0] == '1') ? 1 : 0;
-  { const char *ff = std::getenv("SMILEHIP_FFT"); p->fft_radix2 = (ff && std::strcmp(ff, "radix2") == 0) ? 1 : 0; }
   int rc = build_tables(p);
   if (rc == SMILEHIP_OK && cfg->chain_kind == SMILEHIP_CHAIN_COMPARE) {      // the 60 ms sub-chain
     smilehip_lld_config c60;

@@ -245,12 +245,10 @@ extern "C" int smilehip_rfft_frames(smilehip_plan *p, const float *d_src, int64_
   if (!p->ctx) return fail(SMILEHIP_ERR_NO_DEVICE, "host-only plan: no device attached");
   int rc = check_frames(d_src, d_dst, ld_src, ld_dst, n_frames, p->geo.N, p->geo.Nfft, "smilehip_rfft_frames");
   if (rc) return rc;
+  if ((rc = require_transform(p, "smilehip_rfft_frames"))) return rc;
   const int pad = p->cfg.zero_pad_symmetric ? (int)((p->geo.Nfft - p->geo.N) / 2) : 0;
-  if (!p->fft_radix2)
-    STAGE_RET(stage_rfft_oo(d_src, ld_src, d_dst, ld_dst, n_frames, (int)p->geo.N, (int)p->geo.Nfft, pad, p->oo.tab(),
-                            (hipStream_t)stream), "rfft");
-  STAGE_RET(stage_rfft(d_src, ld_src, d_dst, ld_dst, n_frames, (int)p->geo.N, (int)p->geo.Nfft, pad, p->d_tw_half.p,
-                       p->d_tw_full.p, (hipStream_t)stream), "rfft");
+  STAGE_RET(stage_rfft_oo(d_src, ld_src, d_dst, ld_dst, n_frames, (int)p->geo.N, (int)p->geo.Nfft, pad, p->oo.tab(),
+                          (hipStream_t)stream), "rfft");
 }
 
 extern "C" int smilehip_sumsq_frames(smilehip_context *ctx, const float *d_src, int64_t ld_src, int64_t N, int64_t n_frames,
@@ -289,8 +287,9 @@ extern "C" int smilehip_acf_frames(smilehip_plan *p, const float *d_src, int64_t
                 (long long)n_out, (long long)(p->geo.Nfft / 2));
   int rc = check_frames(d_src, d_dst, ld_src, ld_dst, n_frames, p->geo.K, n_out, "smilehip_acf_frames");
   if (rc) return rc;
+  if ((rc = require_transform(p, "smilehip_acf_frames"))) return rc;
   STAGE_RET(stage_acf(d_src, ld_src, d_dst, ld_dst, n_frames, (int)p->geo.K, (int)n_out, use_power, cepstrum, norm_output,
-                      abs_cepstrum, p->d_tw_half.p, p->d_tw_full.p, p->fft_radix2 ? OouraTab{} : p->oo.tab(), (hipStream_t)stream), "acf");
+                      abs_cepstrum, p->oo.tab(), (hipStream_t)stream), "acf");
 }
 
 extern "C" int smilehip_pitchacf_frames(smilehip_context *ctx, const float *d_src, int64_t ld_src, int64_t n, int64_t n_frames,
@@ -428,6 +427,7 @@ extern "C" int smilehip_fftmag_frames(smilehip_plan *p, const float *d_src, int6
   if (!p->ctx) return fail(SMILEHIP_ERR_NO_DEVICE, "host-only plan: no device attached");
   int rc = check_frames(d_src, d_dst, ld_src, ld_dst, n_frames, p->geo.Nfft, p->geo.K, "smilehip_fftmag_frames");
   if (rc) return rc;
+  if ((rc = require_transform(p, "smilehip_fftmag_frames"))) return rc;
   STAGE_RET(stage_fftmag(d_src, ld_src, d_dst, ld_dst, n_frames, (int)p->geo.Nfft, (hipStream_t)stream), "fftmag");
 }
 
@@ -437,7 +437,7 @@ extern "C" int smilehip_irfft_frames(smilehip_plan *p, const float *d_src, int64
   if (!p->ctx) return fail(SMILEHIP_ERR_NO_DEVICE, "host-only plan: no device attached");
   int rc = check_frames(d_src, d_dst, ld_src, ld_dst, n_frames, p->geo.Nfft, p->geo.Nfft, "smilehip_irfft_frames");
   if (rc) return rc;
-  if (!p->oo.d_tw.p) return fail(SMILEHIP_ERR_INVALID, "smilehip_irfft_frames: the reference-order transform is built for 64 .. 8192 points");
+  if ((rc = require_transform(p, "smilehip_irfft_frames"))) return rc;
   STAGE_RET(stage_irfft_oo(d_src, ld_src, d_dst, ld_dst, n_frames, (int)p->geo.Nfft, p->oo.tab(), (hipStream_t)stream), "irfft");
 }
 

@@ -88,9 +88,9 @@ def test_window_chain_sma_delta_bit_exact(hip, oracle):
 
 
 def test_is09_other_sample_rates_wave_equals_workgroup_kernel():
-    """Geometries other than 16 kHz / 25 ms: 8 kHz (N = 200, M = 128: the wave kernel's run-time-M path with the generic pair
-    transform), 32 kHz (N = 800, M = 512: the fused transform) -- the wave-per-frame kernel against the one-workgroup-per-frame
-    kernel (SMILEHIP_IS09=block), which runs the in-place radix-2 transform and the workgroup reductions: same values within
+    """Geometries other than 16 kHz / 25 ms: 8 kHz (N = 200, M = 128: the wave kernel's run-time-M path with the transform in
+    place in LDS), 32 kHz (N = 800, M = 512: the register form) -- the wave-per-frame kernel against the one-workgroup-per-frame
+    kernel (SMILEHIP_IS09=block), which runs the transform in place in LDS and the workgroup reductions: same values within
     the chain's tolerance (the energy sums use different trees)."""
     import os
     from opensmile_amd import capi, synth
