@@ -12,6 +12,10 @@
 //   load    lane (g, j) loads from global memory exactly the sample pairs it
 //           transforms -- pair n = j + 16 m of frame t, m < MP -- one pass ahead
 //           (the 2.5x overlap of the frames is served by L1/L2; no LDS stage).
+//           The loads are TYPED buffer loads (round 9): the buffer unit hands the int16 samples over
+//           as floats, so the conversion costs no vector instruction (the PLP chain and the
+//           delta-fused MP = 16 instances keep integer loads and convert on the vector ALU:
+//           typed_loads() below).
 //           Conversion (R0, scale folded into the window table), pre-emphasis
 //           (R2, the reference's two roundings; the previous sample comes from
 //           the neighbour lane by DPP) and window (R3) happen in registers:
@@ -185,8 +189,9 @@ __device__ __forceinline__ float dpp_f(float v) {
 }  // namespace
 
 // The next pass's samples of one lane: pair n = j + 16 m of frame tp + g for m < MP. ALIGNED (the buffer is 4-byte
-// aligned and every utterance starts at an even sample, checked on the host): one dword per pair; otherwise two
-// sign-extending 16-bit loads. `base` = first sample of the pass's first frame minus the left padding; the per-lane byte
+// aligned and every utterance starts at an even sample, checked on the host): one load per pair; otherwise two
+// 16-bit loads (typed, i.e. converted to float by the buffer unit, or integer: typed_loads() below). `base` = first
+// sample of the pass's first frame minus the left padding; the per-lane byte
 // offset (g H + 2 j) * 2 is ONE VGPR and load m adds the immediate 64 m -- everything else is wave-uniform and lives in
 // SGPRs: nothing to spill (a spill reload would put an s_waitcnt vmcnt(0) behind the loads and wait out the whole memory
 // latency in every pass). Samples outside a frame meet a zero of the window table and every stored frame lies inside
@@ -257,9 +262,51 @@ constexpr bool kMirrorAtUse = false;          // (the crossbar form has no mirro
 #else
 constexpr bool kMirrorAtUse = kMirrorOperand;
 #endif
-template <int MP, bool ALIGNED, bool PREEMPH>
+// (round 9) The conversion int16 -> float by the buffer unit: a TYPED buffer load returns (float)x exactly. Aligned
+// input: one tbuffer_load_format_xy [16_16, SSCALED] per pair in place of a dword load and two conversions; unaligned
+// input: two tbuffer_load_format_x [16, SSCALED] in place of two 16-bit loads and two conversions. The number of
+// vector-memory instructions is the parent's, 2 MP vector instructions per pass are gone, and every later operation
+// sees the same operands: the bits cannot change (tests/test_gpu_mfcc512_typed_loads.py). The loads are reached
+// through the LLVM intrinsic by name -- no inline assembly: the compiler keeps its own s_waitcnt vmcnt bookkeeping and
+// folds 64 m into the immediate offset.
+// The samples are the window stage's own operands now, so they have to DIE there: the pass loop sets them to zero on
+// the path that issues no further prefetch (the wave's last pass). While they stayed alive on that path the
+// pre-emphasis products could not overwrite their addend (v_fma_f32, 64-bit, instead of v_fmac) and 2 MP registers
+// stayed occupied through both transforms.
+// -DSMILEHIP_MFCC512_CVT_ON_VALU restores the parent's form everywhere (A/B aid). Census, A/B tables and replay floor:
+// DESIGN.md 4.1, profiles/r09_ab.txt.
+#if defined(SMILEHIP_MFCC512_CVT_ON_VALU) || defined(SMILEHIP_MFCC512_B16_SAMPLES) || defined(SMILEHIP_MFCC512_GLOBAL_LOADS)
+constexpr bool kTypedLoads = false;
+#else
+constexpr bool kTypedLoads = true;
+#endif
+// Per instance: the two floats per pair live from the prefetch issue to the window (aligned input: 2 MP registers
+// where the dword form holds MP), and an instance whose scratch would grow against the dword form keeps that form:
+// the PLP chain (every instance of it stands at 128 VGPRs already) and the delta-fused instances with MP = 16. With
+// this rule no instance has more scratch than its parent, all have <= 128 VGPRs and occupancy 4
+// (tools/dev/kernel_resources.sh lld_mfcc512.hip).
+template <int MP, bool PLP, bool DELTA>
+constexpr bool typed_loads() {
+  return kTypedLoads && !PLP && !(MP == 16 && DELTA);
+}
+typedef float float2v __attribute__((ext_vector_type(2)));
+__device__ float2v tbuffer_load_xy(__amdgpu_buffer_rsrc_t rsrc, int voffset, int soffset, int format, int aux)
+    __asm("llvm.amdgcn.raw.ptr.tbuffer.load.v2f32");
+__device__ float tbuffer_load_x(__amdgpu_buffer_rsrc_t rsrc, int voffset, int soffset, int format, int aux)
+    __asm("llvm.amdgcn.raw.ptr.tbuffer.load.f32");
+// gfx9 MTBUF encoding: dfmt | nfmt << 4 with dfmt BUF_DATA_FORMAT_16_16 = 5, BUF_DATA_FORMAT_16 = 2 and
+// nfmt BUF_NUM_FORMAT_SSCALED = 3
+constexpr int kFmt16x2Sscaled = 5 | (3 << 4);
+constexpr int kFmt16Sscaled = 2 | (3 << 4);
+// word 3 of the descriptor: DATA_FORMAT_32 (bits 18:15; what the untyped loads always had) and, for the typed loads,
+// DST_SEL_X = 4 (the element's first component), DST_SEL_Y = 5 (its second) in bits 5:0 -- a selector of 0 returns the
+// constant zero; untyped loads ignore the field
+constexpr int kRsrcWord3 = 0x00020000, kRsrcWord3Typed = 0x00020000 | 4 | (5 << 3);
+
+// TYPED: v holds the two floats of pair m (their bits) in v[2 m], v[2 m + 1]
+template <int MP, bool ALIGNED, bool PREEMPH, bool TYPED>
 struct FrameRegs {
-  uint32_t v[ALIGNED && !kB16Samples ? MP : 2 * MP];
+  uint32_t v[ALIGNED && !kB16Samples && !TYPED ? MP : 2 * MP];
   uint32_t p[PREEMPH && kPredLoads ? MP : 1];        // x[2n - 1], sign-extended
 };
 
@@ -269,14 +316,15 @@ struct FrameRegs {
 // replaces the clamped-address branch: a read behind the end of the buffer (or in front of it: the offset wraps to a huge unsigned
 // value) returns zero, which is as good as the clamped sample -- such samples meet a zero of the window table or belong to a frame
 // that is not stored. -DSMILEHIP_MFCC512_GLOBAL_LOADS builds the round-5 form (A/B aid).
-template <int MP, bool ALIGNED, bool PREEMPH>
+template <int MP, bool ALIGNED, bool PREEMPH, bool TYPED>
 __device__ __forceinline__ void pcm_prefetch(const int16_t *pcm, int64_t pcm_total, int64_t base, int H, int lane,
-                                             FrameRegs<MP, ALIGNED, PREEMPH> &R) {
+                                             FrameRegs<MP, ALIGNED, PREEMPH, TYPED> &R) {
 #ifndef SMILEHIP_MFCC512_GLOBAL_LOADS
   const int64_t b0 = base < 0 ? 0 : base;                // (negative only for the buffer's first frames under symmetric zero padding)
   int64_t left = (pcm_total - b0) * 2;                   // bytes behind the descriptor's base
   left = left < 0 ? 0 : (left > 0xfffffffcLL ? 0xfffffffcLL : left);
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<int16_t *>(pcm + b0), 0, (int)(uint32_t)left, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<int16_t *>(pcm + b0), 0, (int)(uint32_t)left,
+                                                                        TYPED ? kRsrcWord3Typed : kRsrcWord3);
   uint32_t lo = ((uint32_t)(lane >> 4) * (uint32_t)H + 2u * (uint32_t)(lane & 15)) * 2u + (uint32_t)((base - b0) * 2);
   asm volatile("" : "+v"(lo));                           // opaque per call: no hoisted per-m offset registers
   uint32_t lo_p = lo - 2u;                               // the predecessor of pair 0 (m = 0 only: the immediate offset is unsigned)
@@ -285,7 +333,14 @@ __device__ __forceinline__ void pcm_prefetch(const int16_t *pcm, int64_t pcm_tot
   for (int m = 0; m < MP; ++m) {
     if (PREEMPH && kPredLoads)
       R.p[m] = (uint32_t)(int32_t)(int16_t)__builtin_amdgcn_raw_buffer_load_b16(rsrc, m == 0 ? (int)lo_p : (int)lo + 64 * m - 2, 0, 0);
-    if (ALIGNED && !kB16Samples) {
+    if constexpr (TYPED && ALIGNED) {
+      const float2v f = tbuffer_load_xy(rsrc, (int)lo + 64 * m, 0, kFmt16x2Sscaled, 0);
+      R.v[2 * m] = __float_as_uint(f.x);
+      R.v[2 * m + 1] = __float_as_uint(f.y);
+    } else if constexpr (TYPED) {
+      R.v[2 * m] = __float_as_uint(tbuffer_load_x(rsrc, (int)lo + 64 * m, 0, kFmt16Sscaled, 0));
+      R.v[2 * m + 1] = __float_as_uint(tbuffer_load_x(rsrc, (int)lo + 64 * m + 2, 0, kFmt16Sscaled, 0));
+    } else if (ALIGNED && !kB16Samples) {
       R.v[m] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)lo + 64 * m, 0, 0);
     } else {
       R.v[2 * m] = (uint32_t)(int32_t)(int16_t)__builtin_amdgcn_raw_buffer_load_b16(rsrc, (int)lo + 64 * m, 0, 0);
@@ -454,8 +509,9 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
   int64_t nxt_samp0 = cur_samp0;
   if (has_next) nxt_samp0 = recs[tile + tile_stride].samp0;
   int tp = 0;                                          // first frame of the pass, relative to the tile
-  FrameRegs<MP, ALIGNED, PREEMPH> R;
-  pcm_prefetch<MP, ALIGNED, PREEMPH>(P.pcm, P.pcm_total, cur_samp0 - P.pad_left, P.H, lane, R);
+  constexpr bool TYPED = typed_loads<MP, PLP, DELTA>();
+  FrameRegs<MP, ALIGNED, PREEMPH, TYPED> R;
+  pcm_prefetch<MP, ALIGNED, PREEMPH, TYPED>(P.pcm, P.pcm_total, cur_samp0 - P.pad_left, P.H, lane, R);
   unsigned char *pend_row = nullptr;                   // deferred store of the previous pass (wave-uniform row base)
   float pend_val = 0.0f;
   bool pend_live = false;
@@ -536,7 +592,10 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
       for (int m = 0; m < 16; ++m) {
         if (m < MP) {
           float a, b;
-          if constexpr (ALIGNED && !kB16Samples) {
+          if constexpr (TYPED) {                   // converted by the buffer unit
+            a = __uint_as_float(R.v[2 * m]);
+            b = __uint_as_float(R.v[2 * m + 1]);
+          } else if constexpr (ALIGNED && !kB16Samples) {
             a = (float)(int16_t)(R.v[m] & 0xffffu);
             b = (float)(int16_t)(R.v[m] >> 16);
           } else {
@@ -743,7 +802,13 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
     const bool more = !advance || has_next;
     if (advance) ntp = 0;
     if (more)
-      pcm_prefetch<MP, ALIGNED, PREEMPH>(P.pcm, P.pcm_total, (advance ? nxt_samp0 : cur_samp0) + (int64_t)ntp * P.H - P.pad_left, P.H, lane, R);
+      pcm_prefetch<MP, ALIGNED, PREEMPH, TYPED>(P.pcm, P.pcm_total, (advance ? nxt_samp0 : cur_samp0) + (int64_t)ntp * P.H - P.pad_left, P.H, lane, R);
+    else if constexpr (TYPED) {
+      // the wave's last pass (it leaves the loop below): the samples must not stay alive up to here on THIS path
+      // either (see kTypedLoads). Not on the steady path.
+#pragma unroll
+      for (int m = 0; m < 2 * MP; ++m) R.v[m] = 0u;
+    }
 
     PHASE(7);                                   // prefetch issue
     // ------------------------------------------------------------ mel (R6)

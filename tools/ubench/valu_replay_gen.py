@@ -35,7 +35,7 @@ SRC = os.path.join(ROOT, "opensmile_amd", "csrc", "lld_mfcc512.hip")
 KERNEL = "_ZN8smilehip11lld_mfcc512ILi13ELb1ELb1ELb1ELb0ELi6ELb1EEEvNS_9LldParamsENS_13Fast512TablesE"
 FLAGS = ("--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-slp-vectorize -Xclang -target-feature "
          "-Xclang -load-store-opt --cuda-device-only -gline-tables-only -S").split()
-DFT_LINES = set(range(99, 110)) | set(range(118, 123)) | set(range(140, 160))   # dft4, cmul_ns, dft16_first / _twiddles / _last of lld_mfcc512.hip (innermost inlined location); cmul (111-115) is left
+DFT_LINES = set(range(103, 114)) | set(range(122, 127)) | set(range(144, 164))   # dft4, cmul_ns, dft16_first / _twiddles / _last of lld_mfcc512.hip (innermost inlined location); cmul (115-119) is left
 # in: the line tables cannot tell the 4 cmul inside a dft16 from the 15 twiddle products between the stages, which stay on the vector ALU
 
 
@@ -89,6 +89,9 @@ def main():
         ls = blocks[b]
         # delta_exact: the block with the division sequence (v_div_scale) and ds_bpermute; the clamped prefetch: v_min_i32 chains
         if n_valu(ls) > 60 and (has(ls, r"v_div_scale") or (has(ls, r"v_min_i32") and not has(ls, r"v_fmac"))):
+            skipped.append((b, n_valu(ls)))
+        # the wave's last pass instead of the prefetch (typed loads): nothing but the sample registers set to zero
+        elif n_valu(ls) >= 8 and all(re.match(r"\s*v_mov_b32_e32 v\d+, 0\s*$", l) for l in ls if l.strip().startswith("v_")):
             skipped.append((b, n_valu(ls)))
     skip = {b for b, _ in skipped}
     # ---- the stream: (instruction text, source line, is_dft)
