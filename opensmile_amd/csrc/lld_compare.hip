@@ -24,6 +24,7 @@
 #include "lld_device.hpp"
 #include "lld_launch.hpp"
 #include "lld_params.hpp"
+#include "phase_timing.hpp"
 
 namespace smilehip {
 
@@ -32,26 +33,8 @@ constexpr int kRun = kRunFramesMin;   // frames per run when the caller names no
 
 }  // namespace
 
-// Development instrumentation (-DSMILEHIP_PHASE_TIMING in a private build, tools/ubench): s_memtime at the phase
-// boundaries of the frame loop, summed over all workgroups by thread 0. Not compiled into the product.
-#ifdef SMILEHIP_PHASE_TIMING
-__device__ unsigned long long g_phase_cmp[16];
-#define PHASE_DECL unsigned long long ph_acc[8] = {0}; unsigned long long ph_last = __builtin_amdgcn_s_memtime();
-#define PHASE(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); ph_acc[i] += t_ - ph_last; ph_last = t_; } while (0)
-#define PHASE_FLUSH do { if ((threadIdx.x & 63) == 0) for (int i_ = 0; i_ < 8; ++i_) atomicAdd(&g_phase_cmp[i_], ph_acc[i_]); } while (0)
-extern "C" int smilehip_debug_phase_cmp(unsigned long long *out16, int reset) {
-  if (out16 && hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_phase_cmp), sizeof(unsigned long long) * 16) != hipSuccess) return -1;
-  if (reset) {
-    unsigned long long z[16] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_phase_cmp), z, sizeof(z)) != hipSuccess) return -1;
-  }
-  return 0;
-}
-#else
-#define PHASE_DECL
-#define PHASE(i)
-#define PHASE_FLUSH
-#endif
+// the phases of the frame loops (phase_timing.hpp; tools/ubench/phase_timing_cmp.py)
+SMILEHIP_PHASE_COUNTERS(g_phase_cmp, 16, smilehip_debug_phase_cmp)
 
 // LDS: yv[N] | z[M] pairs | mg[K] | pw[K] | prev[K] | mel[32] | aud[32] | lmel[32] | double red[64] | double cum[256] | peaks
 // Nfft = 512 only: thread i of the 256 owns bin i+1 in the descriptor section.
@@ -100,7 +83,7 @@ __global__ void __launch_bounds__(256) lld_compare_frame(LldParams P, ComparePar
   SC.log_tab = nullptr;
   const int run_len = Q.run_frames > 0 ? Q.run_frames : kRun;
   const int t_last = (t0 + run_len < T20) ? t0 + run_len : T20;
-  PHASE_DECL
+  PhaseTimer<8> PH;
 
   // frames t0-1 (magnitudes only, for the flux) .. t_last-1
   for (int t = (t0 > 0 ? t0 - 1 : 0); t < t_last; ++t) {
@@ -118,16 +101,16 @@ __global__ void __launch_bounds__(256) lld_compare_frame(LldParams P, ComparePar
       z[i] = make_float2(v0, v1);
     }
     __syncthreads();
-    PHASE(0);   // load + window
+    PH(0);   // load + window
     ooura_levels<BlockG, false>(z, P.oo);               // the reference's rdft network
-    PHASE(1);   // FFT
+    PH(1);   // FFT
     for (int k = threadIdx.x; k <= M; k += blockDim.x) {
       const float m = bin_magnitude(ooura_bin(z, P.oo, k), k == 0 || k == M);
       mg[k] = m;
       pw[k] = m * m;                                    // squareInput (spectral.cpp:676-683) == melspec usePower
     }
     __syncthreads();
-    PHASE(2);   // magnitudes
+    PH(2);   // magnitudes
     if (warm) {
       for (int k = threadIdx.x; k < K; k += blockDim.x) prev[k] = mg[k];
       __syncthreads();
@@ -150,7 +133,7 @@ __global__ void __launch_bounds__(256) lld_compare_frame(LldParams P, ComparePar
       const float d = seq_sum_f32(aud, P.n_bands);
       rawA[0] = d / (float)P.n_bands;
     }
-    PHASE(3);   // mel, auditory spectrum, MFCC
+    PH(3);   // mel, auditory spectrum, MFCC
     // R12: energy of the raw 20 ms frame (energy.cpp:152-168) and ZCR of the 60 ms frame (mzcr.cpp:117-124)
     {
       const int tid = threadIdx.x;
@@ -167,14 +150,14 @@ __global__ void __launch_bounds__(256) lld_compare_frame(LldParams P, ComparePar
         if (t < T60) rawA[3] = (float)v0[1] / (float)Q.N60;
       }
     }
-    PHASE(4);   // energy + ZCR
+    PH(4);   // energy + ZCR
     // R11: the 15 spectral descriptors, block-parallel (lld_blocks_compare.hpp)
     spectral_frame(mg, pw, prev, t == 0, SC, K, red, cum, pk_val, pk_has, rawB + 26);
     for (int k = threadIdx.x; k < K; k += blockDim.x) prev[k] = mg[k];
     __syncthreads();
-    PHASE(5);   // spectral descriptors
+    PH(5);   // spectral descriptors
   }
-  PHASE_FLUSH;
+  PH.flush(g_phase_cmp);
 }
 
 // The same frame pipeline with ONE wave per frame and four independent runs per workgroup: no workgroup barriers after
@@ -243,7 +226,7 @@ __device__ __forceinline__ void compare_frame_wave_body(const LldParams &P, cons
   const int run_len = Q.run_frames > 0 ? Q.run_frames : kRun;
   const int t_last = (t0 + run_len < T20) ? t0 + run_len : T20;
   const int lane_in = lane;
-  PHASE_DECL
+  PhaseTimer<8> PH;
   const int t_begin = t0 > 0 ? t0 - 1 : 0;
   int rbase = 0;
   int zc_count = 0, zc_front = 0;                        // this lane's crossings inside the window / inside its first hop
@@ -275,21 +258,21 @@ __device__ __forceinline__ void compare_frame_wave_body(const LldParams &P, cons
     }
     const auto R = [&](int n) { int k = n + rbase; if (k >= Gq.N60) k -= Gq.N60; return raw[k]; };
     WaveG::sync();
-    PHASE(0);
+    PH(0);
     const auto load_pair = [&](int i) {
       const int n0 = 2 * i - Gq.pad_left, n1 = n0 + 1;
       return make_float2((n0 >= 0 && n0 < Gq.N) ? R(n0) * P.window[n0] + P.win_offset : 0.0f,
                          (n1 >= 0 && n1 < Gq.N) ? R(n1) * P.window[n1] + P.win_offset : 0.0f);
     };
     oo_wave_forward<TUNED ? 256 : 0>(z, OO, lane, load_pair);  // the reference's rdft network, register form (lld_ooura_wave.hpp)
-    PHASE(1);
+    PH(1);
     for (int k = lane; k <= M; k += 64) {
       const float m = bin_magnitude(oo_wave_bin<TUNED ? 256 : 0>(z, OO, k), k == 0 || k == M);
       mg[k] = m;
       pw[k] = m * m;
     }
     WaveG::sync();
-    PHASE(2);
+    PH(2);
     if (warm) {
       for (int k = lane; k < K; k += 64) prev[k] = mg[k];
       WaveG::sync();
@@ -312,7 +295,7 @@ __device__ __forceinline__ void compare_frame_wave_body(const LldParams &P, cons
       const float d = seq_sum_f32(aud, P.n_bands);
       rawA[0] = d / (float)P.n_bands;
     }
-    PHASE(3);
+    PH(3);
     // R12 in the block kernel's summation order: lane l holds the partial sums of its threads l, l+64, l+128, l+192
     {
       double v0[4][2];
@@ -351,14 +334,14 @@ __device__ __forceinline__ void compare_frame_wave_body(const LldParams &P, cons
         if (t < T60) rawA[3] = (float)tot[1] / (float)Gq.N60;
       }
     }
-    PHASE(4);
+    PH(4);
     spectral_frame_wave<W>(mg, pw, prev, t == 0, SC, K, reinterpret_cast<float *>(z), rawB + 26);   // z: free between two transforms
     WaveG::sync();
     for (int k = lane; k < K; k += 64) prev[k] = mg[k];
     WaveG::sync();
-    PHASE(5);
+    PH(5);
   }
-  PHASE_FLUSH;
+  PH.flush(g_phase_cmp);
 }
 
 // Two builds of the same body. Three waves per SIMD (167 VGPRs, 4 spilled): ComParE A+B alone 12.8 -> 10.1 ms per 1000 x 10 s,
@@ -385,7 +368,7 @@ inline size_t compare_quad_lds_floats(const OouraTab &oo) {
   return (size_t)cq::kTableFloats + (size_t)((oo_table_floats(oo) + 3) & ~3) + (size_t)kCmpQuadWaves * 4 * cq::kRowFloats;
 }
 }  // namespace
-__global__ void __launch_bounds__(kCmpQuadWaves * 64) __attribute__((amdgpu_waves_per_eu(CQ_WAVES, CQ_WAVES))) lld_compare_frame_quad(LldParams P, CompareParams Q, int n_runs) {
+__global__ void __launch_bounds__(kCmpQuadWaves * 64) __attribute__((amdgpu_waves_per_eu(cq::kWavesPerSimd, cq::kWavesPerSimd))) lld_compare_frame_quad(LldParams P, CompareParams Q, int n_runs) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   double2 *s_log = reinterpret_cast<double2 *>(smem);
   double *s_sharp = reinterpret_cast<double *>(smem + 512);

@@ -35,16 +35,12 @@
 #ifndef QPHASE
 #define QPHASE(i)
 #endif
-#ifndef CQ_BINS_GROUP
-#define CQ_BINS_GROUP 3                                    // bins of the entropy / moments loop whose operations may interleave
-#endif
-#ifndef CQ_WAVES
-#define CQ_WAVES 3                                         // waves per SIMD the register budget is set for
-#endif
 
 namespace smilehip {
 
 namespace cq {
+constexpr int kWavesPerSimd = 3;                             // waves per SIMD the register budget is set for
+constexpr int kBinsGroup = 3;                                // bins of the entropy / moments loop whose operations may interleave
 constexpr int kN = 320, kH = 160, kPad = 96, kN60 = 960, kM = 256, kK = 257, kBands = 26, kMfcc = 14;
 constexpr int kRowFloats = 2 * kQuadZPairs + 64 + 16;      // z (544 floats: transform, then mel terms / powers / chains) | lmel[32] | aud[32] | the row's state[16]
 // shared tables: log table (128 double2 = 512 floats, first: 16-byte aligned) | sharpness weights (256 doubles = 512 floats) |
@@ -403,7 +399,7 @@ __device__ __forceinline__ void compare_frame_quad_body(const LldParams &P, cons
             double mm = t1 * t1 * p;
             e1 += mm; mm *= t1; e2m += mm; e3 += mm * t1;
           }
-          if (m % CQ_BINS_GROUP == CQ_BINS_GROUP - 1) __builtin_amdgcn_sched_barrier(0);
+          if (m % kBinsGroup == kBinsGroup - 1) __builtin_amdgcn_sched_barrier(0);
         }
       }
       const double ent = QuadG::sum(e0, nullptr), mom2 = QuadG::sum(e1, nullptr), mom3 = QuadG::sum(e2m, nullptr), mom4 = QuadG::sum(e3, nullptr);

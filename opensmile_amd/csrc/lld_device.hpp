@@ -239,15 +239,11 @@ __device__ __forceinline__ float log_mel(float v, float melfloor, float log_floo
   return (v < melfloor) ? log_floor : glibc_logf(v);     // mfcc.cpp:239-243: log() on a float is logf (glibc_float.hpp)
 }
 __device__ __forceinline__ float log_mel_fast(float v, float melfloor, float log_floor) {
-#ifndef SMILEHIP_MFCC512_LIBRARY_LOGF
-  // (round 6) v_log_f32 x ln 2: two instructions instead of the library logf's ~10 -- v >= melfloor > 0 is a normal number, the
+  // v_log_f32 x ln 2: two instructions instead of the library logf's ~10 -- v >= melfloor > 0 is a normal number, the
   // library's denormal scaling and extended-precision product are dead weight in a kernel whose time is its instruction count
   // (868 -> 849 per pass). ~1.5 ulp of the logarithm instead of < 1; the distance to the reference did not move (per-frame-scaled
   // 1.0412e-6, max abs 1.4877e-4 before and after).
   return (v < melfloor) ? log_floor : __builtin_amdgcn_logf(v) * 0.693147182464599609375f;
-#else
-  return (v < melfloor) ? log_floor : logf(v);
-#endif
 }
 
 // R7: one cepstral coefficient, sequential band order (mfcc.cpp:251-273)

@@ -30,6 +30,7 @@
 #include "lld_device.hpp"
 #include "lld_launch.hpp"
 #include "lld_params.hpp"
+#include "phase_timing.hpp"
 
 namespace smilehip {
 
@@ -82,41 +83,12 @@ __device__ __forceinline__ double f_weight(float f) {
 }
 }  // namespace
 
-// Development instrumentation (tools/ubench/variant_f0.sh builds a private copy with -DSMILEHIP_PHASE_TIMING):
-// s_memtime at the phase boundaries, summed over all waves. Not compiled into the product.
-#ifdef SMILEHIP_PHASE_TIMING
-__device__ unsigned long long g_phase_f0[16];
-#define PHASE_DECL unsigned long long ph_acc[12] = {0}; unsigned long long ph_last = __builtin_amdgcn_s_memtime();
-#define PHASE(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); ph_acc[i] += t_ - ph_last; ph_last = t_; } while (0)
-#define PHASE_FLUSH do { if (lane == 0) for (int i_ = 0; i_ < 12; ++i_) atomicAdd(&g_phase_f0[i_], ph_acc[i_]); } while (0)
-extern "C" int smilehip_debug_phase_f0(unsigned long long *out16, int reset) {
-  if (out16 && hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_phase_f0), sizeof(unsigned long long) * 16) != hipSuccess) return -1;
-  if (reset) {
-    unsigned long long z[16] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_phase_f0), z, sizeof(z)) != hipSuccess) return -1;
-  }
-  return 0;
-}
+// the kernels' phases (phase_timing.hpp; tools/ubench/variant_f0.sh, tools/ubench/phase_timing_f0.py): slots 8 .. 11 are f0_shs's
+// own four parts
+SMILEHIP_PHASE_COUNTERS(g_phase_f0, 16, smilehip_debug_phase_f0)
 // (lld_f0_sweep: 0 pass 1, a block's first 14 bins | 1 pass 1, the wait for the next block | 2 pass 1, the last two bins + the next
 //  block's line from LDS | 3 pass 2, the wait for the block | 4 pass 2, the recurrences | 5 pass 2, target points + output)
-__device__ unsigned long long g_phase_sweep[8];
-#define SWEEP_WAIT_VM asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#define SWEEP_PHASE_FLUSH do { if (lane == 0) for (int i_ = 0; i_ < 8; ++i_) atomicAdd(&g_phase_sweep[i_], ph_acc[i_]); } while (0)
-extern "C" int smilehip_debug_phase_sweep(unsigned long long *out8, int reset) {
-  if (out8 && hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_phase_sweep), sizeof(unsigned long long) * 8) != hipSuccess) return -1;
-  if (reset) {
-    unsigned long long z[8] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_phase_sweep), z, sizeof(z)) != hipSuccess) return -1;
-  }
-  return 0;
-}
-#else
-#define PHASE_DECL
-#define PHASE(i)
-#define PHASE_FLUSH
-#define SWEEP_WAIT_VM
-#define SWEEP_PHASE_FLUSH
-#endif
+SMILEHIP_PHASE_COUNTERS(g_phase_sweep, 8, smilehip_debug_phase_sweep)
 
 // ---- per-frame phases. Lane l owns bins i = l + 64 m, m = 0..8 (bin 512: lane 0); all loops over m are unrolled
 // so that a phase's LDS reads are issued together. A, B: the frame's two double arrays.
@@ -336,15 +308,7 @@ __device__ __forceinline__ int f0_shs(const F0Tbl &T, const F0Params &Q, int lan
   // frame (a few hundred integer operations) and brings the kernel to three waves per SIMD.
   int lane = lane_in;
   asm volatile("" : "+v"(lane));
-#ifdef SMILEHIP_PHASE_TIMING
-  unsigned long long sub_t[5];
-  sub_t[0] = __builtin_amdgcn_s_memtime();
-#define F0_SUB(i) sub_t[i] = __builtin_amdgcn_s_memtime()
-#define F0_SUB_FLUSH do { if (lane_in == 0) for (int i_ = 0; i_ < 4; ++i_) atomicAdd(&g_phase_f0[8 + i_], sub_t[i_ + 1] - sub_t[i_]); } while (0)
-#else
-#define F0_SUB(i)
-#define F0_SUB_FLUSH
-#endif
+  PhaseTimer<4> SUB;
   float *hps = reinterpret_cast<float *>(A), *SS = hps + kKP;
   const float *hps_row = hps_blk ? hps_blk + (((hps_fr >> 6) * G::kNB16) * 64 + (hps_fr & 63)) * 16 : nullptr;
   float hv[kPer];
@@ -381,7 +345,7 @@ __device__ __forceinline__ int f0_shs(const F0Tbl &T, const F0Params &Q, int lan
   if (hps_blk && Q.hps_tap) { F0_FOR_BINS(m, i) if (i < kK) Q.hps_tap[g * Q.ld_tap + i] = hv[m]; }
   WaveG::sync();
   if (only_scale) return 0;
-  F0_SUB(1);   // spline evaluation + auditory weighting
+  SUB(0);   // spline evaluation + auditory weighting
   // The chain's rows (hps_blk) are weighted spectra, >= +0: a bin past the end of the spectrum may then be read as +0 and ADDED (x + 0 * s
   // = x bit for bit for x >= +0) instead of selected away -- kK zeros behind the row (where SS will be written afterwards) save a
   // compare and a select per bin and harmonic, 13 % of lld_f0_cand's vector instructions. Rows of the per-component operators
@@ -438,7 +402,7 @@ __device__ __forceinline__ int f0_shs(const F0Tbl &T, const F0Params &Q, int lan
   }
   // (B: the values widened, for the serial mean -- the chain forms it from SS when it needs it, f0_cand_body)
   F0_FOR_BINS(m, j) if (j < kK) { SS[j] = hv[m]; if constexpr (!CHAIN) B[j] = (double)hv[m]; }
-  F0_SUB(2);   // harmonic summation
+  SUB(1);   // harmonic summation
   if (mean_exact) {
     double part = 0.0;
     float mn = INFINITY;
@@ -451,7 +415,7 @@ __device__ __forceinline__ int f0_shs(const F0Tbl &T, const F0Params &Q, int lan
     *mean_exact = ok ? S / (double)kK : __longlong_as_double(0x7ff8000000000000ll);
   }
   WaveG::sync();
-  F0_SUB(3);   // exact-mean test
+  SUB(2);   // exact-mean test
   // local maxima, then the six best: greedy insertion (:262-283) keeps (score descending, bin ascending)
   float lf[kPer], rt[kPer];
   F0_FOR_BINS(m, j) {
@@ -505,8 +469,8 @@ __device__ __forceinline__ int f0_shs(const F0Tbl &T, const F0Params &Q, int lan
       n_found = r + 1;
     }
   }
-  F0_SUB(4);   // local maxima + top six
-  F0_SUB_FLUSH;
+  SUB(3);   // local maxima + top six
+  SUB.flush(g_phase_f0, 8);
   return n_found;
 }
 
@@ -622,7 +586,7 @@ __global__ void __launch_bounds__(kWaves * 64) lld_f0_frame(LldParams P, F0Param
   T.sp = c_sp; T.dec = c_dec; T.d1 = c_d1; T.d2 = c_d2; T.a = c_a; T.c = c_c; T.d = c_d; T.audw = c_audw;
   T.k = c_k; T.win = c_win;
   unsigned char *base = smem_f0 + f0_shared_bytes<G>(Q.N) + (size_t)wave * (kW * kFrameBytes);
-  PHASE_DECL
+  PhaseTimer<12> PH;
   // persistent waves: work item = up to kTileFrames consecutive frames of one utterance (TileRec), kW at a time
   const int tile_stride = __builtin_amdgcn_readfirstlane((int)gridDim.x) * kWaves;
   const int mode = Q.mode;                               // 0 chain, 1 cSpecScale only, 2 cPitchShs only (per-component operators)
@@ -641,10 +605,10 @@ __global__ void __launch_bounds__(kWaves * 64) lld_f0_frame(LldParams P, F0Param
                                       mode == 1 ? Q.in_rows + (row0 + tf + w) * Q.ld_in : nullptr, lane, A, A + kKP);
         if (lane == 0) *reinterpret_cast<double *>(reinterpret_cast<int *>(A + 2 * kKP) + 8 + 24) = es;
       }
-      PHASE(0);   // load .. 6*ut
+      PH(0);   // load .. 6*ut
       if (lane < n_act && mode != 2) f0_spline_serial<G>(T, reinterpret_cast<double *>(base + lane * kFrameBytes) + kKP);
       WaveG::sync();
-      PHASE(1);   // recurrences
+      PH(1);   // recurrences
 #pragma unroll 1
       for (int w = 0; w < n_act; ++w) {
         double *A = reinterpret_cast<double *>(base + w * kFrameBytes);
@@ -654,11 +618,11 @@ __global__ void __launch_bounds__(kWaves * 64) lld_f0_frame(LldParams P, F0Param
         if (lane == 0) ci[7] = nf;
       }
       WaveG::sync();
-      PHASE(2);   // interpolation, summation, top six
+      PH(2);   // interpolation, summation, top six
       if (mode == 1) continue;
       double mean = 0.0;
       if (lane < n_act) mean = f0_mean_serial<G>(reinterpret_cast<double *>(base + lane * kFrameBytes) + kKP);
-      PHASE(3);   // mean
+      PH(3);   // mean
 #pragma unroll 1
       for (int w = 0; w < n_act; ++w) {
         double *A = reinterpret_cast<double *>(base + w * kFrameBytes);
@@ -666,10 +630,10 @@ __global__ void __launch_bounds__(kWaves * 64) lld_f0_frame(LldParams P, F0Param
         const double es = *reinterpret_cast<double *>(ci + 8 + 24);
         f0_candidates<G>(Q, lane, row0 + tf + w, A, ci, reinterpret_cast<float *>(ci + 8), ci[7], __shfl(mean, w), es);
       }
-      PHASE(4);   // candidates + output
+      PH(4);   // candidates + output
     }
   }
-  PHASE_FLUSH;
+  PH.flush(g_phase_f0);
 }
 // ---- the chain as three kernels. Round 1's single kernel ran the spline's serial sweeps on one lane per frame with
 // three frames per wave: 61 idle lanes for 27 % of its time, and the LDS of three frames per wave capped the occupancy.
@@ -829,7 +793,7 @@ __global__ void __launch_bounds__(kSweepWaves * 64) lld_f0_sweep(F0Params Q) {
   float4 *hp4 = reinterpret_cast<float4 *>(S.hp) + (int64_t)tile * NB * 256 + lane;   // block bb, piece q: + bb * 256 + q * 64
   double2 *cp = reinterpret_cast<double2 *>(S.cp) + lane0;                     // block bb: + bb * 64
   const int tp_r = 4 * lane, tp_x = (lane >> 2) & 3;   // this lane's frame: its piece j is in slot tp_r + (j ^ tp_x)
-  PHASE_DECL
+  PhaseTimer<8> PH;
   // the tables are read through the constant address space (read-only for the kernel's lifetime): with wave-uniform
   // addresses they are scalar loads. Through a global pointer they are not -- the kernel stores to global memory, and a load
   // that a store might have clobbered stays a vector load (64 lanes fetching the same 8 bytes)
@@ -920,7 +884,7 @@ __global__ void __launch_bounds__(kSweepWaves * 64) lld_f0_sweep(F0Params Q) {
     ld_async(0);
     { int t0 = touch_records(0); asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(t0)); }
     ld_get(ca);
-    PHASE(7);
+    PH(7);
     for (int bb = 0; bb < NB; ++bb) {
       pace(bb);
       if (bb + 1 < NB) ld_async(bb + 1);                 // (tp is free: this block is in registers)
@@ -931,15 +895,15 @@ __global__ void __launch_bounds__(kSweepWaves * 64) lld_f0_sweep(F0Params Q) {
       if (edge) smooth(Edge{}, P14{}, yv, lo2, ca, hi2, bb); else smooth(Inner{}, P14{}, yv, lo2, ca, hi2, bb);
       if (edge) fw_block(Edge{}, P14{}, u, yv, up, bb); else fw_block(Inner{}, P14{}, u, yv, up, bb);
       __builtin_amdgcn_sched_barrier(0);                 // (the wait for the next block stays behind the first 14 bins)
-      PHASE(0);
-      SWEEP_WAIT_VM;
-      PHASE(1);
+      PH(0);
+      phase_wait_vm();
+      PH(1);
       if (bb + 1 < NB) { const float4 h = tp[tp_r + tp_x]; hi2[0] = h.x; hi2[1] = h.y; }
       if (edge) smooth(Edge{}, P2{}, yv, lo2, ca, hi2, bb); else smooth(Inner{}, P2{}, yv, lo2, ca, hi2, bb);
       if (edge) fw_block(Edge{}, P2{}, u, yv, up, bb); else fw_block(Inner{}, P2{}, u, yv, up, bb);
       lo2[0] = ca[14]; lo2[1] = ca[15];
       if (bb + 1 < NB) ld_get(ca);
-      PHASE(2);
+      PH(2);
     }
   }
   // ---- pass 2, blocks from the top: u of the block again, the backward recurrence, the target points above its bins
@@ -961,7 +925,7 @@ __global__ void __launch_bounds__(kSweepWaves * 64) lld_f0_sweep(F0Params Q) {
     for (int bb = NB - 1; bb >= 0; --bb) {
       double up = rec_cp.x;
       lo2[0] = __int_as_float(__double2loint(rec_cp.y)); lo2[1] = __int_as_float(__double2hiint(rec_cp.y));
-      PHASE(3);
+      PH(3);
       pace(2 * NB - 1 - bb);
       if (bb > 0) { ld_async(bb - 1); rec_cp = cp[(int64_t)(bb - 1) * 64]; }
       {
@@ -982,7 +946,7 @@ __global__ void __launch_bounds__(kSweepWaves * 64) lld_f0_sweep(F0Params Q) {
         if (!edge || j <= kK - 2) { yn = sw[8 * j + 2] * yn + u[e]; u[e] = yn; }
         else u[e] = 0.0;                                 // bin K-1: y2 = 0; the bins above it do not exist
       }
-      PHASE(4);
+      PH(4);
       // smileMath_csplint + auditory weighting (specScale.cpp:340-353) of the target points whose lower source bin is j
 #pragma unroll
       for (int e = 15; e >= 0; --e) {
@@ -1015,12 +979,12 @@ __global__ void __launch_bounds__(kSweepWaves * 64) lld_f0_sweep(F0Params Q) {
       }
       y2_above = u[0];
       hi2[0] = ca[0]; hi2[1] = ca[1];
-      PHASE(5);
-      SWEEP_WAIT_VM;
+      PH(5);
+      phase_wait_vm();
       if (bb > 0) ld_get(ca);
     }
   }
-  SWEEP_PHASE_FLUSH;
+  PH.flush(g_phase_sweep);
 }
 
 template <int LOGM>
@@ -1041,14 +1005,14 @@ __device__ __forceinline__ void f0_cand_body(const LldParams &P, const F0Params 
   const int64_t row0 = P.tile_rec[tile].row0;
   const int n_fr = P.tile_rec[tile].n_frames;
   const F0Scratch S = f0_scratch<G>(Q);
-  PHASE_DECL
+  PhaseTimer<12> PH;
   for (int w = 0; w < n_fr; ++w) {
     const int64_t fr = (int64_t)(tile - Q.tile0) * kTileFrames + w;
     const double es = S.es[fr];
     double mean = 0.0;
     const int nf = f0_shs<G, true>(T, Q, lane, row0 + w, A, A + kKP, ci, nullptr, false, &mean, S.hp, fr);
     WaveG::sync();
-    PHASE(2);   // rows from global, summation, top six
+    PH(2);   // rows from global, summation, top six
     if (mean != mean) {                                  // (wave-uniform) no exactness guarantee: the reference's chain
       const float *SSf = reinterpret_cast<const float *>(A) + kKP;
       F0_FOR_BINS(m, j) if (j < kK) (A + kKP)[j] = (double)SSf[j];     // (the summation spectrum widened: f0_shs<CHAIN> leaves only the floats)
@@ -1056,11 +1020,11 @@ __device__ __forceinline__ void f0_cand_body(const LldParams &P, const F0Params 
       if (lane == 0) mean = f0_mean_serial<G>(A + kKP);
       mean = wave_first_d(mean);
     }
-    PHASE(3);   // mean
+    PH(3);   // mean
     f0_candidates<G>(Q, lane, row0 + w, A, ci, reinterpret_cast<float *>(ci + 8), nf, mean, es);
-    PHASE(4);   // candidates + output
+    PH(4);   // candidates + output
   }
-  PHASE_FLUSH;
+  PH.flush(g_phase_f0);
 }
 
 // (the tuned geometry at four waves per SIMD: 128 VGPRs, 13 spilled dwords -- 0.97 -> 0.85 ms per 260 k frames; the other

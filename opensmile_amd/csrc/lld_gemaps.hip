@@ -30,34 +30,13 @@
 #include "lld_device.hpp"
 #include "lld_launch.hpp"
 #include "lld_params.hpp"
+#include "phase_timing.hpp"
 
 namespace smilehip {
 
-// Development instrumentation (tools/ubench/variant_any.sh gemaps <name> -DSMILEHIP_PHASE_TIMING): s_memtime at the phase
-// boundaries of lld_gemaps_harm, summed over all waves. Not compiled into the product.
-#ifdef SMILEHIP_PHASE_TIMING
-__device__ unsigned long long g_phase_gm[16];
-#define GPHASE_DECL unsigned long long gph_acc[8] = {0}; unsigned long long gph_last = __builtin_amdgcn_s_memtime();
-#define GPHASE(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); gph_acc[i] += t_ - gph_last; gph_last = t_; } while (0)
-#define GPHASE_FLUSH do { if ((threadIdx.x & 63) == 0) for (int i_ = 0; i_ < 8; ++i_) atomicAdd(&g_phase_gm[i_], gph_acc[i_]); } while (0)
-// the 20 ms frame kernel's phases go to slots 8 .. 15
-#define GPHASE20_FLUSH do { if ((threadIdx.x & 63) == 0) for (int i_ = 0; i_ < 8; ++i_) atomicAdd(&g_phase_gm[8 + i_], gph_acc[i_]); } while (0)
-}  // namespace smilehip
-extern "C" int smilehip_debug_phase_gm(unsigned long long *out16, int reset) {
-  if (out16 && hipMemcpyFromSymbol(out16, HIP_SYMBOL(smilehip::g_phase_gm), sizeof(unsigned long long) * 16) != hipSuccess) return -1;
-  if (reset) {
-    unsigned long long z[16] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(smilehip::g_phase_gm), z, sizeof(z)) != hipSuccess) return -1;
-  }
-  return 0;
-}
-namespace smilehip {
-#else
-#define GPHASE_DECL
-#define GPHASE(i)
-#define GPHASE_FLUSH
-#define GPHASE20_FLUSH
-#endif
+// the phases of lld_gemaps_harm in slots 0 .. 7, the 20 ms frame kernel's in slots 8 .. 15 (phase_timing.hpp;
+// tools/ubench/variant_any.sh gemaps <name> -DSMILEHIP_PHASE_TIMING, tools/ubench/phase_timing_gm.py)
+SMILEHIP_PHASE_COUNTERS(g_phase_gm, 16, smilehip_debug_phase_gm)
 
 namespace {
 constexpr int kRun = 8;            // 20 ms frames per run (same runs as the ComParE A+B kernel)
@@ -224,7 +203,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) l
   };
   const bool ahead = !xuf && P.N <= 512;                 // (longer frames -- 20 ms above 25.6 kHz -- are read at the frame like float input)
   if (ahead) prefetch(xu + (int64_t)(t0 > 0 ? t0 - 1 : 0) * P.H, lane);
-  GPHASE_DECL
+  PhaseTimer<8> PH;
   for (int t = (t0 > 0 ? t0 - 1 : 0); t < t_last; ++t) {
     int lane = lane_in;                                  // opaque per frame (see lld_compare_frame_wave): nothing that depends on
     asm volatile("" : "+v"(lane));                       // the lane only is kept in registers across the frame loop
@@ -245,14 +224,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) l
       for (int n = lane; n < P.N; n += 64) { const float tmp = yv[n]; e2 += tmp * tmp; }
       e2 = WaveG::sum(e2, nullptr);
     }
-    GPHASE(0);   // frame into LDS, energy2
+    PH(0);   // frame into LDS, energy2
     const auto load_pair = [&](int i) {
       const int n0 = 2 * i - P.pad_left, n1 = n0 + 1;
       return make_float2((n0 >= 0 && n0 < P.N) ? yv[n0] * P.window[n0] + P.win_offset : 0.0f,
                          (n1 >= 0 && n1 < P.N) ? yv[n1] * P.window[n1] + P.win_offset : 0.0f);
     };
     oo_wave_forward(z, OO, lane, load_pair);             // the reference's rdft network, register form (lld_ooura_wave.hpp)
-    GPHASE(1);   // FFT
+    PH(1);   // FFT
     float *spec = G.spec220 + (f0 + t) * kRsI;
     for (int k = lane; k <= M; k += 64) {
       const float2 X = oo_wave_bin(z, OO, k);
@@ -267,7 +246,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) l
       }
     }
     WaveG::sync();
-    GPHASE(2);   // magnitudes, spectrum rows for cSpecResample
+    PH(2);   // magnitudes, spectrum rows for cSpecResample
     if (warm) {
       for (int k = lane; k < K; k += 64) prev[k] = mg[k];
       WaveG::sync();
@@ -291,15 +270,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) l
       raw[0] = d / (float)P.n_bands;
     }
     if (lane == 0) raw[10] = (float)(e2 / (double)P.N) * 1.0f + 0.0f;
-    GPHASE(3);   // mel, auditory spectrum, MFCC
+    PH(3);   // mel, auditory spectrum, MFCC
     gemaps_spectral_wave(mg, pw, prev, t == 0, lg, G, K, lane, raw + 1);
     if (lane == 0) raw[11] = 0.0f;
     WaveG::sync();
     for (int k = lane; k < K; k += 64) prev[k] = mg[k];
     WaveG::sync();
-    GPHASE(4);   // GeMAPS spectral descriptors
+    PH(4);   // GeMAPS spectral descriptors
   }
-  GPHASE20_FLUSH;
+  PH.flush(g_phase_gm, 8);
 }
 
 // Sixteen lanes per frame, four runs per wave (lld_gemaps_quad.hpp): the shipped geometry. Workgroups of four waves, three per CU.
@@ -865,7 +844,7 @@ __global__ void __launch_bounds__(HarmG<LOGM>::kWaves * 64) lld_gemaps_harm(LldP
   float *hlr = hmag + 128;
   const double Fb = 1.0 / G.fsSec60;                     // frequency axis of the 60 ms spectrum: frq[i] = Fb * i
   const int tile_stride = (int)gridDim.x * kHarmWaves;
-  GPHASE_DECL
+  PhaseTimer<8> PH;
   const int lane_in = lane;
   const bool rows_mode = G.op_mode == 1;                 // per-component operator: F0, formants and magnitudes given per row
   const int n_tiles = rows_mode ? (int)((G.op_rows + 7) / 8) : G.n_tiles60;
@@ -946,7 +925,7 @@ __global__ void __launch_bounds__(HarmG<LOGM>::kWaves * 64) lld_gemaps_harm(LldP
         for (int k = lane; k <= kHM; k += 64) mg[k] = bin_magnitude(oo_wave_bin<kMC>(z, OO, k), k == 0 || k == kHM);
       }
       WaveG::sync();
-      GPHASE(0);   // load, window, FFT, magnitudes
+      PH(0);   // load, window, FFT, magnitudes
       // computeAcf (:590-630): inverse real FFT of the squared magnitudes, |.| / nBins, lags 0 .. nBins-1
       // rdft(N, -1) on the packed squares (harmonics.cpp:609-627)
       oo_wave_inverse<kMC>(z, OO, lane, [&](int e) {
@@ -956,7 +935,7 @@ __global__ void __launch_bounds__(HarmG<LOGM>::kWaves * 64) lld_gemaps_harm(LldP
       });
       for (int k = lane; k <= kHM; k += 64) acf[k] = fabsf(oo_wave_inverse_out<kMC>(z, OO, k)) / (float)kHK;
       WaveG::sync();
-      GPHASE(1);   // ACF
+      PH(1);   // ACF
       // HNR at the ACF peak closest to the F0 lag (freqToAcfBinLin :393-401, getClosestPeak :632-665, computeAcfHnr_dB :690-712)
       float hnr_db = 0.0f;
       {
@@ -992,7 +971,7 @@ __global__ void __launch_bounds__(HarmG<LOGM>::kWaves * 64) lld_gemaps_harm(LldP
           hnr_db = (float)ret;
         }
       }
-      GPHASE(2);   // HNR peak search
+      PH(2);   // HNR peak search
       // findHarmonicPeaks, frequency-axis branch (:478-546): harmonic i = lane, lane + 64
       const int firstBin = harm_freq_to_bin(Fb, 0.5f * F0, kHK);
       for (int i = lane; i < 128; i += 64) {
@@ -1025,7 +1004,7 @@ __global__ void __launch_bounds__(HarmG<LOGM>::kWaves * 64) lld_gemaps_harm(LldP
         hbin[i] = bin; hfi[i] = fi; hmag[i] = mag; hlr[i] = mi;      // hlr: interpolated magnitude for now
       }
       WaveG::sync();
-      GPHASE(3);   // harmonic peaks
+      PH(3);   // harmonic peaks
       // postProcessHarmonics(…, true) (:550-588): log magnitudes relative to harmonic 0 (log10 of a float: log10f), then the
       // duplicate removal, which is sequential (an entry is compared with its predecessor AFTER that one was cleared)
       {
@@ -1063,7 +1042,7 @@ __global__ void __launch_bounds__(HarmG<LOGM>::kWaves * 64) lld_gemaps_harm(LldP
         if ((C1 >> lane) & 1ull) { hbin[64 + lane] = 0; hfi[64 + lane] = 0.0f; hmag[64 + lane] = 0.0f; hlr[64 + lane] = -201.0f; }
         WaveG::sync();
       }
-      GPHASE(4);   // log magnitudes + duplicate removal
+      PH(4);   // log magnitudes + duplicate removal
       // getFormantAmplitudeIndices (:714-740): the strongest harmonic within 0.8 .. 1.2 of the formant frequency
       int fa[3];
       const float *fm = G.formants + (r20 + tf) * G.fm_ld;
@@ -1091,14 +1070,14 @@ __global__ void __launch_bounds__(HarmG<LOGM>::kWaves * 64) lld_gemaps_harm(LldP
         for (int f = 0; f < 3; ++f) o[3 + f] = (fa[f] >= 0) ? hlr[fa[f]] : 0.0f;   // :957-973
       }
       WaveG::sync();
-      GPHASE(5);   // formant amplitudes + output
+      PH(5);   // formant amplitudes + output
     }
   }
   if (G.harm_ctl && lane_in == 0 && atomicAdd(&G.harm_ctl[1], 1) == (int)gridDim.x * kHarmWaves - 1) {
     G.harm_ctl[0] = 0;
     G.harm_ctl[1] = 0;
   }
-  GPHASE_FLUSH;
+  PH.flush(g_phase_gm);
 }
 
 // ------------------------------------------------------------------------------------------------ selectors + smoothers

@@ -21,6 +21,7 @@
 #include "lld_launch.hpp"
 #include "lld_params.hpp"
 #include "lld_pitch_contour.hpp"
+#include "phase_timing.hpp"
 
 namespace smilehip {
 
@@ -28,26 +29,7 @@ namespace smilehip {
 // the frame body, summed over all waves by lane 0. Not compiled into the product. (Wave RESIDENCE, not issue slots: with six waves per
 // SIMD a phase that waits for memory shows large here and costs little -- round 3 learnt that by turning the kernel into persistent
 // waves with a register prefetch: 256 VGPRs, one wave per SIMD, 3 x slower.)
-#ifdef SMILEHIP_PHASE_TIMING
-__device__ unsigned long long g_phase_is09[16];
-#define IPHASE_DECL unsigned long long iph_last = __builtin_amdgcn_s_memtime(); unsigned long long iph_acc[8] = {0};
-#define IPHASE(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); iph_acc[i] += t_ - iph_last; iph_last = t_; } while (0)
-#define IPHASE_FLUSH do { if ((threadIdx.x & 63) == 0) for (int i_ = 0; i_ < 8; ++i_) atomicAdd(&g_phase_is09[i_], iph_acc[i_]); } while (0)
-}  // namespace smilehip
-extern "C" int smilehip_debug_phase_is09(unsigned long long *out16, int reset) {
-  if (out16 && hipMemcpyFromSymbol(out16, HIP_SYMBOL(smilehip::g_phase_is09), sizeof(unsigned long long) * 16) != hipSuccess) return -1;
-  if (reset) {
-    unsigned long long z[16] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(smilehip::g_phase_is09), z, sizeof(z)) != hipSuccess) return -1;
-  }
-  return 0;
-}
-namespace smilehip {
-#else
-#define IPHASE_DECL
-#define IPHASE(i)
-#define IPHASE_FLUSH
-#endif
+SMILEHIP_PHASE_COUNTERS(g_phase_is09, 16, smilehip_debug_phase_is09)
 
 // the tables a frame reads: in global memory for the workgroup kernel, staged in LDS once per workgroup for the wave kernel
 // (143 global loads per frame and wave before: the kernel waited on them)
@@ -91,10 +73,10 @@ __device__ __forceinline__ void is09_frame_body(const LldParams &P, const Is09Pa
   const PcmIn x = pcm_in(P) + (P.samp_off[lo] + t * (int64_t)P.H);
   float *out = Q.raw16 + row * 16;
 
-  IPHASE_DECL
+  PhaseTimer<8> PH;
   for (int n = G::tid(); n < P.N; n += G::size()) xr[n] = x[n];                      // R0 (or already done: float input)
   G::sync();
-  IPHASE(0);   // utterance lookup + frame load
+  PH(0);   // utterance lookup + frame load
 
   // R12 cMZcr::processVector, zcr (mzcr.cpp:117-124): on the RAW frames
   {
@@ -104,7 +86,7 @@ __device__ __forceinline__ void is09_frame_body(const LldParams &P, const Is09Pa
     const int total = G::sum_i(cnt, iscr);
     if (G::tid() == 0) out[13] = (float)total / (float)P.N;
   }
-  IPHASE(1);   // ZCR
+  PH(1);   // ZCR
   // R2 + R3, then R12 cEnergy rms on the WINDOWED frame (energy.cpp:152-168)
   double e2 = 0.0;
   for (int n = G::tid(); n < P.N; n += G::size()) {
@@ -119,7 +101,7 @@ __device__ __forceinline__ void is09_frame_body(const LldParams &P, const Is09Pa
     const double d = G::sum(e2, scr);
     if (G::tid() == 0) out[0] = (float)sqrt(d / (float)P.N) * 1.0f + 0.0f;
   }
-  IPHASE(2);   // pre-emphasis, window, RMS energy
+  PH(2);   // pre-emphasis, window, RMS energy
   // R4 forward real FFT: the reference's operation order (lld_ooura.hpp / lld_ooura_wave.hpp)
   const auto load_pair = [&](int i) {
     const int n0 = 2 * i - P.pad_left, n1 = n0 + 1;
@@ -133,7 +115,7 @@ __device__ __forceinline__ void is09_frame_body(const LldParams &P, const Is09Pa
     for (int k = G::tid(); k <= M; k += G::size()) mg[k] = bin_magnitude(ooura_bin(z, T.oo, k), k == 0 || k == M);   // R5
   }
   G::sync();
-  IPHASE(3);   // forward transform + magnitudes
+  PH(3);   // forward transform + magnitudes
   // R6 / R7: mel (usePower per config) -> log -> DCT
   for (int k = G::tid(); k <= M; k += G::size()) sp[k] = P.use_power ? mg[k] * mg[k] : mg[k];
   G::sync();
@@ -144,7 +126,7 @@ __device__ __forceinline__ void is09_frame_body(const LldParams &P, const Is09Pa
     out[1 + r] = dct_coeff(lmel, T.dct_rows + r * P.n_bands, P.n_bands, P.dct_gain[r]);
   G::sync();
 
-  IPHASE(4);   // mel, log, DCT
+  PH(4);   // mel, log, DCT
   // R9 cAcf (acf.cpp:249-349): ACF of the power spectrum, then the cepstrum instance
   for (int k = G::tid(); k <= M; k += G::size()) sp[k] = mg[k] * mg[k];                // usePower=1 (:252-259)
   G::sync();
@@ -158,7 +140,7 @@ __device__ __forceinline__ void is09_frame_body(const LldParams &P, const Is09Pa
   if constexpr (kWave) oo_wave_irfft_even<MC>(sp, z, T.oo, cep, (float)P.K, false, G::tid());
   else oo_irfft_even<G>(sp, z, T.oo, cep, (float)P.K, false);
 
-  IPHASE(5);   // ACF + cepstrum: two inverse transforms, 257 double logs
+  PH(5);   // ACF + cepstrum: two inverse transforms, 257 double logs
   // R10 cPitchACF::processVector, per-frame part (pitchACF.cpp:137-192)
   double voicing, Tsamp;
   int max_idx;
@@ -171,8 +153,8 @@ __device__ __forceinline__ void is09_frame_body(const LldParams &P, const Is09Pa
     out[14] = (float)voicing;
     out[15] = pitch;                                    // smoothed in place by lld_pitch_smooth
   }
-  IPHASE(6);   // cPitchACF
-  IPHASE_FLUSH;
+  PH(6);   // cPitchACF
+  PH.flush(g_phase_is09);
 }
 
 // one workgroup per frame (any FFT size the LDS holds)
@@ -223,17 +205,10 @@ __global__ void __launch_bounds__(256) lld_is09_frame_wave(LldParams P, Is09Para
 // magnitudes, the ACF and the cepstrum stay in registers (17 + 16 + 16 per lane): the inverse transforms take their real input
 // from the registers (lld_ooura_quad.hpp: oo_quad_inverse_real), the pitch phase reads its neighbours with row rotations.
 // 2.2 KB per frame; workgroups of four waves (16 frames + 8 KB of tables = 43 KB), three per CU = three waves per SIMD, persistent.
-#ifndef SMILEHIP_IS09_QUAD_WAVES
-#define SMILEHIP_IS09_QUAD_WAVES 3                         // waves per SIMD the register budget is set for (experiments: 2)
-#endif
-#ifndef SMILEHIP_IS09_PREFETCH_EARLY
-#define SMILEHIP_IS09_PREFETCH_EARLY 0
-#endif
-#ifndef SMILEHIP_IS09_LOG_GROUP
-#define SMILEHIP_IS09_LOG_GROUP 3
-#endif
 namespace {
-constexpr int kQuadWaves = 4;
+constexpr int kQuadWaves = 4;                               // waves per workgroup
+constexpr int kQuadWavesPerSimd = 3;                        // waves per SIMD the register budget is set for
+constexpr int kQuadLogBatch = 3;                            // logarithms of the cepstrum input whose operations may interleave
 constexpr int kQuadKpad = 260;
 constexpr int kQuadLmel = 2 * 257;                          // the log mel bands' place in the frame's buffer: behind the two rows of 257 mel terms
 constexpr int kQuadFrameFloats = (2 * kQuadZPairs > kQuadLmel + 34 ? 2 * kQuadZPairs : kQuadLmel + 34);      // (548: the transform needs 544)
@@ -351,11 +326,11 @@ __device__ __forceinline__ void is09_quad_body(const LldParams &P, const Is09Par
   // asked for at the fetch itself they are two memory round trips during which the wave -- one of three on its SIMD -- waits)
   // (the FULL instance has the two registers to spare; the general ones ask at the fetch)
   const int64_t next_base = (FULL && next_row >= 0) ? is09_quad_base(P, next_row) : 0;
-  IPHASE_DECL
+  PhaseTimer<8> PH;
 #pragma unroll
   for (int it = 0; it < NIT; ++it) { const int n = j + 16 * it; if (FULL || n < N) xr[n] = R[it]; }
   QuadG::sync();
-  IPHASE(0);   // utterance lookup + frame load
+  PH(0);   // utterance lookup + frame load
   // R12 cMZcr::processVector, zcr (mzcr.cpp:117-124): on the RAW frames
   {
     int cnt = 0;
@@ -368,7 +343,7 @@ __device__ __forceinline__ void is09_quad_body(const LldParams &P, const Is09Par
     const int total = QuadG::sum_i(cnt, nullptr);
     if (j == 0) out[13] = (float)total / (float)N;
   }
-  IPHASE(1);   // ZCR
+  PH(1);   // ZCR
   // R2 + R3, then R12 cEnergy rms on the WINDOWED frame (energy.cpp:152-168): the lane's samples in R again, then in place
   double e2 = 0.0;
 #pragma unroll 8
@@ -391,7 +366,7 @@ __device__ __forceinline__ void is09_quad_body(const LldParams &P, const Is09Par
 #pragma unroll
   for (int it = 0; it < NIT; ++it) { const int n = j + 16 * it; if (FULL || n < N) xr[n] = R[it]; }
   QuadG::sync();
-  IPHASE(2);   // pre-emphasis, window, RMS energy
+  PH(2);   // pre-emphasis, window, RMS energy
   // R4 forward real FFT in the reference's operation order (all of the frame is in registers before the transposition writes
   // z = the same buffer), R5 magnitudes: mv[m] = |X[j + 16 m]|, kept in registers for the two inverse transforms
   oo_quad_forward(z, T.oo, lane64, [&](int i) {
@@ -428,7 +403,7 @@ __device__ __forceinline__ void is09_quad_body(const LldParams &P, const Is09Par
     }
   }
   QuadG::sync();
-  IPHASE(3);   // forward transform + magnitudes
+  PH(3);   // forward transform + magnitudes
   // R6 / R7: mel (usePower per config) -> log -> DCT
   // a lane takes band j and band n_bands - 1 - j: the bands widen with their index, and a lane's two sums are walked one after
   // the other -- narrow + wide is about the same length in every lane (band j and j + 16: lane 9 walked 8 + 60 terms, lane 0 4)
@@ -442,7 +417,7 @@ __device__ __forceinline__ void is09_quad_body(const LldParams &P, const Is09Par
   QuadG::sync();
   if (j < P.n_mfcc) out[1 + j] = dct_coeff(lmel, T.dct_rows + j * P.n_bands, P.n_bands, P.dct_gain[j]);
   QuadG::sync();
-  IPHASE(4);   // mel, log, DCT
+  PH(4);   // mel, log, DCT
   // R9 cAcf (acf.cpp:249-349): ACF of the power spectrum (usePower = 1, :252-259), and what cPitchACF::processVector
   // (pitchACF.cpp:137-192) takes from it ...
   const int preskip = quad_pitch_preskip(Q.fsSec, Q.maxPitch);
@@ -456,10 +431,6 @@ __device__ __forceinline__ void is09_quad_body(const LldParams &P, const Is09Par
     voicing = quad_pitch_voicing(acf, preskip, lane64);
   }
   __builtin_amdgcn_sched_barrier(0);
-#if SMILEHIP_IS09_PREFETCH_EARLY
-  if (next_row >= 0) is09_quad_fetch<NIT, FULL>(P, FULL ? next_base : is09_quad_base(P, next_row), R, j);   // (the next pass's samples: their latency is the logarithms' and the second transform's)
-  __builtin_amdgcn_sched_barrier(0);
-#endif
   // ... then the cepstrum instance: log(P + 1) (:288-305)
   int max_idx;
   {
@@ -468,13 +439,11 @@ __device__ __forceinline__ void is09_quad_body(const LldParams &P, const Is09Par
     for (int m = 0; m < 17; ++m) {
       const float p = mv[m] * mv[m];
       pw[m] = (p > 0.0f) ? (float)log_d<true>((double)p + 1.0, T.log_tab) : 0.0f;   // (1 + p >= 1: never the library's path)
-      if (m % SMILEHIP_IS09_LOG_GROUP == SMILEHIP_IS09_LOG_GROUP - 1) __builtin_amdgcn_sched_barrier(0);   // (a few logarithms' intermediates at a time: all 17 at once spill)
+      if (m % kQuadLogBatch == kQuadLogBatch - 1) __builtin_amdgcn_sched_barrier(0);   // (a few logarithms' intermediates at a time: all 17 at once spill)
     }
     oo_quad_irfft_even_real(z, T.oo, cep, (float)P.K, false, lane64, pw);
-    IPHASE(5);   // ACF + cepstrum: two inverse transforms, 257 double logs
-#if !SMILEHIP_IS09_PREFETCH_EARLY
-    if (next_row >= 0) is09_quad_fetch<NIT, FULL>(P, FULL ? next_base : is09_quad_base(P, next_row), R, j);
-#endif
+    PH(5);   // ACF + cepstrum: two inverse transforms, 257 double logs
+    if (next_row >= 0) is09_quad_fetch<NIT, FULL>(P, FULL ? next_base : is09_quad_base(P, next_row), R, j);   // the next pass's samples
     max_idx = quad_pitch_cep_peak(cep, preskip, lane64);
   }
   if (j == 0) {
@@ -486,14 +455,14 @@ __device__ __forceinline__ void is09_quad_body(const LldParams &P, const Is09Par
     out[15] = pitch;                                    // smoothed in place by lld_pitch_smooth
   }
   QuadG::sync();
-  IPHASE(6);   // cPitchACF
-  IPHASE_FLUSH;
+  PH(6);   // cPitchACF
+  PH.flush(g_phase_is09);
 }
 }  // namespace
 
 // persistent workgroups; rows past the end of the batch repeat the last frame (same values to the same cells)
 template <int NIT, bool FULL>                            // samples per lane: N <= 16 NIT (FULL: N = 16 NIT, pad_left = 0)
-__global__ void __launch_bounds__(kQuadWaves * 64) __attribute__((amdgpu_waves_per_eu(SMILEHIP_IS09_QUAD_WAVES, SMILEHIP_IS09_QUAD_WAVES))) lld_is09_frame_quad(LldParams P, Is09Params Q) {
+__global__ void __launch_bounds__(kQuadWaves * 64) __attribute__((amdgpu_waves_per_eu(kQuadWavesPerSimd, kQuadWavesPerSimd))) lld_is09_frame_quad(LldParams P, Is09Params Q) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int Npad = (P.N + 3) & ~3;
   double2 *s_log = reinterpret_cast<double2 *>(smem);

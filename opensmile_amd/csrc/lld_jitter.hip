@@ -34,41 +34,14 @@
 #include "lld_device.hpp"
 #include "lld_launch.hpp"
 #include "lld_params.hpp"
+#include "phase_timing.hpp"
 
 namespace smilehip {
 
-// Development instrumentation (tools/ubench/variant_any.sh jitter <name> -DSMILEHIP_PHASE_TIMING): s_memtime at the phase
-// boundaries, summed over all waves. Not compiled into the product.
-#ifdef SMILEHIP_PHASE_TIMING
-__device__ unsigned long long g_phase_jit[8];
-struct JitPhase {
-  unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long last = __builtin_amdgcn_s_memtime();
-  __device__ __forceinline__ void operator()(int i) {
-    const unsigned long long t_ = __builtin_amdgcn_s_memtime();
-    acc[i] += t_ - last;
-    last = t_;
-  }
-  __device__ __forceinline__ void count() { acc[7] += 1; }   // voiced frames
-  __device__ __forceinline__ void flush(int lane) {
-    if (lane == 0) for (int i = 0; i < 8; ++i) atomicAdd(&g_phase_jit[i], acc[i]);
-  }
-};
-extern "C" int smilehip_debug_phase_jit(unsigned long long *out8, int reset) {
-  if (out8 && hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_phase_jit), sizeof(unsigned long long) * 8) != hipSuccess) return -1;
-  if (reset) {
-    unsigned long long z[8] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_phase_jit), z, sizeof(z)) != hipSuccess) return -1;
-  }
-  return 0;
-}
-#else
-struct JitPhase {
-  __device__ __forceinline__ void operator()(int) {}
-  __device__ __forceinline__ void count() {}
-  __device__ __forceinline__ void flush(int) {}
-};
-#endif
+// the phases of the jitter kernels; slot 7 counts the voiced frames (phase_timing.hpp; tools/ubench/variant_any.sh jitter <name>
+// -DSMILEHIP_PHASE_TIMING, tools/ubench/phase_timing_jitter.py)
+SMILEHIP_PHASE_COUNTERS(g_phase_jit, 8, smilehip_debug_phase_jit)
+typedef PhaseTimer<8> JitPhase;
 
 namespace {
 // Values that are the same in every lane but come out of vector instructions (loads through a vector address, double
@@ -94,19 +67,11 @@ __host__ __device__ inline int jit_scale(double Tw) {
 __host__ __device__ inline int jit_wave_cap(const F0Params &Q) {      // samples of wave per frame: the plan's bound, or the general one
   return Q.jit_cap > 0 ? Q.jit_cap : jit_scale(Q.jit_Tw) * kJitCap;
 }
-// The frame's wave samples in LDS: floats, widened by crossCorr as it reads them (exact). -DSMILEHIP_JITTER_WAVE_DOUBLE keeps them as
-// doubles (widened once, when the frame is loaded; the few float readers narrow them back, exactly): crossCorr's loop drops its two
-// conversions per sample and candidate, 10 -> 8 vector instructions -- and is SLOWER, 93 ms against 80 per 12 500 x 10 s (round 6,
-// profiles/r06_jitter_wave_double.txt): every lane reads its own samples, a wave then moves 1 KB per read instruction through the
-// LDS pipe (128 B per clock and CU, twelve waves), and the pipe, not the issue slots, becomes the limit.
-#ifdef SMILEHIP_JITTER_WAVE_DOUBLE
-typedef double JitSample;
-#else
-typedef float JitSample;
-#endif
+// The frame's wave samples in LDS are floats, widened by crossCorr as it reads them (exact). Kept as doubles they were measured
+// and were slower, 93 ms against 80 per 12 500 x 10 s: the LDS pipe, not the issue slots, becomes the limit.
 inline size_t jit_shared_bytes(const F0Params &Q, int threads) {   // ccs (doubles) | wv | avgWf | pbuf | jit_terms
   const size_t r = (size_t)jit_scale(Q.jit_Tw);
-  return r * kJitMaxCand * 8 + (size_t)jit_wave_cap(Q) * sizeof(JitSample) + r * kJitMaxPeriod * 4 + (size_t)kJitMaxPeriods * 4 +
+  return r * kJitMaxCand * 8 + (size_t)jit_wave_cap(Q) * sizeof(float) + r * kJitMaxPeriod * 4 + (size_t)kJitMaxPeriods * 4 +
          (size_t)threads * 4;
 }
 
@@ -122,7 +87,7 @@ __device__ __forceinline__ JitState jit_reset_state() { return JitState{-1, 0, 0
 
 struct JitLds {
   double *ccs;        // [jitMaxCand]
-  JitSample *wv;      // [jitCap] the frame's wave samples
+  float *wv;      // [jitCap] the frame's wave samples
   float *avgWf;       // [jitMaxPeriod]
   int *pbuf;          // [kJitMaxPeriods]
   float *jit_terms;   // [threads] one term per lane and wave for the sequential energy sums
@@ -133,7 +98,7 @@ __device__ __forceinline__ JitLds jit_lds(unsigned char *smem, const F0Params &Q
   const int jr = uni(jit_scale(Q.jit_Tw));
   L.jitCap = uni(jit_wave_cap(Q)); L.jitMaxCand = jr * kJitMaxCand; L.jitMaxPeriod = jr * kJitMaxPeriod;
   L.ccs = reinterpret_cast<double *>(smem);
-  L.wv = reinterpret_cast<JitSample *>(L.ccs + L.jitMaxCand);
+  L.wv = reinterpret_cast<float *>(L.ccs + L.jitMaxCand);
   L.avgWf = reinterpret_cast<float *>(L.wv + L.jitCap);
   L.pbuf = reinterpret_cast<int *>(L.avgWf + L.jitMaxPeriod);
   L.jit_terms = reinterpret_cast<float *>(L.pbuf + kJitMaxPeriods);
@@ -166,7 +131,7 @@ __device__ __forceinline__ bool jit_frame(const F0Params &Q, const JitLds &L, co
   asm volatile("" : "+v"(lane), "+v"(tid));              // opaque per frame: lane-only address arithmetic is not kept in
                                                          // registers across the frame loop (see f0_shs)
   double *ccs = L.ccs;
-  JitSample *wv = L.wv;
+  float *wv = L.wv;
   float *avgWf = L.avgWf;
   int *pbuf = L.pbuf;
   const double Tw = Q.jit_Tw;
@@ -216,7 +181,7 @@ __device__ __forceinline__ bool jit_frame(const F0Params &Q, const JitLds &L, co
 #pragma unroll
           for (int q = 0; q < 8; ++q) { const long i = i0 + (long)q * kJitThreads; v[q] = sample(lastIdx + (i < nT ? i : nT - 1)); }
 #pragma unroll
-          for (int q = 0; q < 8; ++q) { const long i = i0 + (long)q * kJitThreads; if (i < nT) wv[i] = (JitSample)v[q]; }
+          for (int q = 0; q < 8; ++q) { const long i = i0 + (long)q * kJitThreads; if (i < nT) wv[i] = v[q]; }
         }
       };
       if (x.f) fill([&](long n) { return x.f[n]; });
@@ -225,7 +190,7 @@ __device__ __forceinline__ bool jit_frame(const F0Params &Q, const JitLds &L, co
     for (long i = tid; i <= T0f; i += kJitThreads) avgWf[i] = 0.0f;
     __syncthreads();
     PH(0);   // frame set-up + wave load
-    PH.count();
+    PH.count(7);
     int numPeriods = 0;
     long pp = 0;
     float minCC = -2.0f;
@@ -258,7 +223,7 @@ __device__ __forceinline__ bool jit_frame(const F0Params &Q, const JitLds &L, co
         }
         if (c < clo) continue;
         const long tf = T0minF + c;
-        const JitSample *xa = wv + start, *ya = wv + start + tf;
+        const float *xa = wv + start, *ya = wv + start + tf;
         const long nr = tf >> 2;
         const double sx = bx + ex, sy = (bx + bp + ep) - sx;     // sum of x[0..tf), sum of x[tf..2tf)
         const double mx = sx / (double)tf, my = sy / (double)tf;
@@ -266,7 +231,7 @@ __device__ __forceinline__ bool jit_frame(const F0Params &Q, const JitLds &L, co
         // sums stay sequential in the reference's order); two rounds per loop iteration on alternating registers
         double cc = 0.0, nx = 0.0, ny = 0.0;
         {
-          const auto add4 = [&](const JitSample (&xs)[4], const JitSample (&ys)[4]) {
+          const auto add4 = [&](const float (&xs)[4], const float (&ys)[4]) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
               const double dx = (double)xs[q] - mx, dy = (double)ys[q] - my;
@@ -276,7 +241,7 @@ __device__ __forceinline__ bool jit_frame(const F0Params &Q, const JitLds &L, co
             }
           };
           const int nri = (int)nr;
-          JitSample xv[4], yv[4], xn[4], yn[4];
+          float xv[4], yv[4], xn[4], yn[4];
 #pragma unroll
           for (int q = 0; q < 4; ++q) { xv[q] = xa[q]; yv[q] = ya[q]; }
           int r = 0;
@@ -336,9 +301,9 @@ __device__ __forceinline__ bool jit_frame(const F0Params &Q, const JitLds &L, co
       if (maxI >= 0) {
         start += pp;
         // amplitudeDiff (:422-459): max - min of x[1 .. pp-2] in both periods
-        float mx0 = (float)wv[os + 1], mn0 = mx0, mx1 = (float)wv[start + 1], mn1 = mx1;
+        float mx0 = wv[os + 1], mn0 = mx0, mx1 = wv[start + 1], mn1 = mx1;
         for (long i = 1 + lane; i < pp - 1; i += 64) {
-          const float a = (float)wv[os + i], b = (float)wv[start + i];
+          const float a = wv[os + i], b = wv[start + i];
           mx0 = a > mx0 ? a : mx0; mn0 = a < mn0 ? a : mn0;
           mx1 = b > mx1 ? b : mx1; mn1 = b < mn1 ? b : mn1;
         }
@@ -354,7 +319,7 @@ __device__ __forceinline__ bool jit_frame(const F0Params &Q, const JitLds &L, co
         const float ad = fabsf((mx0 - mn0) - (mx1 - mn1));
         if (tid == 0) pbuf[numPeriods] = (int)os;
         numPeriods++;
-        for (long i = tid; i < T0f; i += kJitThreads) avgWf[i] += (float)wv[os + i];
+        for (long i = tid; i < T0f; i += kJitThreads) avgWf[i] += wv[os + i];
         double ccI = 0.0;
         const double maxId = fabs((double)T0minF + quad_vertex((double)(maxI - 1), ccs[maxI - 1], (double)maxI, ccs[maxI],
                                                                (double)(maxI + 1), ccs[maxI + 1], ccI)) * Tw;
@@ -387,7 +352,7 @@ __device__ __forceinline__ bool jit_frame(const F0Params &Q, const JitLds &L, co
     if (tid == 0) { pbuf[numPeriods] = (int)start; pbuf[numPeriods + 1] = (pp > 0) ? (int)(start + pp) : 0; }
     numPeriods++;
     for (long i = tid; i < T0f && start + i < nT; i += kJitThreads) {
-      avgWf[i] += (float)wv[start + i];
+      avgWf[i] += wv[start + i];
       avgWf[i] /= (float)numPeriods;
     }
     __syncthreads();
@@ -436,7 +401,7 @@ __device__ __forceinline__ bool jit_frame(const F0Params &Q, const JitLds &L, co
       for (long j = p0 + 2; j < lim; j += 64, k += 64) {
         const int cnt = (int)((lim - j < 64) ? (lim - j) : 64);
         float t = 0.0f;
-        if (ln < cnt) { const float delta = (float)wv[j + ln] - avgWf[k + ln]; t = delta * delta; }
+        if (ln < cnt) { const float delta = wv[j + ln] - avgWf[k + ln]; t = delta * delta; }
         En = chain_add(En, t, cnt);
         nEn += cnt;
       }
@@ -538,7 +503,7 @@ __global__ void __launch_bounds__(kJitThreads) lld_f0_jitter(LldParams P, F0Para
     js[0] = (double)S.lastIdx; js[1] = (double)S.lastMis; js[2] = (double)t_end;
     js[3] = S.lastT0; js[4] = S.lastDiff; js[5] = S.lastJL; js[6] = S.lastJD; js[7] = S.lastSh;
   }
-  PH.flush(lane);
+  PH.flush(g_phase_jit);
 }
 
 // Persistent waves; a work item = 64 consecutive frames [t0, t0 + 64) of utterance u (Q.jit_item_utt / jit_item_t0), taken
@@ -604,7 +569,7 @@ __global__ void __launch_bounds__(64) lld_jitter_runs(LldParams P, F0Params Q, c
     Q.jit_ctl[0] = 0;
     Q.jit_ctl[1] = 0;
   }
-  PH.flush(lane_in);
+  PH.flush(g_phase_jit);
 }
 
 namespace {

@@ -17,7 +17,7 @@
 //           delta-fused MP = 16 instances keep integer loads and convert on the vector ALU:
 //           typed_loads() below).
 //           Conversion (R0, scale folded into the window table), pre-emphasis
-//           (R2, the reference's two roundings; the previous sample comes from
+//           (R2, one fused multiply-add; the previous sample comes from
 //           the neighbour lane by DPP) and window (R3) happen in registers:
 //           z[m] = y[2n] + i*y[2n+1]; the real 512-FFT is a complex 256-FFT of z
 //           plus an untangle pass
@@ -28,7 +28,7 @@
 //           Order of the transposition traffic (round 8): the first DFT's last layer finishes its outputs in groups of four --
 //           k1 = 0, 4, 8, 12, then 1, 5, 9, 13, .. -- and each is twiddled and stored at once, so the sixteen stores are spread
 //           over that layer and the twiddles instead of standing in one block in front of the sixteen loads (which are issued
-//           in index order jj = 0 .. 15; the order of the second DFT's first layer was measured and is no gain). LDS operations
+//           in index order jj = 0 .. 15). LDS operations
 //           of a wave return in order: what a wave waits for is decided by the ORDER of its requests. No instruction is added,
 //           and an instruction's lane -> bank pattern does not depend on its position (tools/lds_bank_sim.py)
 //   spect.  lanes j and 16-j own mirror-image bins: the partner's half of Z
@@ -54,6 +54,7 @@
 // lld_mfcc_generic (SMILEHIP_FORCE_GENERIC=1).
 #include <hip/hip_runtime.h>
 #include "kernel_timing.hpp"
+#include "phase_timing.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -195,99 +196,31 @@ __device__ __forceinline__ float dpp_f(float v) {
 // offset (g H + 2 j) * 2 is ONE VGPR and load m adds the immediate 64 m -- everything else is wave-uniform and lives in
 // SGPRs: nothing to spill (a spill reload would put an s_waitcnt vmcnt(0) behind the loads and wait out the whole memory
 // latency in every pass). Samples outside a frame meet a zero of the window table and every stored frame lies inside
-// its utterance, so out-of-range addresses are only clamped into the buffer (wave-uniform branch, first / last span).
+// its utterance, so an out-of-range address needs no care: the buffer unit's range check answers it with zero (pcm_prefetch).
 //
 // PREEMPH: the predecessor x[2n - 1] of pair n's even sample is the neighbour lane's odd sample (DPP row_ror:1; lane 0 takes lane
-// 15's of the register one pair down). (round 7, measured and NOT taken) -DSMILEHIP_MFCC512_PRED_LOADS loads it instead: a third,
-// sign-extending 16-bit load per m (byte offset -2; the sample in front of the buffer is the offset's wrap-around and reads as zero)
-// and one 32-bit v_cvt_f32_i32 where the DPP form takes a DPP move and a select, both 64-bit encoded -- 849 -> 803 VALU instructions
-// per pass with the other round-7 changes, but the launch was 1.7 % SLOWER than without it (0.3641 against 0.3580 ms per 998 000
-// frames, three A/B pairs): thirteen more vector-memory instructions per pass cost more than the issue cycles they save.
-#ifdef SMILEHIP_MFCC512_PRED_LOADS
-#ifdef SMILEHIP_MFCC512_GLOBAL_LOADS
-#error "SMILEHIP_MFCC512_GLOBAL_LOADS loads no predecessor samples"
-#endif
-constexpr bool kPredLoads = true;
-#else
-constexpr bool kPredLoads = false;
-#endif
-// (round 7, measured and NOT taken) -DSMILEHIP_MFCC512_B16_SAMPLES: dword-aligned input read with the unaligned form's two 16-bit
-// loads per pair as well (32-bit v_cvt_f32_i32 instead of the 64-bit SDWA conversions). Alone on top of the kept form: 821 VALU
-// instructions, 129 of them 64-bit, 127 VGPRs, no scratch; its replayed VALU stream is shorter (0.2931 against 0.3022 ms per 998 000
-// frames) but the launch is 4 % SLOWER (0.3749 against 0.3605 ms, three A/B rounds on one box): 26 buffer loads per pass instead of
-// 13 for the same bytes. (Stacked on the predecessor loads the build spilled -- 128 VGPRs, scratch reloads in the pass loop -- and
-// its 0.4957 ms measures that.)
-#ifdef SMILEHIP_MFCC512_B16_SAMPLES
-#ifdef SMILEHIP_MFCC512_GLOBAL_LOADS
-#error "SMILEHIP_MFCC512_GLOBAL_LOADS loads dwords for aligned input: it cannot be combined with SMILEHIP_MFCC512_B16_SAMPLES"
-#endif
-constexpr bool kB16Samples = true;
-#else
-constexpr bool kB16Samples = false;
-#endif
-// (round 8) LDS latency out of the wave's critical path without one more LDS, vector-memory or vector-ALU instruction: three changes
-// of ORDER, each behind a switch (A/B aids, make MFCC512_EXTRA=-D...). The bits are the parent's in every combination
-// (tests/test_gpu_mfcc512_bits_r8.py). Figures: DESIGN.md 4.1, profiles/r08_ab.txt, profiles/r08_mfcc512_phases.txt.
-// KEPT: the transposition writes index by index behind the first DFT's last layer (-DSMILEHIP_MFCC512_WRITES_IN_ONE_BLOCK restores the
-// parent's form): 0.3808 -> 0.3756 ms per bench step on one box (faster in each of three interleaved rounds), 0.3663 -> 0.3581 on a
-// second one (four rounds; the kernel under the profiler 0.3632 -> 0.3555 ms).
-#ifdef SMILEHIP_MFCC512_WRITES_IN_ONE_BLOCK
-constexpr bool kWritesEarly = false;          // DFT, fifteen twiddle products, sixteen transposition writes
-#else
-constexpr bool kWritesEarly = true;           // last DFT layer, twiddle product and write index by index
-#endif
-// (round 8, measured and NOT taken) -DSMILEHIP_MFCC512_READS_IN_DFT_ORDER: the transposition reads in the order in which the second
-// DFT's first layer takes them (0, 4, 8, 12 | 1, 5, 9, 13 | ..): its four dft4 then wait for lgkmcnt(13, 12) / (9, 8) / (5, 4) / (1, 0)
-// where the index order makes the first one wait for (7), (3) -- thirteen of the sixteen reads. Alone on top of the parent it was not
-// faster in each of three rounds (0.3816 against 0.3808 ms, -0.7 % / -0.1 % / +1.4 %); on top of the early writes it changes nothing
-// (0.3582 against 0.3581 ms, four rounds; kernel 0.3557 against 0.3555 ms): with four waves per SIMD the other waves' instructions
-// fill the ~9 further reads' worth of waiting.
-#ifdef SMILEHIP_MFCC512_READS_IN_DFT_ORDER
-constexpr bool kReadsInDftOrder = true;
-#else
-constexpr bool kReadsInDftOrder = false;      // the transposition reads jj = 0 .. 15
-#endif
-// (round 8, measured and NOT taken) -DSMILEHIP_MFCC512_MIRROR_OPERAND: the untangle's row_mirror step as the DPP operand of the four
-// additions it feeds (written next to them, the compiler's DPP combiner folds it: it looks no further than 20 instructions ahead of a
-// move) instead of 16 moves of their own: 815 -> 797 VALU instructions per pass, but the 32 additions become 64-bit encoded (155 ->
-// 171 such instructions) and the launch is SLOWER: 0.3849 against 0.3808 ms per bench step (+1.1 %, slower in each of three
-// interleaved rounds on one box, alone on top of the parent).
-#ifdef SMILEHIP_MFCC512_MIRROR_OPERAND
-constexpr bool kMirrorOperand = true;
-#else
-constexpr bool kMirrorOperand = false;
-#endif
-#ifdef SMILEHIP_MFCC512_BPERMUTE_PARTNER
-constexpr bool kMirrorAtUse = false;          // (the crossbar form has no mirror step)
-#else
-constexpr bool kMirrorAtUse = kMirrorOperand;
-#endif
-// (round 9) The conversion int16 -> float by the buffer unit: a TYPED buffer load returns (float)x exactly. Aligned
+// 15's of the register one pair down): no further vector-memory instruction.
+//
+// The conversion int16 -> float is the buffer unit's: a TYPED buffer load returns (float)x exactly. Aligned
 // input: one tbuffer_load_format_xy [16_16, SSCALED] per pair in place of a dword load and two conversions; unaligned
 // input: two tbuffer_load_format_x [16, SSCALED] in place of two 16-bit loads and two conversions. The number of
-// vector-memory instructions is the parent's, 2 MP vector instructions per pass are gone, and every later operation
-// sees the same operands: the bits cannot change (tests/test_gpu_mfcc512_typed_loads.py). The loads are reached
+// vector-memory instructions is the integer form's, 2 MP vector instructions per pass are gone, and every later operation
+// sees the same operands: the bits are the integer form's (tests/test_gpu_mfcc512_typed_loads.py). The loads are reached
 // through the LLVM intrinsic by name -- no inline assembly: the compiler keeps its own s_waitcnt vmcnt bookkeeping and
 // folds 64 m into the immediate offset.
-// The samples are the window stage's own operands now, so they have to DIE there: the pass loop sets them to zero on
+// The samples are the window stage's own operands, so they have to DIE there: the pass loop sets them to zero on
 // the path that issues no further prefetch (the wave's last pass). While they stayed alive on that path the
 // pre-emphasis products could not overwrite their addend (v_fma_f32, 64-bit, instead of v_fmac) and 2 MP registers
 // stayed occupied through both transforms.
-// -DSMILEHIP_MFCC512_CVT_ON_VALU restores the parent's form everywhere (A/B aid). Census, A/B tables and replay floor:
-// DESIGN.md 4.1, profiles/r09_ab.txt.
-#if defined(SMILEHIP_MFCC512_CVT_ON_VALU) || defined(SMILEHIP_MFCC512_B16_SAMPLES) || defined(SMILEHIP_MFCC512_GLOBAL_LOADS)
-constexpr bool kTypedLoads = false;
-#else
-constexpr bool kTypedLoads = true;
-#endif
 // Per instance: the two floats per pair live from the prefetch issue to the window (aligned input: 2 MP registers
-// where the dword form holds MP), and an instance whose scratch would grow against the dword form keeps that form:
-// the PLP chain (every instance of it stands at 128 VGPRs already) and the delta-fused instances with MP = 16. With
-// this rule no instance has more scratch than its parent, all have <= 128 VGPRs and occupancy 4
+// where the dword form holds MP), and an instance whose scratch would grow against the dword form keeps that form
+// (integer loads, v_cvt_f32_i32 on the vector ALU): the PLP chain (every instance of it stands at 128 VGPRs already) and
+// the delta-fused instances with MP = 16. With this rule no instance has more scratch than with integer loads, all have
+// <= 128 VGPRs and occupancy 4
 // (tools/dev/kernel_resources.sh lld_mfcc512.hip).
 template <int MP, bool PLP, bool DELTA>
 constexpr bool typed_loads() {
-  return kTypedLoads && !PLP && !(MP == 16 && DELTA);
+  return !PLP && !(MP == 16 && DELTA);
 }
 typedef float float2v __attribute__((ext_vector_type(2)));
 __device__ float2v tbuffer_load_xy(__amdgpu_buffer_rsrc_t rsrc, int voffset, int soffset, int format, int aux)
@@ -303,23 +236,22 @@ constexpr int kFmt16Sscaled = 2 | (3 << 4);
 // constant zero; untyped loads ignore the field
 constexpr int kRsrcWord3 = 0x00020000, kRsrcWord3Typed = 0x00020000 | 4 | (5 << 3);
 
-// TYPED: v holds the two floats of pair m (their bits) in v[2 m], v[2 m + 1]
-template <int MP, bool ALIGNED, bool PREEMPH, bool TYPED>
+// TYPED: v holds the two floats of pair m (their bits) in v[2 m], v[2 m + 1]; integer loads: pair m as one dword in v[m]
+// (ALIGNED) or its two sign-extended samples in v[2 m], v[2 m + 1]
+template <int MP, bool ALIGNED, bool TYPED>
 struct FrameRegs {
-  uint32_t v[ALIGNED && !kB16Samples && !TYPED ? MP : 2 * MP];
-  uint32_t p[PREEMPH && kPredLoads ? MP : 1];        // x[2n - 1], sign-extended
+  uint32_t v[ALIGNED && !TYPED ? MP : 2 * MP];
 };
 
-// (round 6) The loads are BUFFER loads: a wave-uniform resource descriptor (base = the pass's first sample, size = what is left of the
+// The loads are BUFFER loads: a wave-uniform resource descriptor (base = the pass's first sample, size = what is left of the
 // PCM buffer behind it) in four SGPRs, ONE VGPR of per-lane byte offset and the immediate 64 m -- no 64-bit address arithmetic on the
-// vector ALU (the global-load form spent 13 v_lshl_add_u64 and 26 address VGPRs per pass on it), and the hardware's range check
-// replaces the clamped-address branch: a read behind the end of the buffer (or in front of it: the offset wraps to a huge unsigned
+// vector ALU (global loads spent 13 v_lshl_add_u64 and 26 address VGPRs per pass on it), and the hardware's range check
+// replaces a clamped-address branch: a read behind the end of the buffer (or in front of it: the offset wraps to a huge unsigned
 // value) returns zero, which is as good as the clamped sample -- such samples meet a zero of the window table or belong to a frame
-// that is not stored. -DSMILEHIP_MFCC512_GLOBAL_LOADS builds the round-5 form (A/B aid).
-template <int MP, bool ALIGNED, bool PREEMPH, bool TYPED>
+// that is not stored.
+template <int MP, bool ALIGNED, bool TYPED>
 __device__ __forceinline__ void pcm_prefetch(const int16_t *pcm, int64_t pcm_total, int64_t base, int H, int lane,
-                                             FrameRegs<MP, ALIGNED, PREEMPH, TYPED> &R) {
-#ifndef SMILEHIP_MFCC512_GLOBAL_LOADS
+                                             FrameRegs<MP, ALIGNED, TYPED> &R) {
   const int64_t b0 = base < 0 ? 0 : base;                // (negative only for the buffer's first frames under symmetric zero padding)
   int64_t left = (pcm_total - b0) * 2;                   // bytes behind the descriptor's base
   left = left < 0 ? 0 : (left > 0xfffffffcLL ? 0xfffffffcLL : left);
@@ -327,12 +259,8 @@ __device__ __forceinline__ void pcm_prefetch(const int16_t *pcm, int64_t pcm_tot
                                                                         TYPED ? kRsrcWord3Typed : kRsrcWord3);
   uint32_t lo = ((uint32_t)(lane >> 4) * (uint32_t)H + 2u * (uint32_t)(lane & 15)) * 2u + (uint32_t)((base - b0) * 2);
   asm volatile("" : "+v"(lo));                           // opaque per call: no hoisted per-m offset registers
-  uint32_t lo_p = lo - 2u;                               // the predecessor of pair 0 (m = 0 only: the immediate offset is unsigned)
-  if (PREEMPH && kPredLoads) asm volatile("" : "+v"(lo_p));
 #pragma unroll
   for (int m = 0; m < MP; ++m) {
-    if (PREEMPH && kPredLoads)
-      R.p[m] = (uint32_t)(int32_t)(int16_t)__builtin_amdgcn_raw_buffer_load_b16(rsrc, m == 0 ? (int)lo_p : (int)lo + 64 * m - 2, 0, 0);
     if constexpr (TYPED && ALIGNED) {
       const float2v f = tbuffer_load_xy(rsrc, (int)lo + 64 * m, 0, kFmt16x2Sscaled, 0);
       R.v[2 * m] = __float_as_uint(f.x);
@@ -340,71 +268,17 @@ __device__ __forceinline__ void pcm_prefetch(const int16_t *pcm, int64_t pcm_tot
     } else if constexpr (TYPED) {
       R.v[2 * m] = __float_as_uint(tbuffer_load_x(rsrc, (int)lo + 64 * m, 0, kFmt16Sscaled, 0));
       R.v[2 * m + 1] = __float_as_uint(tbuffer_load_x(rsrc, (int)lo + 64 * m + 2, 0, kFmt16Sscaled, 0));
-    } else if (ALIGNED && !kB16Samples) {
+    } else if constexpr (ALIGNED) {
       R.v[m] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)lo + 64 * m, 0, 0);
     } else {
       R.v[2 * m] = (uint32_t)(int32_t)(int16_t)__builtin_amdgcn_raw_buffer_load_b16(rsrc, (int)lo + 64 * m, 0, 0);
       R.v[2 * m + 1] = (uint32_t)(int32_t)(int16_t)__builtin_amdgcn_raw_buffer_load_b16(rsrc, (int)lo + 64 * m + 2, 0, 0);
     }
   }
-#else
-#ifdef SMILEHIP_DEBUG_SAME_SPAN
-  base &= 0xfffff;                                       // experiment: every span inside the first 2 MB (L2 resident)
-#endif
-  uint32_t lo = ((uint32_t)(lane >> 4) * (uint32_t)H + 2u * (uint32_t)(lane & 15)) * 2u;
-  asm volatile("" : "+v"(lo));                           // opaque per call: no hoisted per-m offset registers
-#ifdef SMILEHIP_DEBUG_NO_LOADS
-  for (int m = 0; m < (ALIGNED ? MP : 2 * MP); ++m) R.v[m] = lo * (m + 3);      // experiment: no global loads at all
-  return;
-#endif
-  const unsigned char *span = reinterpret_cast<const unsigned char *>(pcm + base);
-  const int64_t room = pcm_total - base;
-  if (base >= 0 && room >= (int64_t)(3 * H + 32 * MP)) {
-#pragma unroll
-    for (int m = 0; m < MP; ++m) {
-      const unsigned char *q = span + 64 * m + lo;
-      if (ALIGNED) {
-        R.v[m] = *reinterpret_cast<const uint32_t *>(q);
-      } else {
-        R.v[2 * m] = (uint32_t)(int32_t) reinterpret_cast<const int16_t *>(q)[0];
-        R.v[2 * m + 1] = (uint32_t)(int32_t) reinterpret_cast<const int16_t *>(q)[1];
-      }
-    }
-  } else {
-    const int64_t last = ALIGNED ? ((pcm_total >> 1) - 1) * 2 : pcm_total - 2;     // last index with a whole pair behind it
-    const int32_t lim_lo = base < 0 ? (int32_t)(-base) * 2 : 0;
-    int64_t hi64 = (last - base) * 2;
-    hi64 = hi64 > (1 << 24) ? (1 << 24) : hi64;
-    const int32_t lim_hi = hi64 < lim_lo ? lim_lo : (int32_t)hi64;
-#pragma unroll
-    for (int m = 0; m < MP; ++m) {
-      int32_t off = (int32_t)lo + 64 * m;
-      off = off < lim_lo ? lim_lo : (off > lim_hi ? lim_hi : off);
-      const unsigned char *q = span + off;
-      if (ALIGNED) {
-        R.v[m] = *reinterpret_cast<const uint32_t *>(q);
-      } else {
-        R.v[2 * m] = (uint32_t)(int32_t) reinterpret_cast<const int16_t *>(q)[0];
-        R.v[2 * m + 1] = (uint32_t)(int32_t) reinterpret_cast<const int16_t *>(q)[1];
-      }
-    }
-  }
-#endif
 }
 
-// Developer instrumentation (tools/ubench/variant.sh builds a private copy of the library
-// with -DSMILEHIP_PHASE_TIMING): s_memtime at the phase boundaries of the pass loop, summed
-// over all waves. Not compiled into the product.
-#ifdef SMILEHIP_PHASE_TIMING
-__device__ unsigned long long g_phase[16];
-#define PHASE_DECL unsigned long long ph_acc[12] = {0}; unsigned long long ph_last = __builtin_amdgcn_s_memtime();
-#define PHASE(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); ph_acc[i] += t_ - ph_last; ph_last = t_; } while (0)
-#define PHASE_FLUSH do { if (lane == 0) for (int i_ = 0; i_ < 12; ++i_) atomicAdd(&g_phase[i_], ph_acc[i_]); } while (0)
-#else
-#define PHASE_DECL
-#define PHASE(i)
-#define PHASE_FLUSH
-#endif
+// the phases of the pass loop (phase_timing.hpp; tools/ubench/variant.sh phase -DSMILEHIP_PHASE_TIMING, tools/ubench/phase_timing.py)
+SMILEHIP_PHASE_COUNTERS(g_phase, 16, smilehip_debug_phase)
 
 // LDS layout (dynamic), sizes in floats:
 //   shared tables : tw512 [256 f2] | win [MP*16 f2] | tw256 [256 f2, index k1*16+j] |
@@ -480,7 +354,7 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
   float *pb_m = s_pb + pb_pos(256 - j);        // their mirror images 256 - k sit 24 q floats back
 
   const Dft16K dk;
-  PHASE_DECL
+  PhaseTimer<12> PH;
   // Persistent waves walk tiles tile, tile + #waves, ... as ONE flat stream of passes: the
   // next pass's PCM (same tile or the first pass of the next tile) is always in flight, tile
   // records are fetched one tile ahead, and a pass's results are stored at the top of the
@@ -510,8 +384,8 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
   if (has_next) nxt_samp0 = recs[tile + tile_stride].samp0;
   int tp = 0;                                          // first frame of the pass, relative to the tile
   constexpr bool TYPED = typed_loads<MP, PLP, DELTA>();
-  FrameRegs<MP, ALIGNED, PREEMPH, TYPED> R;
-  pcm_prefetch<MP, ALIGNED, PREEMPH, TYPED>(P.pcm, P.pcm_total, cur_samp0 - P.pad_left, P.H, lane, R);
+  FrameRegs<MP, ALIGNED, TYPED> R;
+  pcm_prefetch<MP, ALIGNED, TYPED>(P.pcm, P.pcm_total, cur_samp0 - P.pad_left, P.H, lane, R);
   unsigned char *pend_row = nullptr;                   // deferred store of the previous pass (wave-uniform row base)
   float pend_val = 0.0f;
   bool pend_live = false;
@@ -570,7 +444,7 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
 
   for (;;) {
     const bool live = tp + g < (DELTA ? cur_live : cur_n);
-    PHASE(0);                                   // loop overhead
+    PH(0);                                   // loop overhead
     // ------------------------------------------------------------ frame from registers: R0 (scale folded), R2, R3
     if constexpr (!DELTA) {
       if (pend_row != nullptr && pend_live) {     // previous pass's coefficients
@@ -595,7 +469,7 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
           if constexpr (TYPED) {                   // converted by the buffer unit
             a = __uint_as_float(R.v[2 * m]);
             b = __uint_as_float(R.v[2 * m + 1]);
-          } else if constexpr (ALIGNED && !kB16Samples) {
+          } else if constexpr (ALIGNED) {
             a = (float)(int16_t)(R.v[m] & 0xffffu);
             b = (float)(int16_t)(R.v[m] >> 16);
           } else {
@@ -604,26 +478,16 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
           }
           float ya = a, yb = b;
           if (PREEMPH) {
-            float pa;
-            if constexpr (kPredLoads) {
-              pa = (float)(int32_t)R.p[m];         // x[2n - 1] (SMILEHIP_MFCC512_PRED_LOADS)
-            } else {
-              const float t = dpp_f<0x121>(b);     // row_ror:1 -- lane j sees the odd sample of pair j-1 (lane 0: of lane 15)
-              pa = (j == 0) ? tprev : t;
-              tprev = t;
-            }
-#ifndef SMILEHIP_MFCC512_PREEMPH_TWO_ROUNDINGS
-            // (round 6) one rounding where the reference has two (preemphasis.cpp: x - k x' as a product and a difference): 26 vector
+            const float t = dpp_f<0x121>(b);       // row_ror:1 -- lane j sees the odd sample of pair j-1 (lane 0: of lane 15)
+            const float pa = (j == 0) ? tprev : t;   // x[2n - 1]
+            tprev = t;
+            // One rounding where the reference has two (preemphasis.cpp: x - k x' as a product and a difference): 26 vector
             // instructions fewer per pass, 0.3745 -> 0.3665 ms per 998 000 frames, and the distance to the reference went DOWN
             // (per-frame-scaled 1.048e-6 -> 1.041e-6, max abs 1.56e-4 -> 1.49e-4: the fused form is the exact difference rounded once).
             // This kernel's contract is the 1e-5 gate; the reference's own rounding sequence is lld_mfcc_generic's.
-            // (round 7) yb first: then both are v_fmac (the addend is the destination, -k an SGPR operand), no VOP3 v_fma_f32.
+            // yb first: then both are v_fmac (the addend is the destination, -k an SGPR operand), no VOP3 v_fma_f32.
             yb = fmaf(nkpre, a, b);
             ya = fmaf(nkpre, pa, a);
-#else
-            yb = b + nkpre * a;
-            ya = a + nkpre * pa;
-#endif
             if (PAD0 ? (m == 0 && j == 0) : (m == m0 && j == j0)) ya = P.one_minus_k * a;      // y[0] = (1-k) x[0]
           }
           const float2 w = s_win[m * 16 + j];
@@ -634,7 +498,7 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
         }
       }
     }
-    PHASE(1);                                   // wait for the prefetch, pre-emphasis, window
+    PH(1);                                   // wait for the prefetch, pre-emphasis, window
     if constexpr (DELTA) {
       // (first pass of a wave: the tile constants are zero, nothing is written)
       const bool clamped = !(b_tp - 6 >= b_lo && b_tp + 3 <= b_live - 1);
@@ -670,12 +534,12 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
     // bank-conflict free with immediate offsets only (tools/lds_bank_sim.py).
     float2 *tbw = reinterpret_cast<float2 *>(wbase) + g * 16 + j;
     const float2 *tbr = reinterpret_cast<const float2 *>(wbase) + g * 16 + j * kTB2Row;
-    if constexpr (kWritesEarly) {
-      // (round 8) The last layer of the DFT hands out final values group by group -- q = 0 gives k1 = 0, 4, 8, 12 -- so the twiddle
+    {
+      // The last layer of the DFT hands out final values group by group -- q = 0 gives k1 = 0, 4, 8, 12 -- so the twiddle
       // product and the ds_write_b64 of an index follow its dft4 at once: the sixteen writes are spread over the last layer and the
-      // twiddles instead of standing in one block in front of the reads. The twiddle pairs of group q + 1 are requested before group
-      // q's last layer (those of group 0 before the whole DFT): no table read stands behind a transposition write that the compiler
-      // cannot tell apart from it, and each has ~30 vector instructions to arrive in.
+      // twiddles instead of standing in one block in front of the reads (0.3808 -> 0.3756 ms per bench step). The twiddle pairs of
+      // group q + 1 are requested before group q's last layer (those of group 0 before the whole DFT): no table read stands behind a
+      // transposition write that the compiler cannot tell apart from it, and each has ~30 vector instructions to arrive in.
       float2 w[4], wn[4];
 #pragma unroll
       for (int p = 1; p < 4; ++p) w[p] = s_tw256[(4 * p) * 16 + j];
@@ -699,34 +563,21 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
 #pragma unroll
         for (int p = 0; p < 4; ++p) w[p] = wn[p];
       }
-    } else {
-      dft16(re, im, dk);                                       // over m  -> index k1
-#pragma unroll
-      for (int k1 = 1; k1 < 16; ++k1) {
-        const float2 w = s_tw256[k1 * 16 + j];
-        cmul(re[k1], im[k1], w.x, w.y);
-      }
-#pragma unroll
-      for (int k1 = 0; k1 < 16; ++k1) tbw[k1 * kTB2Row] = make_float2(re[k1], im[k1]);
     }
-    PHASE(3);                                   // dft16 + twiddles (+ transposition writes)
+    PH(3);                                   // dft16 + twiddles (+ transposition writes)
     {
       wave_lds_fence();
-      // (SMILEHIP_MFCC512_READS_IN_DFT_ORDER: in the order in which the second DFT's first layer takes them, see the switch)
 #pragma unroll
-      for (int i = 0; i < 16; ++i) {             // one ds_read_b64 each (2 LDS cycles); paired into ds_read2_b64 they would take 8 per pair
-        const int jj = kReadsInDftOrder ? (i >> 2) + 4 * (i & 3) : i;
+      for (int jj = 0; jj < 16; ++jj) {          // one ds_read_b64 each (2 LDS cycles); paired into ds_read2_b64 they would take 8 per pair
         typedef const volatile __attribute__((address_space(3))) unsigned long long *LdsU64;
         const unsigned long long v = ((LdsU64)tbr)[jj];
         re[jj] = __int_as_float((int)(uint32_t)v); im[jj] = __int_as_float((int)(uint32_t)(v >> 32));
       }
       wave_lds_fence();
     }
-    PHASE(4);                                   // transposes
-#ifndef SMILEHIP_DEBUG_SKIP_DFT2
+    PH(4);                                   // transposes
     dft16(re, im, dk);                                       // over j -> k2 ; Z[j + 16 k2]
-#endif
-    PHASE(5);                                   // second dft16
+    PH(5);                                   // second dft16
 
     // ------------------------------------------------------------ untangle pairs + power
     // The partner of lane j is lane (16 - j) & 15 of the same row, reached without an LDS round trip: shift the row one
@@ -734,34 +585,15 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
     // register up (bin 256 - 16 q = 0 + 16 (16 - q)): its value is parked in lane 15 first (row_ror:15), where the shift
     // has no source and leaves it. q = 0 of lane 0 is the DC/Nyquist pair, handled below.
     float zr[8], zi[8];
-#ifdef SMILEHIP_MFCC512_BPERMUTE_PARTNER
-    // (round 6, measured and NOT taken) ... through the LDS crossbar instead (ds_bpermute: no storage): one crossbar read + one
-    // select (lane 0 is its own partner one register up) where the DPP route takes three vector instructions per value -- 33 fewer
-    // VALU instructions per pass (905 -> 872; replayed VALU stream 0.343 -> 0.314 ms per 998 000 frames), but the launch got SLOWER,
-    // 0.3773 -> 0.3830 ms: sixteen more LDS-pipe instructions per pass cost more than the vector instructions they replace.
-    {
-      const int paddr = 4 * ((lane & 48) | ((16 - j) & 15));
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        float c = __int_as_float(__builtin_amdgcn_ds_bpermute(paddr, __float_as_int(re[15 - q])));
-        float d = __int_as_float(__builtin_amdgcn_ds_bpermute(paddr, __float_as_int(im[15 - q])));
-        if (q > 0) { c = (j == 0) ? re[16 - q] : c; d = (j == 0) ? im[16 - q] : d; }
-        zr[q] = c; zi[q] = d;
-      }
-    }
-#else
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const float pr = q > 0 ? dpp_f<0x12f>(re[(16 - q) & 15]) : re[15];
       const float pi = q > 0 ? dpp_f<0x12f>(im[(16 - q) & 15]) : im[15];
       const float tr = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(pr), __float_as_int(re[15 - q]), 0x101, 0xf, 0xf, false));
       const float ti = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(pi), __float_as_int(im[15 - q]), 0x101, 0xf, 0xf, false));
-      // (SMILEHIP_MFCC512_MIRROR_OPERAND: the row_mirror step is taken next to its four additions below and zr / zi hold the
-      // shifted values until then)
-      zr[q] = kMirrorOperand ? tr : dpp_f<0x140>(tr);
-      zi[q] = kMirrorOperand ? ti : dpp_f<0x140>(ti);
+      zr[q] = dpp_f<0x140>(tr);
+      zi[q] = dpp_f<0x140>(ti);
     }
-#endif
     float2 tw5[8];                                // e^{-2 pi i k/512} of my eight bins, all read before the first store to the
 #pragma unroll                                    // power buffer (the compiler cannot tell the two LDS regions apart)
     for (int q = 0; q < 8; ++q) tw5[q] = s_tw512[j + 16 * q];
@@ -769,7 +601,7 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
     for (int q = 0; q < 8; ++q) {
       const float2 w = tw5[q];
       const float a = re[q], b = im[q];
-      const float c = kMirrorAtUse ? dpp_f<0x140>(zr[q]) : zr[q], d = kMirrorAtUse ? dpp_f<0x140>(zi[q]) : zi[q];
+      const float c = zr[q], d = zi[q];
       const float sr = a + c, si = b - d, dr = a - c, di = b + d;
       const float ur = fmaf(w.x, dr, -w.y * di);
       const float ui = fmaf(w.x, di, w.y * dr);
@@ -794,7 +626,7 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
     }
     wave_lds_fence();
 
-    PHASE(6);                                   // untangle + power
+    PH(6);                                   // untangle + power
     // next pass's PCM: issued here, where register pressure is low; the loads fly
     // during mel/DCT of this pass and the other resident waves' arithmetic
     int ntp = tp + 4;
@@ -802,15 +634,15 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
     const bool more = !advance || has_next;
     if (advance) ntp = 0;
     if (more)
-      pcm_prefetch<MP, ALIGNED, PREEMPH, TYPED>(P.pcm, P.pcm_total, (advance ? nxt_samp0 : cur_samp0) + (int64_t)ntp * P.H - P.pad_left, P.H, lane, R);
+      pcm_prefetch<MP, ALIGNED, TYPED>(P.pcm, P.pcm_total, (advance ? nxt_samp0 : cur_samp0) + (int64_t)ntp * P.H - P.pad_left, P.H, lane, R);
     else if constexpr (TYPED) {
       // the wave's last pass (it leaves the loop below): the samples must not stay alive up to here on THIS path
-      // either (see kTypedLoads). Not on the steady path.
+      // either (see typed_loads). Not on the steady path.
 #pragma unroll
       for (int m = 0; m < 2 * MP; ++m) R.v[m] = 0u;
     }
 
-    PHASE(7);                                   // prefetch issue
+    PH(7);                                   // prefetch issue
     // ------------------------------------------------------------ mel (R6)
     {
       float a0 = 0.0f, a1 = 0.0f;                 // my two bands; a band's units are added in unit order, starting from 0
@@ -825,7 +657,7 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
         a0 = fmaf(acc, uf0[i], a0);
         a1 = fmaf(acc, uf1[i], a1);
       }
-      PHASE(8);                                   // mel units
+      PH(8);                                   // mel units
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const int b = h ? band1 : band0;
@@ -845,7 +677,7 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
     }
     wave_lds_fence();
 
-    PHASE(9);                                   // band sums + log
+    PH(9);                                   // band sums + log
     // ------------------------------------------------------------ PLP-CC (R8): IDFT rows (s_dct holds the cosine
     // table, same 28-float rows), then Durbin + cepstra + lifter on the group's lane 0
     if (PLP) {
@@ -873,7 +705,7 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
     pend_row = reinterpret_cast<unsigned char *>(P.out + (cur_row0 + tp - (DELTA ? 4 : 0)) * P.ld_out);   // wave-uniform
     if constexpr (DELTA) { b_tp = tp; b_lo = cur_lo; b_live = cur_live; b_e0 = cur_e0; b_e1 = cur_e1; b_don = cur_don; }
     wave_lds_fence();   // band vector and power buffer are overwritten by the next pass's transpose
-    PHASE(10);                                  // DCT
+    PH(10);                                  // DCT
     if (!more) break;
     if (advance) {
       tile += tile_stride;
@@ -902,7 +734,7 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
     asm volatile("" : "+v"(oo));
     *reinterpret_cast<float *>(pend_row + oo) = pend_val;
   }
-  PHASE_FLUSH;
+  PH.flush(g_phase);
 }
 
 template <int MP, bool PREEMPH, bool USE_POWER, bool ALIGNED, bool PLP, int UC, bool DELTA = false>
@@ -913,17 +745,6 @@ template <int MP, bool PREEMPH, bool USE_POWER, bool ALIGNED, bool PLP, int UC, 
 __global__ void __launch_bounds__(kWavesPerBlock * 64, 4) lld_mfcc512_padded(LldParams P, Fast512Tables F) {
   lld_mfcc512_body<MP, PREEMPH, USE_POWER, ALIGNED, PLP, UC, DELTA, false>(P, F);
 }
-
-#ifdef SMILEHIP_PHASE_TIMING
-extern "C" int smilehip_debug_phase(unsigned long long *out16, int reset) {
-  if (out16 && hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_phase), sizeof(unsigned long long) * 16) != hipSuccess) return -1;
-  if (reset) {
-    unsigned long long z[16] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_phase), z, sizeof(z)) != hipSuccess) return -1;
-  }
-  return 0;
-}
-#endif
 
 // ---------------------------------------------------------------------------
 // host side

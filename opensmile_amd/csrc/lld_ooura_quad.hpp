@@ -22,12 +22,10 @@
 
 #include "lld_ooura_wave.hpp"
 
-// OO_QUAD_BF_FENCE: a scheduling fence behind every butterfly (two butterflies' operands and twiddles in flight instead of four)
-#ifndef OO_QUAD_BF_FENCE
-#define OO_QUAD_BF_FENCE __builtin_amdgcn_sched_barrier(0)
-#endif
-
 namespace smilehip {
+
+// a scheduling fence behind every butterfly (two butterflies' operands and twiddles in flight instead of four)
+__device__ __forceinline__ void oo_quad_bf_fence() { __builtin_amdgcn_sched_barrier(0); }
 
 constexpr int kQuadXRow = 17;                               // pairs per line of a row's 16 x 16 transposition: lane j reads line j --
                                                             // 17 pairs apart, sixteen different bank pairs
@@ -42,10 +40,10 @@ __device__ __forceinline__ void oo_quad256(float2 (&v)[16], const OouraTab &T, f
   const int j = lane & 15;
   // L0, q = 64: node 0, butterfly s works on e = c + {0, 64, 128, 192}, c = 16 s + j -> registers s, s + 4, s + 8, s + 12
 #pragma unroll
-  for (int s = 0; s < 4; ++s) { oo_level_bf<BWD>(v[s], v[4 + s], v[8 + s], v[12 + s], T, 0, 64, 0, 0u, 16 * s + j); OO_QUAD_BF_FENCE; }
+  for (int s = 0; s < 4; ++s) { oo_level_bf<BWD>(v[s], v[4 + s], v[8 + s], v[12 + s], T, 0, 64, 0, 0u, 16 * s + j); oo_quad_bf_fence(); }
   // L1, q = 16: node k = (e7 e6), c = j: e = 64 k + j + {0, 16, 32, 48} -> registers 4 k + {0, 1, 2, 3}
 #pragma unroll
-  for (int k = 0; k < 4; ++k) { oo_level_bf<false>(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3], T, 1, 16, 64, (unsigned)k, j); OO_QUAD_BF_FENCE; }
+  for (int k = 0; k < 4; ++k) { oo_level_bf<false>(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3], T, 1, 16, 64, (unsigned)k, j); oo_quad_bf_fence(); }
   // 16 x 16 transposition inside the row: element (register r, lane j) -> (register j, lane r): e = 16 j + r
   {
     float2 *xw = zx + j;
@@ -59,10 +57,10 @@ __device__ __forceinline__ void oo_quad256(float2 (&v)[16], const OouraTab &T, f
   }
   // L2, q = 4: node j (e7 .. e4), butterfly c works on e = 16 j + c + {0, 4, 8, 12} -> registers c, c + 4, c + 8, c + 12
 #pragma unroll
-  for (int c = 0; c < 4; ++c) { oo_level_bf<false>(v[c], v[4 + c], v[8 + c], v[12 + c], T, 2, 4, 112, (unsigned)j, c); OO_QUAD_BF_FENCE; }
+  for (int c = 0; c < 4; ++c) { oo_level_bf<false>(v[c], v[4 + c], v[8 + c], v[12 + c], T, 2, 4, 112, (unsigned)j, c); oo_quad_bf_fence(); }
   // L3, q = 1: node 4 j + m, e = 16 j + 4 m + {0, 1, 2, 3} -> registers 4 m + {0, 1, 2, 3}
 #pragma unroll
-  for (int m = 0; m < 4; ++m) { oo_level_bf<false>(v[4 * m], v[4 * m + 1], v[4 * m + 2], v[4 * m + 3], T, 3, 1, 0, (unsigned)(4 * j + m), 0); OO_QUAD_BF_FENCE; }
+  for (int m = 0; m < 4; ++m) { oo_level_bf<false>(v[4 * m], v[4 * m + 1], v[4 * m + 2], v[4 * m + 3], T, 3, 1, 0, (unsigned)(4 * j + m), 0); oo_quad_bf_fence(); }
 }
 
 // v[r] (spectrum index 16 bitrev4(r) + bitrev4(j)) -> z[oo_pos(F)], z = the row's buffer. Ends with a wave sync.

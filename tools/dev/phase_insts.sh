@@ -1,8 +1,9 @@
 #!/bin/bash
 # usage: tools/dev/phase_insts.sh <file.hip> <mangled-name prefix> [MACRO] [extra hipcc flags]: static instruction counts of one kernel between
-# the phase markers of its body (the IPHASE / CPHASE ... macros compiled as assembler comments; the loops are unrolled, so
-# static = dynamic per pass up to the predicated regions). CPU only: what a change does to the instruction count before a GPU run.
-F=$1; K=$2; M=${3:-IPHASE}; shift; shift; [ $# -gt 0 ] && shift
+# the phase markers of its body (a marker macro with an empty definition, such as lld_compare_quad.hpp's QPHASE, compiled as assembler
+# comments; the loops are unrolled, so static = dynamic per pass up to the predicated regions). CPU only: what a change does to the
+# instruction count before a GPU run.
+F=$1; K=$2; M=${3:-QPHASE}; shift; shift; [ $# -gt 0 ] && shift
 cd "$(dirname "$0")/../../opensmile_amd/csrc" || exit 1
 sed "s|^#define $M(i)\$|#define $M(i) asm volatile(\"; PHASEMARK \" #i)|" $F > _tmp_mark.hip
 # (a marker macro defined in a header the file includes behind an #ifndef: the forced include defines it first)

@@ -6,8 +6,8 @@ a b128 access per group of 16 lanes). Prints the extra (conflict) cycles per DS 
 The transposition is modelled per instruction and in issue order (`transposition`): an instruction's lane -> bank pattern depends
 on its own row / column index only, so the ORDER in which the sixteen stores and the sixteen loads are issued cannot change the
 conflict count -- the function checks that and returns the count for any order (since round 8 the stores are issued in the order of
-the first DFT's last layer, TRANSPOSE_ORDER_R8, and the loads can be, -DSMILEHIP_MFCC512_READS_IN_DFT_ORDER; the parent commit issued
-both in index order)."""
+the first DFT's last layer, TRANSPOSE_ORDER_R8; the loads in that order too were measured and are no gain; before
+round 8 both were issued in index order)."""
 import numpy as np
 
 MP, UC = 13, 6                       # the bench's instance
