@@ -794,6 +794,54 @@ int smilehip_spectral_op_n_out(const smilehip_spectral_op *op);
 int smilehip_spectral_op_frames(smilehip_spectral_op *op, const float *d_mag, int64_t ld_src, float *d_state, int first,
                                 float *d_dst, int64_t ld_dst, int64_t n_frames, void *stream);
 int smilehip_spectral_op_destroy(smilehip_spectral_op *op);
+/* R11 on any spectrum: cSpectral::processVector (spectral.cpp:586-1555) with the options smilehip_spectral_opts leaves at their
+ * shipped values, on K = 4 .. 8193 bins of any level -- an FFT magnitude or power spectrum or what cSpecScale makes of one. `base`:
+ * as above. Output order (setupNamesForField, :378-583): bands, slopes, alphaRatio, hammarbergIndex, rollOff, specDiff, specPosDiff,
+ * flux, fluxCentroid, fluxAtFluxCentroid, centroid, maxPos, minPos, entropy, standardDeviation, variance, skewness, kurtosis, slope,
+ * sharpness, harmonicity, flatness.
+ *   square_input        squareInput (:661-688): 1 = the rows are magnitudes (srcP = src^2), 0 = powers (srcM = sqrt(src) where src > 0,
+ *                       else 0). All three require* flags are raised by the constructor (:87) and never lowered (:200-375), so the
+ *                       log spectrum always comes from srcP with the factor (FLOAT_DMEM)(10 / ln 10) (:689-716)
+ *   use_log_spectrum,   useLogSpectrum / specFloor (:228-237, :708-716): slopes, centroid, extremes, entropy, moments, slope,
+ *   spec_floor          harmonicity and flatness from 10 log10 of the powers, floored where srcP <= (FLOAT_DMEM)specFloor^2; band
+ *                       energies in dB (:859-861)
+ *   norm_band_energies  normBandEnergies (:849-856 band / frame energy, :1093-1094, :1502-1511 harmonicity over the frame's sum)
+ *   alpha_ratio,        alphaRatio / hammarbergIndex (:995-1089), in dB under the log spectrum
+ *   hammarberg_index
+ *   old_slope_scale     oldSlopeScale (:987-991, :1422-1426): 1 = slope * (Nind - 1)
+ *   buggy_roll_off      buggyRollOff (:1104-1118)
+ *   freq_lo, freq_hi    freqRange in Hz (:625-647; 0-0 = bins 1 .. K-1); another range needs the axis
+ *   frq_scale,          the writer level's SCALED_SPEC meta data as :614-623 reads it (SMILEHIP_SPECSCALE_*; linear where the level
+ *   frq_scale_param     has none): the scale the sharpness weights undo before they go to Bark (:1438-1457)
+ *   tonality            must be 0 (the reference prints an error and writes 0)
+ * frq / n_scale (smilehip_spectral_axis_op_create): the level's frequency axis, host doubles (FrameMetaInfo::field[].info, :595-612);
+ * with it every `(nScale >= Nsrc) && frq != NULL` branch applies, without it (frq = NULL, n_scale = 0) the index-based ones.
+ * d_state / first: as for smilehip_spectral_op_frames (K floats: the last frame's ROW as it came in). One thread per frame, every
+ * sum the reference's own sequential chain, each lane walking its own row (the slopes[] sums: a column of LDS per lane). */
+typedef struct smilehip_spectral_axis_opts {
+  smilehip_spectral_opts base;
+  int32_t square_input, use_log_spectrum, norm_band_energies, alpha_ratio, hammarberg_index, old_slope_scale, buggy_roll_off, tonality;
+  double  spec_floor;
+  int32_t freq_lo, freq_hi;
+  int32_t frq_scale, reserved;
+  double  frq_scale_param;
+} smilehip_spectral_axis_opts;
+typedef struct smilehip_spectral_axis_op smilehip_spectral_axis_op;
+int smilehip_spectral_axis_opts_count(const smilehip_spectral_axis_opts *opts);     /* outputs per frame, -1 if out of range */
+/* The data-independent setup alone, on the host (no device): range bins (:625-647), band and slope edge bins and weights in both
+ * forms (:771-840, :873-946), the slope's axis sums (:1400-1418), the alpha-ratio / Hammarberg bin classes, the sharpness weights
+ * (:1438-1468; smileUtil.c:1064-1199). geo (12 int32): lo bin, hi bin, has axis, alpha n1, alpha stop, hammarberg n1, hammarberg
+ * stop, 0...; edges (n_bands + n_slopes rows of 5 doubles): iL, iR, wL, wR, idxR - idxL; sums (2): Sf, S2f; sharp (hi - lo + 1).
+ * Any of the output pointers may be NULL. Returns the number of outputs per frame, or a negative SMILEHIP_ERR_* with
+ * smilehip_last_error naming the option. */
+int smilehip_spectral_axis_tables(const smilehip_spectral_axis_opts *opts, int64_t K, double frame_size_sec, const double *frq,
+                                  int64_t n_scale, int32_t *geo, double *edges, double *sums, double *sharp);
+int smilehip_spectral_axis_op_create(smilehip_context *ctx, const smilehip_spectral_axis_opts *opts, int64_t K, double frame_size_sec,
+                                     const double *frq, int64_t n_scale, smilehip_spectral_axis_op **op);
+int smilehip_spectral_axis_op_n_out(const smilehip_spectral_axis_op *op);
+int smilehip_spectral_axis_op_frames(smilehip_spectral_axis_op *op, const float *d_src, int64_t ld_src, float *d_state, int first,
+                                     float *d_dst, int64_t ld_dst, int64_t n_frames, void *stream);
+int smilehip_spectral_axis_op_destroy(smilehip_spectral_axis_op *op);
 /* R8: cPlp::processVector as auditory spectrum (doAud = 1, doIDFT = doLP = 0; plp.cpp:416-593). d_eql: the
  * equal-loudness weights of the bands (their logs when new_rasta, plp.cpp:335-357), as cPlp::initTables
  * derives them from the input level's band-centre metadata. new_rasta: rasta_coef (host) = {iir, fir[0..4]}

@@ -112,6 +112,29 @@ def spectral_opts(bands, rolloff=(0.25, 0.5, 0.75, 0.9), slopes=(), **flags):
     return o
 
 
+class SpectralAxisOpts(C.Structure):
+    """smilehip_spectral_axis_opts (include/smilehip.h): cSpectral on any spectrum"""
+    _fields_ = [("base", SpectralOpts)] + [(k, C.c_int32) for k in ("square_input", "use_log_spectrum", "norm_band_energies", "alpha_ratio",
+                                                                     "hammarberg_index", "old_slope_scale", "buggy_roll_off", "tonality")] + [
+                   ("spec_floor", C.c_double), ("freq_lo", C.c_int32), ("freq_hi", C.c_int32), ("frq_scale", C.c_int32),
+                   ("reserved", C.c_int32), ("frq_scale_param", C.c_double)]
+
+
+def spectral_axis_opts(bands=(), rolloff=(), slopes=(), square_input=1, use_log_spectrum=0, norm_band_energies=0, alpha_ratio=0,
+                       hammarberg_index=0, old_slope_scale=1, buggy_roll_off=0, tonality=0, spec_floor=0.0000001, freq_range=(0, 0),
+                       frq_scale=0, frq_scale_param=0.0, **flags):
+    """the component's defaults for the options of the axis operator; **flags: the fields of smilehip_spectral_opts"""
+    o = SpectralAxisOpts()
+    o.base = spectral_opts(bands, rolloff, slopes, **flags)
+    o.square_input, o.use_log_spectrum, o.norm_band_energies = int(square_input), int(use_log_spectrum), int(norm_band_energies)
+    o.alpha_ratio, o.hammarberg_index, o.old_slope_scale = int(alpha_ratio), int(hammarberg_index), int(old_slope_scale)
+    o.buggy_roll_off, o.tonality, o.spec_floor = int(buggy_roll_off), int(tonality), float(spec_floor)
+    o.freq_lo, o.freq_hi = int(freq_range[0]), int(freq_range[1])
+    o.frq_scale = SPECSCALE[frq_scale] if isinstance(frq_scale, str) else int(frq_scale)
+    o.frq_scale_param = float(frq_scale_param)
+    return o
+
+
 class SpecScaleOpts(C.Structure):
     """smilehip_specscale_opts (include/smilehip.h): cSpecScale on any target scale"""
     _fields_ = [("scale", C.c_int32), ("param", C.c_double), ("min_f", C.c_double), ("max_f", C.c_double), ("n_points_target", C.c_int32),
@@ -256,6 +279,12 @@ SYMBOLS = {
     "smilehip_spectral_op_n_out": (C.c_int, [_vp]),
     "smilehip_spectral_op_frames": (C.c_int, [_vp, _vp, _i64, _vp, C.c_int, _vp, _i64, _i64, _vp]),
     "smilehip_spectral_op_destroy": (C.c_int, [_vp]),
+    "smilehip_spectral_axis_opts_count": (C.c_int, [_vp]),
+    "smilehip_spectral_axis_tables": (C.c_int, [_vp, _i64, C.c_double, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "smilehip_spectral_axis_op_create": (C.c_int, [_vp, _vp, _i64, C.c_double, _vp, _i64, _vp]),
+    "smilehip_spectral_axis_op_n_out": (C.c_int, [_vp]),
+    "smilehip_spectral_axis_op_frames": (C.c_int, [_vp, _vp, _i64, _vp, C.c_int, _vp, _i64, _i64, _vp]),
+    "smilehip_spectral_axis_op_destroy": (C.c_int, [_vp]),
     "smilehip_plp_audspec_frames": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp, C.c_float, C.c_float, C.c_int, _vp, _vp, _vp, _i64,
                                              _i64, _vp]),
     "smilehip_plp_cc_frames": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp, C.c_float, C.c_float, C.c_int, _vp, _vp, _vp, _i64, _i64,

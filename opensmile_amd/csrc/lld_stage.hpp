@@ -92,6 +92,25 @@ hipError_t stage_mfcc_inverse(const float *src, int64_t lds, float *dst, int64_t
                               int do_log, const float *rows, const float *lifter, hipStream_t s);
 hipError_t stage_spectral_general(const SpectralGeneral &G, const float *mag, int64_t ld_src, float *state, int first, float *dst,
                                   int64_t ld_dst, int64_t n_frames, hipStream_t s);
+// cSpectral on any spectrum (lld_spectral_axis.hip): smilehip_spectral_axis_opts and make_spectral_axis_tables, ready to use
+struct SpectralAxisDev {
+  int32_t K, n_out, lo, hi, has_axis;
+  int32_t square_input, use_log, norm_band, alpha_ratio, hammarberg, old_slope_scale, buggy_roll_off;
+  int32_t ar_n1, ar_n2, hb_n1, hb_n2;
+  float spec_floor, log_spec_floor, log_spec_factor;
+  double F0, ln10;                                      // 1 / frameSizeSec; the host's log(10.0)
+  int32_t n_bands, n_slopes, n_rolloff;
+  int32_t iL[32], iR[32];                               // bands[], then slopes[] (make_spectral_axis_tables)
+  double wL[32], wR[32], Nind[32];
+  double rolloff[16];
+  int32_t flux, centroid, max_pos, min_pos, entropy, variance, skewness, kurtosis, slope, sharpness, harmonicity, flatness, log_flatness;
+  int32_t spec_diff, spec_pos_diff, flux_centroid, flux_at_flux_centroid, standard_deviation;
+  double slope_Sf, slope_S2f;
+  const double *ax_c, *ax_m, *ax_s, *sharp_w;          // [K] x 3, [hi - lo + 1]
+  const float *ax_ro;                                   // [K]
+};
+hipError_t stage_spectral_axis(const SpectralAxisDev &G, const float *src, int64_t ld_src, float *state, int first, float *dst,
+                               int64_t ld_dst, int64_t n_frames, hipStream_t s);
 hipError_t stage_plp(const float *src, int64_t lds, int n_bands, const float *eql, const PlpConsts &Q, int rasta, float *state,
                      float *dst, int64_t ldd, int64_t nF, hipStream_t s);
 hipError_t stage_plp_cc(const float *src, int64_t lds, int n_bands, const float *eql, float melfloor, float compression,

@@ -149,6 +149,95 @@ extern "C" int smilehip_spectral_op_frames(smilehip_spectral_op *op, const float
   STAGE_RET(stage_spectral_general(op->G, d_mag, ld_src, d_state, first, d_dst, ld_dst, n_frames, (hipStream_t)stream), "spectral (general)");
 }
 
+// ---- cSpectral on any spectrum (spectral.cpp:586-1555 with the options smilehip_spectral_op_* fixes, and the level's own axis):
+// make_spectral_axis_tables holds everything that follows from the options and the axis
+struct smilehip_spectral_axis_op {
+  smilehip_context *ctx = nullptr;
+  SpectralAxisDev G{};
+  DevBuf<double> d_ax_c, d_ax_m, d_ax_s, d_sharp;
+  DevBuf<float> d_ax_ro;
+};
+extern "C" int smilehip_spectral_axis_op_destroy(smilehip_spectral_axis_op *op) {
+  delete op;
+  return SMILEHIP_OK;
+}
+extern "C" int smilehip_spectral_axis_op_n_out(const smilehip_spectral_axis_op *op) { return op ? op->G.n_out : -1; }
+extern "C" int smilehip_spectral_axis_opts_count(const smilehip_spectral_axis_opts *o) {
+  if (!o) return -1;
+  const int n = smilehip_spectral_opts_count(&o->base);
+  if (n < 0) return -1;
+  return n + (o->alpha_ratio != 0) + (o->hammarberg_index != 0);
+}
+extern "C" int smilehip_spectral_axis_tables(const smilehip_spectral_axis_opts *o, int64_t K, double frame_size_sec, const double *frq,
+                                             int64_t n_scale, int32_t *geo, double *edges, double *sums, double *sharp) {
+  if (!o) return fail(SMILEHIP_ERR_INVALID, "smilehip_spectral_axis_tables: null argument");
+  SpectralAxisHost h;
+  const char *why = "";
+  const int rc = make_spectral_axis_tables(*o, K, frame_size_sec, frq, n_scale, h, &why);
+  if (rc) return fail(rc, "cSpectral (%lld bins, frame size %g s): %s", (long long)K, frame_size_sec, why);
+  if (geo) {
+    const int32_t g[12] = {h.lo, h.hi, h.has_axis, h.ar_n1, h.ar_n2, h.hb_n1, h.hb_n2, 0, 0, 0, 0, 0};
+    std::memcpy(geo, g, sizeof(g));
+  }
+  if (edges)
+    for (int k = 0; k < o->base.n_bands + o->base.n_slopes; ++k) {
+      double *e = edges + 5 * k;
+      e[0] = h.iL[k]; e[1] = h.iR[k]; e[2] = h.wL[k]; e[3] = h.wR[k]; e[4] = h.Nind[k];
+    }
+  if (sums) { sums[0] = h.slope_Sf; sums[1] = h.slope_S2f; }
+  if (sharp) std::memcpy(sharp, h.sharp.data(), h.sharp.size() * sizeof(double));
+  return h.n_out;
+}
+extern "C" int smilehip_spectral_axis_op_create(smilehip_context *ctx, const smilehip_spectral_axis_opts *o, int64_t K, double frame_size_sec,
+                                                const double *frq, int64_t n_scale, smilehip_spectral_axis_op **out) {
+  if (!ctx || !o || !out) return fail(SMILEHIP_ERR_INVALID, "smilehip_spectral_axis_op_create: null argument");
+  SpectralAxisHost h;
+  const char *why = "";
+  int rc = make_spectral_axis_tables(*o, K, frame_size_sec, frq, n_scale, h, &why);
+  if (rc) return fail(rc, "cSpectral (%lld bins, frame size %g s): %s", (long long)K, frame_size_sec, why);
+  std::unique_ptr<smilehip_spectral_axis_op> op(new smilehip_spectral_axis_op);
+  op->ctx = ctx;
+  if ((rc = op->d_ax_m.upload(h.ax_m)) || (rc = op->d_ax_ro.upload(h.ax_ro)) || (rc = op->d_sharp.upload(h.sharp))) return rc;
+  if (!h.has_axis && ((rc = op->d_ax_c.upload(h.ax_c)) || (rc = op->d_ax_s.upload(h.ax_s)))) return rc;
+  const smilehip_spectral_opts &b = o->base;
+  SpectralAxisDev &G = op->G;
+  G.K = h.K; G.n_out = h.n_out; G.lo = h.lo; G.hi = h.hi; G.has_axis = h.has_axis;
+  G.square_input = o->square_input != 0; G.use_log = o->use_log_spectrum != 0; G.norm_band = o->norm_band_energies != 0;
+  G.alpha_ratio = o->alpha_ratio != 0; G.hammarberg = o->hammarberg_index != 0; G.old_slope_scale = o->old_slope_scale != 0;
+  G.buggy_roll_off = o->buggy_roll_off == 1;                // `buggyRollOff == 1`, spectral.cpp:1107
+  G.ar_n1 = h.ar_n1; G.ar_n2 = h.ar_n2; G.hb_n1 = h.hb_n1; G.hb_n2 = h.hb_n2;
+  G.spec_floor = h.spec_floor; G.log_spec_floor = h.log_spec_floor; G.log_spec_factor = h.log_spec_factor;
+  G.F0 = 1.0 / frame_size_sec; G.ln10 = std::log(10.0);
+  G.n_bands = b.n_bands; G.n_slopes = b.n_slopes; G.n_rolloff = b.n_rolloff;
+  for (int k = 0; k < b.n_bands; ++k) { G.iL[k] = h.iL[k]; G.iR[k] = h.iR[k]; G.wL[k] = h.wL[k]; G.wR[k] = h.wR[k]; G.Nind[k] = h.Nind[k]; }
+  for (int k = 0; k < b.n_slopes; ++k) {                   // the kernel keeps slopes[] at 16 ..
+    const int s = b.n_bands + k;
+    G.iL[16 + k] = h.iL[s]; G.iR[16 + k] = h.iR[s]; G.wL[16 + k] = h.wL[s]; G.wR[16 + k] = h.wR[s]; G.Nind[16 + k] = h.Nind[s];
+  }
+  for (int i = 0; i < b.n_rolloff; ++i) G.rolloff[i] = b.rolloff[i];
+  G.flux = b.flux != 0; G.centroid = b.centroid != 0; G.max_pos = b.max_pos != 0; G.min_pos = b.min_pos != 0;
+  G.entropy = b.entropy != 0; G.variance = b.variance != 0; G.skewness = b.skewness != 0; G.kurtosis = b.kurtosis != 0;
+  G.slope = b.slope != 0; G.sharpness = b.sharpness != 0; G.harmonicity = b.harmonicity != 0;
+  G.flatness = b.flatness != 0; G.log_flatness = b.log_flatness != 0;
+  G.spec_diff = b.spec_diff != 0; G.spec_pos_diff = b.spec_pos_diff != 0; G.flux_centroid = b.flux_centroid != 0;
+  G.flux_at_flux_centroid = b.flux_at_flux_centroid != 0; G.standard_deviation = b.standard_deviation != 0;
+  G.slope_Sf = h.slope_Sf; G.slope_S2f = h.slope_S2f;
+  G.ax_m = op->d_ax_m.p; G.ax_ro = op->d_ax_ro.p; G.sharp_w = op->d_sharp.p;
+  G.ax_c = h.has_axis ? op->d_ax_m.p : op->d_ax_c.p;
+  G.ax_s = h.has_axis ? op->d_ax_m.p : op->d_ax_s.p;
+  *out = op.release();
+  return SMILEHIP_OK;
+}
+extern "C" int smilehip_spectral_axis_op_frames(smilehip_spectral_axis_op *op, const float *d_src, int64_t ld_src, float *d_state, int first,
+                                                float *d_dst, int64_t ld_dst, int64_t n_frames, void *stream) {
+  if (!op) return fail(SMILEHIP_ERR_INVALID, "smilehip_spectral_axis_op_frames: null operator");
+  const SpectralAxisDev &G = op->G;
+  if (n_frames < 0 || ld_src < G.K || ld_dst < G.n_out || (n_frames > 0 && (!d_src || !d_dst)) ||
+      ((G.flux || G.spec_diff || G.spec_pos_diff || G.flux_centroid || G.flux_at_flux_centroid) && !d_state))
+    return fail(SMILEHIP_ERR_INVALID, "smilehip_spectral_axis_op_frames: bad argument (K %d, %d outputs; d_state is needed when flux is on)", G.K, G.n_out);
+  STAGE_RET(stage_spectral_axis(G, d_src, ld_src, d_state, first, d_dst, ld_dst, n_frames, (hipStream_t)stream), "spectral (axis)");
+}
+
 // ---- cSpecScale on any target scale: an operator object (the axes and the spline's caches are functions of the options and the
 // level's geometry alone: cSpecScale::dataProcessorCustomFinalise, src/dsp/specScale.cpp:248-321)
 struct smilehip_specscale_op {

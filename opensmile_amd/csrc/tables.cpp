@@ -4,6 +4,8 @@
 
 #include <cmath>
 
+#include "glibc_float.hpp"
+
 namespace smilehip {
 
 static int64_t next_pow2(int64_t x) {
@@ -449,6 +451,202 @@ int make_specscale_tables(const smilehip_specscale_opts &o, int64_t n_src, doubl
       const double w = 0.5 + std::atan(3.0 * (i + 1 - atan_s) / nPointsPerOctave) / M_PI;
       if (!std::isfinite(w)) { *why = "the auditory weighting is not finite (a target range of zero octaves)"; return SMILEHIP_ERR_INVALID; }
       h.ip_rec[(size_t)i * 4 + 3] = w;
+    }
+  }
+  return SMILEHIP_OK;
+}
+
+// smileDsp_specScaleTransfInv (src/smileutil/smileUtil.c:1158-1199) for the same scales
+static double specscale_inv(double x, int scale, double param) {
+  switch (scale) {
+    case SMILEHIP_SPECSCALE_LOG:
+      return std::exp(x * std::log(param));
+    case SMILEHIP_SPECSCALE_SEMITONE:
+      return param * std::pow(2.0, x / 12.0);
+    case SMILEHIP_SPECSCALE_BARK_OLD: {
+      const double z0 = (x + 0.53) / 26.81;
+      if (z0 != 1.0) return (1960.0 * z0) / (1.0 - z0);
+      return 0.0;
+    }
+    case SMILEHIP_SPECSCALE_BARK: {
+      double zz = x;
+      if (x > 20.1) zz = (x + 0.22 * 20.1) / 1.22;
+      else if (x < 2) zz = (x - 0.3) / 0.85;
+      const double z0 = 26.81 / (zz + 0.53);
+      if (z0 != 1.0) return 1960.0 / (z0 - 1.0);
+      return 0.0;
+    }
+    case SMILEHIP_SPECSCALE_MEL:
+      return 700.0 * (std::exp(x / 1127.0) - 1.0);
+    default:
+      return x;
+  }
+}
+
+// f * smileDsp_getSharpnessWeightG(f, SPECTSCALE_BARK, 0.0) (smileUtil.c:1064-1078) for f in Bark
+static double sharpness_weight(double bark) {
+  const double g = (bark <= 16.0) ? 1.0 : std::pow((bark - 16.0) / 4.0, 1.5849625) + 1.0;
+  return bark * g;
+}
+
+// cSpectral::processVector's setup (src/lldcore/spectral.cpp): the range bins (:625-647), the band and slope edges in the axis form
+// and in the index form (:771-840, :873-946), the slope's axis sums (:1400-1418), where the alpha ratio's and the Hammarberg index'
+// walks change band and stop (:995-1089), the sharpness weights (:1438-1468), the floor of the log spectrum (:85-91, :228-237).
+// Without an axis the reference's nScale is 0 (:601), so the interior loop of slopes[] (`ii < nScale`, :969) never runs, the
+// centroid's axis is the running sum f += F0 from 0 at the range's first bin (:1291-1294) and the sharpness weights continue that
+// same f (:1464-1466). What the reference leaves undefined is refused by the option's name.
+int make_spectral_axis_tables(const smilehip_spectral_axis_opts &o, int64_t K, double frame_size_sec, const double *frq, int64_t n_scale,
+                              SpectralAxisHost &h, const char **why) {
+  const char *dummy;
+  if (!why) why = &dummy;
+  *why = "";
+  const smilehip_spectral_opts &b = o.base;
+  if (K < 4 || K > 8193) { *why = "K: 4 .. 8193 bins are built"; return SMILEHIP_ERR_INVALID; }
+  if (!(frame_size_sec > 0.0)) { *why = "frame_size_sec: the level's frameSizeSec must be positive"; return SMILEHIP_ERR_INVALID; }
+  if (o.tonality) { *why = "tonality: not implemented in the reference (it writes 0 and prints an error)"; return SMILEHIP_ERR_INVALID; }
+  if (b.n_bands < 0 || b.n_bands > 16) { *why = "bands: 0 .. 16 are built"; return SMILEHIP_ERR_INVALID; }
+  if (b.n_slopes < 0 || b.n_slopes > 16) { *why = "slopes: 0 .. 16 are built"; return SMILEHIP_ERR_INVALID; }
+  if (b.n_rolloff < 0 || b.n_rolloff > 16) { *why = "rollOff: 0 .. 16 points are built"; return SMILEHIP_ERR_INVALID; }
+  for (int i = 0; i < b.n_rolloff; ++i)
+    if (!(b.rolloff[i] >= 0.0 && b.rolloff[i] <= 1.0)) { *why = "rollOff: a point outside 0 .. 1"; return SMILEHIP_ERR_INVALID; }
+  if (frq && n_scale < K) { *why = "n_scale: an axis shorter than the spectrum (the reference then mixes the two forms)"; return SMILEHIP_ERR_INVALID; }
+  if (!frq && n_scale != 0) { *why = "n_scale: must be 0 without an axis"; return SMILEHIP_ERR_INVALID; }
+  const int fs = o.frq_scale;
+  if (fs != SMILEHIP_SPECSCALE_LINEAR && fs != SMILEHIP_SPECSCALE_LOG && fs != SMILEHIP_SPECSCALE_BARK && fs != SMILEHIP_SPECSCALE_MEL &&
+      fs != SMILEHIP_SPECSCALE_SEMITONE && fs != SMILEHIP_SPECSCALE_BARK_OLD) { *why = "frq_scale: unknown scale"; return SMILEHIP_ERR_INVALID; }
+  const int Nsrc = (int)K;
+  const bool axis = frq != nullptr;
+  if (axis)
+    for (int i = 0; i < Nsrc; ++i)
+      if (!std::isfinite(frq[i]) || (i > 0 && !(frq[i] > frq[i - 1]))) { *why = "frq: the axis does not increase"; return SMILEHIP_ERR_INVALID; }
+  if (o.freq_lo < 0 || o.freq_hi < o.freq_lo) { *why = "freqRange: 0 <= lower <= upper"; return SMILEHIP_ERR_INVALID; }
+  h = SpectralAxisHost();
+  h.K = Nsrc; h.has_axis = axis ? 1 : 0;
+  h.n_out = smilehip_spectral_axis_opts_count(&o);
+  if (h.n_out < 1) { *why = "no output is switched on"; return SMILEHIP_ERR_INVALID; }
+  const double F0 = 1.0 / frame_size_sec;
+  // :85-91, :228-237
+  if (o.use_log_spectrum) {
+    float sf = (float)o.spec_floor;
+    if (!(sf > 0.0f) || !std::isfinite(sf)) { *why = "specFloor: must be positive (its logarithm is the floor)"; return SMILEHIP_ERR_INVALID; }
+    sf = sf * sf;
+    if (!(sf > 0.0f)) { *why = "specFloor: its square underflows"; return SMILEHIP_ERR_INVALID; }
+    h.spec_floor = sf;
+  } else {
+    h.spec_floor = (float)(0.0000001 * 0.0000001);
+  }
+  h.log_spec_floor = (float)(10.0 * (double)glibc_logf(h.spec_floor) / std::log(10.0));
+  h.log_spec_factor = (float)(10.0 / std::log(10.0));
+  // :625-647
+  if (o.freq_lo == 0 && o.freq_hi == 0) {
+    h.lo = 1; h.hi = Nsrc - 1;
+  } else {
+    if (!axis) { *why = "freqRange: a range other than 0-0 reads the axis"; return SMILEHIP_ERR_INVALID; }
+    int lb = -1, ub = -1;
+    for (int i = 0; i < Nsrc; i++) {
+      if ((double)o.freq_lo >= frq[i]) lb = i;
+      if ((double)o.freq_hi > frq[i]) ub = i;
+    }
+    if (ub == -1 || ub >= Nsrc) ub = Nsrc - 1;
+    if (lb < 0) lb = 0;
+    if (ub < lb) { *why = "freqRange: the range selects no bin"; return SMILEHIP_ERR_INVALID; }
+    h.lo = lb; h.hi = ub;
+  }
+  const int nBins = h.hi - h.lo + 1;
+  // :771-840, :873-946
+  for (int k = 0; k < b.n_bands + b.n_slopes; ++k) {
+    const bool is_slope = k >= b.n_bands;
+    const int lo = is_slope ? b.slope_lo[k - b.n_bands] : b.band_lo[k], hi = is_slope ? b.slope_hi[k - b.n_bands] : b.band_hi[k];
+    if (lo < 0 || hi <= lo) { *why = is_slope ? "slopes: lower < upper, both >= 0" : "bands: lower < upper, both >= 0"; return SMILEHIP_ERR_INVALID; }
+    double idxL, wghtL, idxR, wghtR;
+    if (!axis) {
+      idxL = (double)lo / F0;
+      wghtL = std::ceil(idxL) - idxL;
+      idxR = (double)hi / F0;
+      wghtR = idxR - std::floor(idxR);
+    } else {
+      int ii;
+      for (ii = 0; ii < Nsrc; ii++) if (frq[ii] > (double)lo) break;
+      if ((ii < Nsrc) && (ii > 0)) wghtL = (frq[ii] - (double)lo) / (frq[ii] - frq[ii - 1]); else wghtL = 1.0;
+      idxL = (double)ii - 1.0;
+      if (idxL < 0) idxL = 0;
+      if (idxL >= Nsrc) idxL = Nsrc;
+      for (ii = 0; ii < Nsrc; ii++) if (frq[ii] >= (float)hi) break;
+      if ((ii < Nsrc) && (ii > 0)) wghtR = ((double)hi - frq[ii - 1]) / (frq[ii] - frq[ii - 1]); else wghtR = 1.0;
+      if ((ii < Nsrc) && (frq[ii] == (float)hi)) idxR = (double)ii; else idxR = (double)ii - 1.0;
+      if (idxR >= Nsrc) idxR = Nsrc - 1;
+    }
+    if (wghtL == 0.0) wghtL = 1.0;
+    if (wghtR == 0.0) wghtR = 1.0;
+    long iL = (long)std::floor(idxL), iR = (long)std::floor(idxR);
+    if (iL >= Nsrc) { iL = iR = Nsrc - 1; wghtR = 0.0; wghtL = 0.0; }
+    if (iR >= Nsrc) { iR = Nsrc - 1; wghtR = 1.0; }
+    if (iL < 0) iL = 0;
+    if (iR < 0) iR = 0;
+    if (iR < iL) { *why = is_slope ? "slopes: a band that lies between two bins of this spectrum" : "bands: a band that lies between two bins of this spectrum"; return SMILEHIP_ERR_INVALID; }
+    h.iL[k] = (int32_t)iL; h.iR[k] = (int32_t)iR; h.wL[k] = wghtL; h.wR[k] = wghtR; h.Nind[k] = idxR - idxL;
+  }
+  // :995-1089: both walks end at the first bin above 5 kHz; f is the axis or the running sum f += F0
+  {
+    double f = 0.0;
+    h.ar_n1 = h.hb_n1 = -1;
+    int j;
+    for (j = 0; j < Nsrc; j++) {
+      const double fj = axis ? frq[j] : f;
+      if (fj > 5000.0) break;
+      if (!(fj < 1000.0) && h.ar_n1 < 0) h.ar_n1 = j;
+      if (!(fj < 2000.0) && h.hb_n1 < 0) h.hb_n1 = j;
+      f += F0;
+    }
+    h.ar_n2 = h.hb_n2 = j;
+    if (h.ar_n1 < 0) h.ar_n1 = j;
+    if (h.hb_n1 < 0) h.hb_n1 = j;
+  }
+  // the axes the kernel reads
+  const bool ctr_group = b.centroid || b.standard_deviation || b.variance || b.skewness || b.kurtosis || b.slope;
+  h.ax_m.assign((size_t)Nsrc, 0.0);
+  h.ax_ro.assign((size_t)Nsrc, 0.0f);
+  double f = 0.0;                                         // :1261, shared by the centroid and the sharpness weights
+  if (axis) {
+    for (int j = 0; j < Nsrc; ++j) { h.ax_m[j] = frq[j]; h.ax_ro[j] = (float)frq[j]; }
+    h.ax_c = h.ax_m;
+    h.ax_s = h.ax_m;
+  } else {
+    h.ax_c.assign((size_t)Nsrc, 0.0);
+    h.ax_s.assign((size_t)Nsrc, 0.0);
+    for (int j = 0; j < Nsrc; ++j) { h.ax_m[j] = (double)j * F0; h.ax_ro[j] = (float)j * (float)F0; h.ax_s[j] = (double)j; }
+    if (ctr_group)
+      for (int j = h.lo; j <= h.hi; ++j) { h.ax_c[j] = f; f += F0; }
+  }
+  // :1400-1418
+  if (axis) {
+    for (int i = h.lo; i <= h.hi; i++) { h.slope_S2f += frq[i] * frq[i]; h.slope_Sf += frq[i]; }
+  } else {
+    const double Nind = (double)nBins;
+    const double NNm1 = Nind * (Nind - 1.0);
+    const double S1 = NNm1 / (double)2.0;
+    const double S2 = NNm1 * ((double)2.0 * Nind - (double)1.0) / (double)6.0;
+    h.slope_Sf = S1 * F0;
+    h.slope_S2f = S2 * F0 * F0;
+  }
+  // :1438-1468
+  h.sharp.assign((size_t)nBins, 0.0);
+  if (b.sharpness) {
+    for (int j = h.lo; j <= h.hi; j++) {
+      double fb;
+      if (axis) {
+        fb = frq[j];
+        if (fs != SMILEHIP_SPECSCALE_BARK) {
+          fb = specscale_inv(fb, fs, o.frq_scale_param);
+          fb = specscale_fwd(fb, SMILEHIP_SPECSCALE_BARK, 0.0);
+        }
+      } else {
+        fb = specscale_fwd(f, SMILEHIP_SPECSCALE_BARK, 0.0);
+        f += F0;
+      }
+      const double w = sharpness_weight(fb);
+      if (!std::isfinite(w)) { *why = "frq_scale: a sharpness weight is not finite on this axis"; return SMILEHIP_ERR_INVALID; }
+      h.sharp[(size_t)(j - h.lo)] = w;
     }
   }
   return SMILEHIP_OK;

@@ -70,6 +70,25 @@ struct SpecScaleHost {
 // n_src bins of a spectrum level whose frameSizeSec is frame_size_sec; 0 on success, otherwise `why` names the cause
 int  make_specscale_tables(const smilehip_specscale_opts &o, int64_t n_src, double frame_size_sec, SpecScaleHost &h, const char **why);
 
+// cSpectral on any spectrum (smilehip_spectral_axis_opts): everything of cSpectral::processVector (src/lldcore/spectral.cpp:586-1555)
+// that depends on the options and the frequency axis alone, restated in double
+struct SpectralAxisHost {
+  int32_t K = 0, n_out = 0, has_axis = 0;
+  int32_t lo = 0, hi = 0;                                 // specRangeLowerBin / specRangeUpperBin (:625-647)
+  int32_t ar_n1 = 0, ar_n2 = 0, hb_n1 = 0, hb_n2 = 0;     // alpha ratio: bins [0, n1) below 1 kHz, [n1, n2) up to 5 kHz; Hammarberg: 2 kHz (:995-1089)
+  int32_t iL[32] = {0}, iR[32] = {0};                     // bands[], then slopes[]: edge bins, weights, idxR - idxL (:771-840, :873-946)
+  double wL[32] = {0}, wR[32] = {0}, Nind[32] = {0};
+  double slope_Sf = 0.0, slope_S2f = 0.0;                 // :1400-1418
+  float spec_floor = 0.0f, log_spec_floor = 0.0f, log_spec_factor = 0.0f;   // :85-91, :228-237, :690
+  std::vector<double> ax_c, ax_m, ax_s;                   // [K] the axis the centroid (:1263-1299), the moments / flux centroid / extremes and the slopes[] read
+  std::vector<float> ax_ro;                               // [K] a roll-off point's value (:1110-1116)
+  std::vector<double> sharp;                              // [hi - lo + 1] (:1438-1468)
+};
+// K bins of a level whose frameSizeSec is frame_size_sec; frq / n_scale: the level's axis or (nullptr, 0); 0 on success, otherwise
+// `why` names the option
+int  make_spectral_axis_tables(const smilehip_spectral_axis_opts &o, int64_t K, double frame_size_sec, const double *frq, int64_t n_scale,
+                               SpectralAxisHost &h, const char **why);
+
 int  make_geometry(const smilehip_lld_config &c, Geometry &g);
 int  make_window(const smilehip_lld_config &c, int64_t N, std::vector<float> &w);
 int  make_mel(const smilehip_lld_config &c, const Geometry &g, MelBank &m);

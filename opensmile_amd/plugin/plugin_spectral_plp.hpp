@@ -15,6 +15,25 @@ class cHipSpectral : public BlockVP<cSpectral> {
   int general_ = -1, gen_n_out_ = 0;
   smilehip_spectral_opts gen_opts_;
   smilehip_spectral_op *gen_op_[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  // every other option set (smilehip_spectral_axis_op_*: log spectrum, freqRange, normBandEnergies, alphaRatio / hammarbergIndex, power
+  // input, the new slope scale, the old roll-off, any frequency axis): one operator per field
+  int axis_ = -1, ax_n_out_ = 0;
+  std::string ax_why_;
+  smilehip_spectral_axis_opts ax_opts_;
+  smilehip_spectral_axis_op *ax_op_[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  const double *ax_frq_ = nullptr;                       // the axis of the field seen first, as the reference caches it (spectral.cpp:595-612)
+  long ax_n_scale_ = -1;
+  // bands[] / slopes[] = "lo-hi" in Hz, integers, sorted as parseBandsConfig does (spectral.cpp:142-208)
+  bool parse_bands(const char *name, int n, int32_t *lo_out, int32_t *hi_out) {
+    for (int b = 0; b < n; ++b) {
+      const char *v = getStr_f(myvprint("%s[%i]", name, b));
+      long lo = -1, hi = -1;
+      int used = 0;
+      if (!v || sscanf(v, "%ld-%ld%n", &lo, &hi, &used) != 2 || v[used] != 0 || lo < 0 || hi < 0 || lo > 2000000000 || hi > 2000000000) return false;
+      lo_out[b] = (int32_t)(lo < hi ? lo : hi); hi_out[b] = (int32_t)(lo < hi ? hi : lo);
+    }
+    return true;
+  }
   bool array_is(const char *name, int n, const char *const *vals) {
     if (getArraySize(name) != n) return false;
     for (int i = 0; i < n; ++i) {
@@ -136,9 +155,83 @@ class cHipSpectral : public BlockVP<cSpectral> {
       g_frames[12] += g_blk.n;
       return (int)Ndst;
     }
+    if (!compare_set && axis_ < 0) {
+      // everything else spectral.cpp:586-1555 offers, on whatever level the instance reads
+      std::memset(&ax_opts_, 0, sizeof(ax_opts_));
+      smilehip_spectral_opts &b = ax_opts_.base;
+      const int nb = getArraySize("bands") > 0 ? getArraySize("bands") : 0, nr = getArraySize("rollOff") > 0 ? getArraySize("rollOff") : 0;
+      const int nsl = getArraySize("slopes") > 0 ? getArraySize("slopes") : 0;
+      if (getInt("tonality")) ax_why_ = "tonality (the reference writes 0 and prints an error)";
+      else if (nb > 16) ax_why_ = "more than 16 bands";
+      else if (nsl > 16) ax_why_ = "more than 16 slopes";
+      else if (nr > 16) ax_why_ = "more than 16 rollOff points";
+      else if (!parse_bands("bands", nb, b.band_lo, b.band_hi)) ax_why_ = "a bands[] entry that is not lo-hi in Hz";
+      else if (!parse_bands("slopes", nsl, b.slope_lo, b.slope_hi)) ax_why_ = "a slopes[] entry that is not lo-hi in Hz";
+      b.n_bands = nb; b.n_slopes = nsl; b.n_rolloff = nr;
+      for (int i = 0; i < nr && i < 16; ++i) {            // clipped as at spectral.cpp:340-347
+        double r = getDouble_f(myvprint("rollOff[%i]", i));
+        b.rolloff[i] = r < 0.0 ? 0.0 : (r > 1.0 ? 1.0 : r);
+      }
+      b.spec_diff = getInt("specDiff"); b.spec_pos_diff = getInt("specPosDiff"); b.flux = getInt("flux"); b.flux_centroid = getInt("fluxCentroid");
+      b.flux_at_flux_centroid = getInt("fluxAtFluxCentroid"); b.centroid = getInt("centroid"); b.max_pos = getInt("maxPos"); b.min_pos = getInt("minPos");
+      b.entropy = getInt("entropy"); b.standard_deviation = getInt("standardDeviation"); b.variance = getInt("variance");
+      b.skewness = getInt("skewness"); b.kurtosis = getInt("kurtosis"); b.slope = getInt("slope"); b.sharpness = getInt("sharpness");
+      b.harmonicity = getInt("harmonicity"); b.flatness = getInt("flatness"); b.log_flatness = getInt("logFlatness");
+      ax_opts_.square_input = getInt("squareInput"); ax_opts_.use_log_spectrum = getInt("useLogSpectrum");
+      ax_opts_.norm_band_energies = getInt("normBandEnergies"); ax_opts_.alpha_ratio = getInt("alphaRatio");
+      ax_opts_.hammarberg_index = getInt("hammarbergIndex"); ax_opts_.old_slope_scale = getInt("oldSlopeScale");
+      ax_opts_.buggy_roll_off = getInt("buggyRollOff"); ax_opts_.spec_floor = getDouble("specFloor");
+      const char *fr = getStr("freqRange");                // parseRange, spectral.cpp:94-140
+      long r1 = -1, r2 = -1;
+      int used = 0;
+      if (ax_why_.empty() && (!fr || sscanf(fr, "%ld-%ld%n", &r1, &r2, &used) != 2 || fr[used] != 0 || r1 < 0 || r2 < 0 || r1 > 2000000000 || r2 > 2000000000))
+        ax_why_ = "a freqRange that is not lower-upper in Hz";
+      ax_opts_.freq_lo = (int32_t)(r1 <= r2 ? r1 : r2); ax_opts_.freq_hi = (int32_t)(r1 <= r2 ? r2 : r1);
+      ax_n_out_ = ax_why_.empty() ? smilehip_spectral_axis_opts_count(&ax_opts_) : 0;
+      if (ax_why_.empty() && ax_n_out_ < 1) ax_why_ = "an instance without outputs";
+      axis_ = ax_why_.empty() ? 1 : 0;
+    }
+    if (!compare_set && axis_ == 1 && Nsrc >= 4 && Nsrc <= 8193 && Ndst == ax_n_out_ && fc >= 0 && fc < 8) {
+      if (!ax_op_[fc]) {
+        if (ax_n_scale_ < 0) {                             // spectral.cpp:595-612: the axis of the field that comes first, kept for all
+          const FrameMetaInfo *fmeta = reader_->getFrameMetaInfo();
+          ax_n_scale_ = 0;
+          if (fmeta && idxi < fmeta->N) {
+            ax_n_scale_ = (long)(fmeta->field[idxi].infoSize / sizeof(double));
+            ax_frq_ = (const double *)(fmeta->field[idxi].info);
+          }
+          // :614-623: the scale comes from the WRITER level's meta data (this instance's own output level), not from the reader's
+          cVectorMeta *mdata = writer_->getLevelMetaDataPtr();
+          if (mdata != NULL && mdata->ID == 1001 /* SCALED_SPEC */) {
+            ax_opts_.frq_scale = (int)mdata->fData[6];
+            ax_opts_.frq_scale_param = (double)mdata->fData[7];
+          } else {
+            ax_opts_.frq_scale = SMILEHIP_SPECSCALE_LINEAR;
+            ax_opts_.frq_scale_param = 0.0;
+          }
+        }
+        const bool have = ax_frq_ && ax_n_scale_ > 0;      // (no points: `nScale < Nsrc`, the index-based branches)
+        if (smilehip_spectral_axis_op_create(context(), &ax_opts_, Nsrc, reader_->getLevelConfig()->frameSizeSec, have ? ax_frq_ : nullptr,
+                                             have ? ax_n_scale_ : 0, &ax_op_[fc])) {
+          ax_why_ = std::string("what the operator refuses (") + smilehip_last_error() + ")";   // the instance leaves this route: the fall-through below
+          axis_ = 0;
+        }
+      }
+    }
+    if (!compare_set && axis_ == 1 && Nsrc >= 4 && Nsrc <= 8193 && Ndst == ax_n_out_ && fc >= 0 && fc < 8 && ax_op_[fc]) {
+      io_.ensure(Nsrc, ax_n_out_);
+      io_.up(src, Nsrc);
+      float *d_prev = (float *)prev_[fc].ensure(sizeof(float) * (uint64_t)Nsrc);
+      check(smilehip_spectral_axis_op_frames(ax_op_[fc], io_.d_in, Nsrc, d_prev, seen_[fc] ? 0 : 1, io_.d_out, ax_n_out_, g_blk.n, nullptr));
+      seen_[fc] = true;
+      io_.down(dst, ax_n_out_);
+      g_frames[12] += g_blk.n;
+      return (int)Ndst;
+    }
     if (!compare_set || fc < 0 || fc >= 8) {
-      HIP_FALLTHROUGH(12, "cSpectral: the linear-spectrum descriptor sets (bands, slopes, rollOff points, specDiff, specPosDiff, flux, fluxCentroid, fluxAtFluxCentroid, centroid, "
-                          "maxPos, minPos, entropy, standardDeviation, variance, skewness, kurtosis, slope, sharpness, harmonicity, flatness; freqRange 0-0) and the two GeMAPS sets (log-spectrum slopes + alphaRatio + hammarbergIndex; flux over 0-5000 Hz) are built");
+      const std::string why = "cSpectral: " + (ax_why_.empty() ? std::string("more than 8 input fields, fewer than 4 or more than 8193 bins, or an output count the options do not give") : ax_why_) +
+                              " is not built (every other option of the component is)";
+      HIP_FALLTHROUGH(12, why.c_str());
       return cSpectral::processVector(src, dst, Nsrc, Ndst, idxi);
     }
     smilehip_plan *&pl = plans_.at(fc);
@@ -171,6 +264,7 @@ class cHipSpectral : public BlockVP<cSpectral> {
   ~cHipSpectral() override {
     if (gm_plan_) smilehip_plan_destroy(gm_plan_);
     for (auto *op : gen_op_) if (op) smilehip_spectral_op_destroy(op);
+    for (auto *op : ax_op_) if (op) smilehip_spectral_axis_op_destroy(op);
   }
   static cSmileComponent *create(const char *n) {
     cSmileComponent *c = new cHipSpectral(n);
