@@ -766,10 +766,12 @@ int smilehip_spectral_frames(smilehip_plan *plan, const float *d_mag, int64_t ld
                              float *d_dst, int64_t ld_dst, int64_t n_frames, void *stream);
 /* R11, every option set of the shipped configuration files: cSpectral::processVector (spectral.cpp:586-1560; options :31-63, output
  * order = the order of the fields below) with squareInput = 1 on a linear magnitude spectrum, freqRange 0-0, normBandEnergies = 0,
- * useLogSpectrum = 0, buggyRollOff = 0, oldSlopeScale = 1. An operator object holds what follows from the options and the frequency axis
- * (frq[i] = i / frame_size_sec, i < K: the axis cTransformFFT attaches, transformFft.cpp:102-117). Frames of ONE stream in order:
- * d_state (K floats; needed when flux is on) carries the last frame's magnitudes from call to call, `first` != 0 marks the stream's
- * first frame (a single 0 for the flux, :1132-1136). One thread per frame, every sum the reference's own sequential chain. */
+ * useLogSpectrum = 0, buggyRollOff = 0, oldSlopeScale = 1, on K = 4 .. 2^20 bins. This IS the operator of
+ * smilehip_spectral_axis_op_* below with these options fixed (alphaRatio = hammarbergIndex = 0, linear frq_scale) on the frequency
+ * axis frq[i] = i / frame_size_sec, i < K (the one cTransformFFT attaches, transformFft.cpp:102-117): the same kernel, the same
+ * tables, the same refusals (SMILEHIP_ERR_INVALID: an inverted band, one between two bins, a rollOff point outside 0 .. 1, no
+ * output). Frames of ONE stream in order: d_state (K floats; needed when flux is on) carries the last frame's magnitudes from call
+ * to call, `first` != 0 marks the stream's first frame (a single 0 for the flux, :1132-1136). */
 typedef struct smilehip_spectral_opts {
   int32_t n_bands;              /* bands[]: lo-hi in Hz, <= 16 */
   int32_t band_lo[16], band_hi[16];
@@ -795,7 +797,7 @@ int smilehip_spectral_op_frames(smilehip_spectral_op *op, const float *d_mag, in
                                 float *d_dst, int64_t ld_dst, int64_t n_frames, void *stream);
 int smilehip_spectral_op_destroy(smilehip_spectral_op *op);
 /* R11 on any spectrum: cSpectral::processVector (spectral.cpp:586-1555) with the options smilehip_spectral_opts leaves at their
- * shipped values, on K = 4 .. 8193 bins of any level -- an FFT magnitude or power spectrum or what cSpecScale makes of one. `base`:
+ * shipped values, on K = 4 .. 2^20 bins of any level -- an FFT magnitude or power spectrum or what cSpecScale makes of one. `base`:
  * as above. Output order (setupNamesForField, :378-583): bands, slopes, alphaRatio, hammarbergIndex, rollOff, specDiff, specPosDiff,
  * flux, fluxCentroid, fluxAtFluxCentroid, centroid, maxPos, minPos, entropy, standardDeviation, variance, skewness, kurtosis, slope,
  * sharpness, harmonicity, flatness.

@@ -1,8 +1,9 @@
 // R11 on any spectrum: cSpectral::processVector (src/lldcore/spectral.cpp:586-1555) with squareInput, useLogSpectrum / specFloor,
 // normBandEnergies, alphaRatio, hammarbergIndex, freqRange, oldSlopeScale, buggyRollOff free and the level's own frequency axis
-// (or none: the index-based branches), on K = 4 .. 8193 bins. What depends on the options and the axis alone comes from
-// make_spectral_axis_tables (tables.cpp); the kernel reads it through wave-uniform addresses.
-// One THREAD per frame, as in lld_spectral_general.hip: every accumulator is the reference's own sequential chain (double, or
+// (or none: the index-based branches), on K = 4 .. 2^20 bins: the one cSpectral operator for every option set but ComParE_2016's and
+// GeMAPS' (their wave-parallel kernels: lld_blocks_compare.hpp / lld_gemaps.hip). What depends on the options and the axis alone comes
+// from make_spectral_axis_tables (tables.cpp); the kernel reads it through wave-uniform addresses.
+// One THREAD per frame, the frames of a launch side by side: every accumulator is the reference's own sequential chain (double, or
 // FLOAT_DMEM where it has one), and each lane walks its own row of the matrix, deriving srcM / srcP / srcL of a bin (:661-716) where
 // it reads it. A form that staged 64-frame x 32-bin tiles through LDS (coalesced row loads, the derivations once per bin and
 // walk, padded columns) was built and measured on the same rows: 7 to 23 % slower on every option set timed
@@ -29,6 +30,31 @@ __device__ __forceinline__ float spectral_log(const SpectralAxisDev &G, float p)
 __device__ __forceinline__ float spectral_mag(const SpectralAxisDev &G, float x) {   // :661-676
   if (G.square_input) return x;
   return x > 0.0f ? sqrtf(x) : 0.0f;
+}
+
+// One bin's share of bands[B ..] (:843-847: the left edge bin weighted, the bins between, the right edge bin weighted) and of
+// rollOff[I ..] (:1104-1118). The slots nest, every index a constant: the first unused slot ends the bin's tests. A loop over the
+// sixteen slots tests each one for every bin, a fifth of the launch on avec2011's two bands and four points
+// (profiles/spectral_one_operator_timing.json against ..._parent.json); one that leaves at the first unused slot is not unrolled, and
+// its running index puts band[] and ro[] behind indexed register moves.
+template <int B>
+__device__ __forceinline__ void band_bin(const SpectralAxisDev &G, int j, float p, double (&band)[16]) {
+  if constexpr (B < 16) {
+    if (B >= G.n_bands) return;
+    if (j == G.iL[B]) band[B] = (double)p * G.wL[B];
+    else if (j > G.iL[B] && j < G.iR[B]) band[B] += (double)p;
+    if (j == G.iR[B]) band[B] += (double)p * G.wR[B];
+    band_bin<B + 1>(G, j, p, band);
+  }
+}
+template <int I>
+__device__ __forceinline__ void rolloff_bin(const SpectralAxisDev &G, int j, float p, double frameSum, double &sumC, float (&ro)[16]) {
+  if constexpr (I < 16) {
+    if (I >= G.n_rolloff) return;
+    if (G.buggy_roll_off == 1 && I > 0) sumC += (double)p;
+    if ((ro[I] == 0.0f) && (sumC >= G.rolloff[I] * frameSum)) ro[I] = G.ax_ro[j];
+    rolloff_bin<I + 1>(G, j, p, frameSum, sumC, ro);
+  }
 }
 
 }  // namespace
@@ -61,14 +87,7 @@ __global__ void __launch_bounds__(64) lld_spectral_axis(SpectralAxisDev G, const
     const float x = row[j];
     const float m = spectral_mag(G, x), p = spectral_pow(G, x);   // srcM, srcP (:661-688)
     const float lp = use_log ? spectral_log(G, p) : p;         // srcLP (:689-721)
-#pragma unroll
-    for (int b = 0; b < 16; ++b) {                             // :843-847: the left edge bin weighted, the bins between, the right edge bin weighted
-      if (b < G.n_bands) {
-        if (j == G.iL[b]) band[b] = (double)p * G.wL[b];
-        else if (j > G.iL[b] && j < G.iR[b]) band[b] += (double)p;
-        if (j == G.iR[b]) band[b] += (double)p * G.wR[b];
-      }
-    }
+    band_bin<0>(G, j, p, band);
     if (G.n_slopes > 0) {
       const double a = G.ax_s[j];                              // frq[j], or j itself where there is no axis (:964-978)
       for (int b = 0; b < G.n_slopes; ++b) {
@@ -195,13 +214,7 @@ __global__ void __launch_bounds__(64) lld_spectral_axis(SpectralAxisDev G, const
     const float p = spectral_pow(G, row[j]);
     const float lp = use_log ? spectral_log(G, p) : p;
     sumC += (double)p;                                         // :1104-1118
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      if (i < G.n_rolloff) {
-        if (G.buggy_roll_off == 1 && i > 0) sumC += (double)p;
-        if ((ro[i] == 0.0f) && (sumC >= G.rolloff[i] * frameSum)) ro[i] = G.ax_ro[j];
-      }
-    }
+    rolloff_bin<0>(G, j, p, frameSum, sumC, ro);
     if (G.entropy) {                                           // smileUtil.c:2112-2122
       double v = lp - emin;
       if (v <= entropy_floor) v = entropy_floor;

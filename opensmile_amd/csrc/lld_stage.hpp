@@ -59,22 +59,6 @@ hipError_t stage_pitchacf(const float *src, int64_t lds, int64_t nF, int n, doub
 struct PlpConsts { float melfloor, compression, iir, fir[5]; };
 hipError_t stage_spectral(const float *src, int64_t lds, float *state, bool first, float *dst, int64_t ldd, int64_t nF, int K,
                           const SpectralConsts &C, hipStream_t s);
-// cSpectral, general option set (lld_spectral_general.hip): what the kernel needs of smilehip_spectral_opts, ready to use
-struct SpectralGeneral {
-  int32_t K;
-  double frame_size_sec;
-  int32_t n_bands, band_iL[16], band_iR[16];            // edge bins and their weights (spectral.cpp:779-826)
-  double band_wL[16], band_wR[16];
-  int32_t n_rolloff;
-  double rolloff[16];
-  int32_t flux, centroid, max_pos, min_pos, entropy, variance, skewness, kurtosis, slope, sharpness, harmonicity, flatness, log_flatness;
-  double slope_Sf, slope_S2f;                           // sums of frq and frq^2 over bins 1 .. K-1 (:1405-1412)
-  const double *sharp_w;                                // [K - 1] sharpness weights of bins 1 .. K-1 (:1440-1455)
-  // round 6: the rest of the linear-spectrum branch
-  int32_t spec_diff, spec_pos_diff, flux_centroid, flux_at_flux_centroid, standard_deviation, n_out;
-  int32_t n_slopes, sl_iL[16], sl_iR[16];               // slopes[]: edge bins, their weights, idxR - idxL (:872-943)
-  double sl_wL[16], sl_wR[16], sl_Nind[16];
-};
 // cSpecScale, any target scale (lld_specscale.hip): the device tables of make_specscale_tables and the operator's scratch
 struct SpecScaleDev {
   int32_t n_src, n_tgt, nb8;                            // nb8: 8-bin blocks of a row, ceil(n_src / 8)
@@ -90,8 +74,6 @@ hipError_t stage_specscale_general(const SpecScaleDev &S, const float *src, int6
                                    hipStream_t s);
 hipError_t stage_mfcc_inverse(const float *src, int64_t lds, float *dst, int64_t ldd, int64_t nF, int n_bands, int first, int last, int htk,
                               int do_log, const float *rows, const float *lifter, hipStream_t s);
-hipError_t stage_spectral_general(const SpectralGeneral &G, const float *mag, int64_t ld_src, float *state, int first, float *dst,
-                                  int64_t ld_dst, int64_t n_frames, hipStream_t s);
 // cSpectral on any spectrum (lld_spectral_axis.hip): smilehip_spectral_axis_opts and make_spectral_axis_tables, ready to use
 struct SpectralAxisDev {
   int32_t K, n_out, lo, hi, has_axis;

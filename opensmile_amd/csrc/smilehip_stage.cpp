@@ -43,19 +43,7 @@ extern "C" int smilehip_pcm_convert_float(smilehip_context *ctx, const float *d_
   STAGE_RET(stage_pcm_convert_float(d_raw, n_chan, mono_mixdown != 0, n, d_out, (hipStream_t)stream), "pcm_convert_float");
 }
 
-// ---- R11, general option set: an operator object (the band edges, the slope's sums and the sharpness weights are functions of the
-// options and the frequency axis alone)
-struct smilehip_spectral_op {
-  smilehip_context *ctx = nullptr;
-  SpectralGeneral G;
-  DevBuf<double> d_sharp;
-  int n_out = 0;
-};
-extern "C" int smilehip_spectral_op_destroy(smilehip_spectral_op *op) {
-  delete op;
-  return SMILEHIP_OK;
-}
-extern "C" int smilehip_spectral_op_n_out(const smilehip_spectral_op *op) { return op ? op->n_out : -1; }
+// ---- R11, cSpectral's option sets: the number of outputs of the options smilehip_spectral_opts holds
 extern "C" int smilehip_spectral_opts_count(const smilehip_spectral_opts *o) {
   if (!o || o->n_bands < 0 || o->n_bands > 16 || o->n_rolloff < 0 || o->n_rolloff > 16 || o->n_slopes < 0 || o->n_slopes > 16) return -1;
   return o->n_bands + o->n_slopes + o->n_rolloff + (o->spec_diff != 0) + (o->spec_pos_diff != 0) + (o->flux != 0) + (o->flux_centroid != 0) +
@@ -63,94 +51,9 @@ extern "C" int smilehip_spectral_opts_count(const smilehip_spectral_opts *o) {
          (o->standard_deviation != 0) + (o->variance != 0) + (o->skewness != 0) + (o->kurtosis != 0) + (o->slope != 0) +
          (o->sharpness != 0) + (o->harmonicity != 0) + (o->flatness != 0);
 }
-extern "C" int smilehip_spectral_op_create(smilehip_context *ctx, const smilehip_spectral_opts *o, int64_t K, double frame_size_sec,
-                                           smilehip_spectral_op **out) {
-  if (!ctx || !o || !out) return fail(SMILEHIP_ERR_INVALID, "smilehip_spectral_op_create: null argument");
-  const int n_out = smilehip_spectral_opts_count(o);
-  if (n_out < 1) return fail(SMILEHIP_ERR_INVALID, "smilehip_spectral_op_create: 0 .. 16 bands, 0 .. 16 rollOff points, at least one output");
-  if (K < 8 || K > (1 << 20) || !(frame_size_sec > 0.0)) return fail(SMILEHIP_ERR_INVALID, "smilehip_spectral_op_create: K %lld, frame size %g s", (long long)K, frame_size_sec);
-  for (int b = 0; b < o->n_bands; ++b)
-    if (o->band_lo[b] < 0 || o->band_hi[b] <= o->band_lo[b]) return fail(SMILEHIP_ERR_INVALID, "cSpectral bands[%d] = %d-%d", b, o->band_lo[b], o->band_hi[b]);
-  for (int i = 0; i < o->n_rolloff; ++i)
-    if (!(o->rolloff[i] >= 0.0 && o->rolloff[i] <= 1.0)) return fail(SMILEHIP_ERR_INVALID, "cSpectral rollOff[%d] = %g", i, o->rolloff[i]);
-  smilehip_spectral_op *op = new smilehip_spectral_op;
-  op->ctx = ctx;
-  op->n_out = n_out;
-  SpectralGeneral &G = op->G;
-  std::memset(&G, 0, sizeof(G));
-  G.K = (int32_t)K;
-  G.frame_size_sec = frame_size_sec;
-  G.n_bands = o->n_bands; G.n_rolloff = o->n_rolloff;
-  for (int i = 0; i < o->n_rolloff; ++i) G.rolloff[i] = o->rolloff[i];
-  G.flux = o->flux != 0; G.centroid = o->centroid != 0; G.max_pos = o->max_pos != 0; G.min_pos = o->min_pos != 0;
-  G.entropy = o->entropy != 0; G.variance = o->variance != 0; G.skewness = o->skewness != 0; G.kurtosis = o->kurtosis != 0;
-  G.slope = o->slope != 0; G.sharpness = o->sharpness != 0; G.harmonicity = o->harmonicity != 0;
-  G.flatness = o->flatness != 0; G.log_flatness = o->log_flatness != 0;
-  G.spec_diff = o->spec_diff != 0; G.spec_pos_diff = o->spec_pos_diff != 0; G.flux_centroid = o->flux_centroid != 0;
-  G.flux_at_flux_centroid = o->flux_at_flux_centroid != 0; G.standard_deviation = o->standard_deviation != 0;
-  G.n_out = n_out; G.n_slopes = o->n_slopes;
-  const int Nsrc = (int)K;
-  const double F0 = 1.0 / frame_size_sec;                // frq[i] = F0 * i, transformFft.cpp:102-117
-  for (int b = 0; b < o->n_bands + o->n_slopes; ++b) {    // a band's (spectral.cpp:779-826) or a slope band's (:872-943: the same mapping) edge bins and weights
-    const bool is_slope = b >= o->n_bands;
-    const int lo = is_slope ? o->slope_lo[b - o->n_bands] : o->band_lo[b], hi = is_slope ? o->slope_hi[b - o->n_bands] : o->band_hi[b];
-    if (is_slope && (lo < 0 || hi <= lo)) { delete op; return fail(SMILEHIP_ERR_INVALID, "cSpectral slopes[%d] = %d-%d", b - o->n_bands, lo, hi); }
-    int ii;
-    double wghtL, wghtR, idxL, idxR;
-    for (ii = 0; ii < Nsrc; ii++) if (F0 * ii > (double)lo) break;
-    if ((ii < Nsrc) && (ii > 0)) wghtL = (F0 * ii - (double)lo) / (F0 * ii - F0 * (ii - 1)); else wghtL = 1.0;
-    idxL = (double)ii - 1.0;
-    if (idxL < 0) idxL = 0;
-    if (idxL >= Nsrc) idxL = Nsrc;
-    if (wghtL == 0.0) wghtL = 1.0;
-    for (ii = 0; ii < Nsrc; ii++) if (F0 * ii >= (float)hi) break;
-    if ((ii < Nsrc) && (ii > 0)) wghtR = ((double)hi - F0 * (ii - 1)) / (F0 * ii - F0 * (ii - 1)); else wghtR = 1.0;
-    if ((ii < Nsrc) && (F0 * ii == (float)hi)) idxR = (double)ii; else idxR = (double)ii - 1.0;
-    if (idxR >= Nsrc) idxR = Nsrc - 1;
-    if (wghtR == 0.0) wghtR = 1.0;
-    int iL = (int)std::floor(idxL), iR = (int)std::floor(idxR);
-    if (iL >= Nsrc) { iL = iR = Nsrc - 1; wghtR = 0.0; wghtL = 0.0; }
-    if (iR >= Nsrc) { iR = Nsrc - 1; wghtR = 1.0; }
-    if (iL < 0) iL = 0;
-    if (iR < 0) iR = 0;
-    if (iR < iL) { delete op; return fail(SMILEHIP_ERR_INVALID, "cSpectral %s[%d] = %d-%d lies between two bins of this spectrum", is_slope ? "slopes" : "bands", is_slope ? b - o->n_bands : b, lo, hi); }
-    if (is_slope) {
-      const int k = b - o->n_bands;
-      G.sl_iL[k] = iL; G.sl_iR[k] = iR; G.sl_wL[k] = wghtL; G.sl_wR[k] = wghtR; G.sl_Nind[k] = idxR - idxL;
-    } else {
-      G.band_iL[b] = iL; G.band_iR[b] = iR; G.band_wL[b] = wghtL; G.band_wR[b] = wghtR;
-    }
-  }
-  for (int64_t i = 1; i < K; ++i) { G.slope_S2f += (F0 * i) * (F0 * i); G.slope_Sf += F0 * i; }
-  std::vector<double> sw((size_t)(K - 1));                // sharpness weights bark(f) g(bark(f)), spectral.cpp:1440-1455, smileUtil.c:1063-1078, 1123-1137
-  for (int64_t j = 1; j < K; ++j) {
-    const double x = F0 * double(j);
-    double zz = 0.0;
-    if (x > 0) {
-      zz = (26.81 / (1.0 + 1960.0 / x)) - 0.53;
-      if (zz < 2) zz = 0.85 * zz + 0.3;
-      else if (zz > 20.1) zz = 1.22 * zz - 0.22 * 20.1;
-    }
-    const double g = (zz <= 16.0) ? 1.0 : std::pow((zz - 16.0) / 4.0, 1.5849625) + 1.0;
-    sw[(size_t)(j - 1)] = zz * g;
-  }
-  const int rc = op->d_sharp.upload(sw);
-  if (rc) { delete op; return rc; }
-  G.sharp_w = op->d_sharp.p;
-  *out = op;
-  return SMILEHIP_OK;
-}
-extern "C" int smilehip_spectral_op_frames(smilehip_spectral_op *op, const float *d_mag, int64_t ld_src, float *d_state, int first,
-                                           float *d_dst, int64_t ld_dst, int64_t n_frames, void *stream) {
-  if (!op) return fail(SMILEHIP_ERR_INVALID, "smilehip_spectral_op_frames: null operator");
-  if (n_frames < 0 || ld_src < op->G.K || ld_dst < op->n_out || (n_frames > 0 && (!d_mag || !d_dst)) ||
-      ((op->G.flux || op->G.spec_diff || op->G.spec_pos_diff || op->G.flux_centroid || op->G.flux_at_flux_centroid) && !d_state))
-    return fail(SMILEHIP_ERR_INVALID, "smilehip_spectral_op_frames: bad argument (K %d, %d outputs; d_state is needed when flux is on)", op->G.K, op->n_out);
-  STAGE_RET(stage_spectral_general(op->G, d_mag, ld_src, d_state, first, d_dst, ld_dst, n_frames, (hipStream_t)stream), "spectral (general)");
-}
 
-// ---- cSpectral on any spectrum (spectral.cpp:586-1555 with the options smilehip_spectral_op_* fixes, and the level's own axis):
-// make_spectral_axis_tables holds everything that follows from the options and the axis
+// ---- cSpectral on any spectrum (spectral.cpp:586-1555 with every option free, and the level's own axis): make_spectral_axis_tables holds
+// everything that follows from the options and the axis
 struct smilehip_spectral_axis_op {
   smilehip_context *ctx = nullptr;
   SpectralAxisDev G{};
@@ -237,6 +140,31 @@ extern "C" int smilehip_spectral_axis_op_frames(smilehip_spectral_axis_op *op, c
     return fail(SMILEHIP_ERR_INVALID, "smilehip_spectral_axis_op_frames: bad argument (K %d, %d outputs; d_state is needed when flux is on)", G.K, G.n_out);
   STAGE_RET(stage_spectral_axis(G, d_src, ld_src, d_state, first, d_dst, ld_dst, n_frames, (hipStream_t)stream), "spectral (axis)");
 }
+
+// ---- the same operator behind the older entry points: the options every shipped linear set leaves alone at their fixed values, on the
+// axis cTransformFFT attaches to a magnitude level (frq[i] = i / frameSizeSec, transformFft.cpp:102-117). A smilehip_spectral_op IS
+// a smilehip_spectral_axis_op.
+static smilehip_spectral_axis_op *axis_op(const smilehip_spectral_op *op) { return (smilehip_spectral_axis_op *)op; }
+extern "C" int smilehip_spectral_op_create(smilehip_context *ctx, const smilehip_spectral_opts *o, int64_t K, double frame_size_sec,
+                                           smilehip_spectral_op **out) {
+  if (!ctx || !o || !out) return fail(SMILEHIP_ERR_INVALID, "smilehip_spectral_op_create: null argument");
+  smilehip_spectral_axis_opts ao;
+  std::memset(&ao, 0, sizeof(ao));
+  ao.base = *o;
+  ao.square_input = 1;
+  ao.old_slope_scale = 1;
+  ao.frq_scale = SMILEHIP_SPECSCALE_LINEAR;
+  const double F0 = 1.0 / frame_size_sec;
+  std::vector<double> frq((size_t)std::min<int64_t>(std::max<int64_t>(K, 0), 1 << 20));   // (a K out of range is refused before the axis is read)
+  for (size_t i = 0; i < frq.size(); ++i) frq[i] = F0 * (double)i;
+  return smilehip_spectral_axis_op_create(ctx, &ao, K, frame_size_sec, frq.data(), (int64_t)frq.size(), (smilehip_spectral_axis_op **)out);
+}
+extern "C" int smilehip_spectral_op_n_out(const smilehip_spectral_op *op) { return smilehip_spectral_axis_op_n_out(axis_op(op)); }
+extern "C" int smilehip_spectral_op_frames(smilehip_spectral_op *op, const float *d_mag, int64_t ld_src, float *d_state, int first,
+                                           float *d_dst, int64_t ld_dst, int64_t n_frames, void *stream) {
+  return smilehip_spectral_axis_op_frames(axis_op(op), d_mag, ld_src, d_state, first, d_dst, ld_dst, n_frames, stream);
+}
+extern "C" int smilehip_spectral_op_destroy(smilehip_spectral_op *op) { return smilehip_spectral_axis_op_destroy(axis_op(op)); }
 
 // ---- cSpecScale on any target scale: an operator object (the axes and the spline's caches are functions of the options and the
 // level's geometry alone: cSpecScale::dataProcessorCustomFinalise, src/dsp/specScale.cpp:248-321)

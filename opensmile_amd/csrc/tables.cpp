@@ -501,7 +501,7 @@ int make_spectral_axis_tables(const smilehip_spectral_axis_opts &o, int64_t K, d
   if (!why) why = &dummy;
   *why = "";
   const smilehip_spectral_opts &b = o.base;
-  if (K < 4 || K > 8193) { *why = "K: 4 .. 8193 bins are built"; return SMILEHIP_ERR_INVALID; }
+  if (K < 4 || K > (1 << 20)) { *why = "K: 4 .. 1048576 bins are built"; return SMILEHIP_ERR_INVALID; }
   if (!(frame_size_sec > 0.0)) { *why = "frame_size_sec: the level's frameSizeSec must be positive"; return SMILEHIP_ERR_INVALID; }
   if (o.tonality) { *why = "tonality: not implemented in the reference (it writes 0 and prints an error)"; return SMILEHIP_ERR_INVALID; }
   if (b.n_bands < 0 || b.n_bands > 16) { *why = "bands: 0 .. 16 are built"; return SMILEHIP_ERR_INVALID; }

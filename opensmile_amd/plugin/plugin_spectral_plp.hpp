@@ -11,12 +11,9 @@ class cHipSpectral : public BlockVP<cSpectral> {
   smilehip_plan *gm_plan_ = nullptr;
   int band_lo_[2] = {250, 1000}, band_hi_[2] = {650, 4000};
   bool sel_[3] = {true, true, true};
-  // the general option set (smilehip_spectral_op_*: any bands / rollOff points, every descriptor optional): one operator per field
-  int general_ = -1, gen_n_out_ = 0;
-  smilehip_spectral_opts gen_opts_;
-  smilehip_spectral_op *gen_op_[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  // every other option set (smilehip_spectral_axis_op_*: log spectrum, freqRange, normBandEnergies, alphaRatio / hammarbergIndex, power
-  // input, the new slope scale, the old roll-off, any frequency axis): one operator per field
+  // every other option set (smilehip_spectral_axis_op_*: any bands / slopes / rollOff points, every descriptor optional, linear or log
+  // spectrum, freqRange, normBandEnergies, alphaRatio / hammarbergIndex, power input, either slope scale, the old roll-off, any
+  // frequency axis): one operator per field
   int axis_ = -1, ax_n_out_ = 0;
   std::string ax_why_;
   smilehip_spectral_axis_opts ax_opts_;
@@ -108,55 +105,9 @@ class cHipSpectral : public BlockVP<cSpectral> {
       return (int)Ndst;
     }
     const bool compare_set = plain_ && (Nsrc == 129 || Nsrc == 257 || Nsrc == 513) && Ndst == 12 + (int)sel_[0] + (int)sel_[1] + (int)sel_[2];
-    if (!compare_set && general_ < 0) {
-      // everything the linear-spectrum branch of spectral.cpp:586-1560 offers except the alphaRatio / hammarbergIndex / tonality outputs
-      // (round 6: + slopes[], specDiff, specPosDiff, fluxCentroid, fluxAtFluxCentroid, standardDeviation)
-      std::memset(&gen_opts_, 0, sizeof(gen_opts_));
-      const int nb = getArraySize("bands") > 0 ? getArraySize("bands") : 0, nr = getArraySize("rollOff") > 0 ? getArraySize("rollOff") : 0;
-      const int nsl = getArraySize("slopes") > 0 ? getArraySize("slopes") : 0;
-      bool ok = nb <= 16 && nr <= 16 && nsl <= 16;
-      for (int b = 0; ok && b < nsl; ++b) {              // slopes[b] = "lo-hi" in Hz, integers (spectral.cpp:327-338)
-        const char *v = getStr_f(myvprint("slopes[%i]", b));
-        int lo = -1, hi = -1, used = 0;
-        ok = v && sscanf(v, "%d-%d%n", &lo, &hi, &used) == 2 && v[used] == 0 && lo >= 0 && hi > lo;
-        gen_opts_.slope_lo[b] = lo; gen_opts_.slope_hi[b] = hi;
-      }
-      gen_opts_.n_slopes = nsl;
-      gen_opts_.spec_diff = getInt("specDiff"); gen_opts_.spec_pos_diff = getInt("specPosDiff"); gen_opts_.flux_centroid = getInt("fluxCentroid");
-      gen_opts_.flux_at_flux_centroid = getInt("fluxAtFluxCentroid"); gen_opts_.standard_deviation = getInt("standardDeviation");
-      for (int b = 0; ok && b < nb; ++b) {               // bands[b] = "lo-hi" in Hz, integers (spectral.cpp:163-190)
-        const char *v = getStr_f(myvprint("bands[%i]", b));
-        int lo = -1, hi = -1, used = 0;
-        ok = v && sscanf(v, "%d-%d%n", &lo, &hi, &used) == 2 && v[used] == 0 && lo >= 0 && hi > lo;
-        gen_opts_.band_lo[b] = lo; gen_opts_.band_hi[b] = hi;
-      }
-      for (int i = 0; ok && i < nr; ++i) gen_opts_.rolloff[i] = getDouble_f(myvprint("rollOff[%i]", i));
-      gen_opts_.n_bands = nb; gen_opts_.n_rolloff = nr;
-      gen_opts_.flux = getInt("flux"); gen_opts_.centroid = getInt("centroid"); gen_opts_.max_pos = getInt("maxPos"); gen_opts_.min_pos = getInt("minPos");
-      gen_opts_.entropy = getInt("entropy"); gen_opts_.variance = getInt("variance"); gen_opts_.skewness = getInt("skewness");
-      gen_opts_.kurtosis = getInt("kurtosis"); gen_opts_.slope = getInt("slope"); gen_opts_.sharpness = getInt("sharpness");
-      gen_opts_.harmonicity = getInt("harmonicity"); gen_opts_.flatness = getInt("flatness"); gen_opts_.log_flatness = getInt("logFlatness");
-      static const char *const off[] = {"normBandEnergies", "alphaRatio", "hammarbergIndex", "tonality", "buggyRollOff", "useLogSpectrum"};
-      for (const char *o : off) ok = ok && getInt(o) == 0;
-      ok = ok && getInt("squareInput") != 0 && ((!gen_opts_.slope && !nsl) || getInt("oldSlopeScale") != 0);
-      const char *fr = getStr("freqRange");
-      ok = ok && fr && !strcmp(fr, "0-0");
-      gen_n_out_ = ok ? smilehip_spectral_opts_count(&gen_opts_) : 0;
-      general_ = (ok && gen_n_out_ > 0) ? 1 : 0;
-    }
-    if (!compare_set && general_ == 1 && Nsrc >= 9 && ((Nsrc - 1) & (Nsrc - 2)) == 0 && Ndst == gen_n_out_ && fc >= 0 && fc < 8) {   // (2^k + 1 bins: an FFT magnitude level, linear axis)
-      if (!gen_op_[fc]) check(smilehip_spectral_op_create(context(), &gen_opts_, Nsrc, reader_->getLevelConfig()->frameSizeSec, &gen_op_[fc]));
-      io_.ensure(Nsrc, gen_n_out_);
-      io_.up(src, Nsrc);
-      float *d_prev = (float *)prev_[fc].ensure(sizeof(float) * (uint64_t)Nsrc);
-      check(smilehip_spectral_op_frames(gen_op_[fc], io_.d_in, Nsrc, d_prev, seen_[fc] ? 0 : 1, io_.d_out, gen_n_out_, g_blk.n, nullptr));
-      seen_[fc] = true;
-      io_.down(dst, gen_n_out_);
-      g_frames[12] += g_blk.n;
-      return (int)Ndst;
-    }
     if (!compare_set && axis_ < 0) {
-      // everything else spectral.cpp:586-1555 offers, on whatever level the instance reads
+      // everything spectral.cpp:586-1555 offers beside the ComParE and GeMAPS sets, on whatever level the instance reads: its own axis from the frame
+      // meta data (on an FFT magnitude level frq[i] = i / frameSizeSec), the index-based branches where there is none
       std::memset(&ax_opts_, 0, sizeof(ax_opts_));
       smilehip_spectral_opts &b = ax_opts_.base;
       const int nb = getArraySize("bands") > 0 ? getArraySize("bands") : 0, nr = getArraySize("rollOff") > 0 ? getArraySize("rollOff") : 0;
@@ -191,7 +142,7 @@ class cHipSpectral : public BlockVP<cSpectral> {
       if (ax_why_.empty() && ax_n_out_ < 1) ax_why_ = "an instance without outputs";
       axis_ = ax_why_.empty() ? 1 : 0;
     }
-    if (!compare_set && axis_ == 1 && Nsrc >= 4 && Nsrc <= 8193 && Ndst == ax_n_out_ && fc >= 0 && fc < 8) {
+    if (!compare_set && axis_ == 1 && Nsrc >= 4 && Nsrc <= (1 << 20) && Ndst == ax_n_out_ && fc >= 0 && fc < 8) {
       if (!ax_op_[fc]) {
         if (ax_n_scale_ < 0) {                             // spectral.cpp:595-612: the axis of the field that comes first, kept for all
           const FrameMetaInfo *fmeta = reader_->getFrameMetaInfo();
@@ -218,7 +169,7 @@ class cHipSpectral : public BlockVP<cSpectral> {
         }
       }
     }
-    if (!compare_set && axis_ == 1 && Nsrc >= 4 && Nsrc <= 8193 && Ndst == ax_n_out_ && fc >= 0 && fc < 8 && ax_op_[fc]) {
+    if (!compare_set && axis_ == 1 && Nsrc >= 4 && Nsrc <= (1 << 20) && Ndst == ax_n_out_ && fc >= 0 && fc < 8 && ax_op_[fc]) {
       io_.ensure(Nsrc, ax_n_out_);
       io_.up(src, Nsrc);
       float *d_prev = (float *)prev_[fc].ensure(sizeof(float) * (uint64_t)Nsrc);
@@ -229,7 +180,7 @@ class cHipSpectral : public BlockVP<cSpectral> {
       return (int)Ndst;
     }
     if (!compare_set || fc < 0 || fc >= 8) {
-      const std::string why = "cSpectral: " + (ax_why_.empty() ? std::string("more than 8 input fields, fewer than 4 or more than 8193 bins, or an output count the options do not give") : ax_why_) +
+      const std::string why = "cSpectral: " + (ax_why_.empty() ? std::string("more than 8 input fields, fewer than 4 or more than 1048576 bins, or an output count the options do not give") : ax_why_) +
                               " is not built (every other option of the component is)";
       HIP_FALLTHROUGH(12, why.c_str());
       return cSpectral::processVector(src, dst, Nsrc, Ndst, idxi);
@@ -263,7 +214,6 @@ class cHipSpectral : public BlockVP<cSpectral> {
   explicit cHipSpectral(const char *n) : BlockVP<cSpectral>(n) {}
   ~cHipSpectral() override {
     if (gm_plan_) smilehip_plan_destroy(gm_plan_);
-    for (auto *op : gen_op_) if (op) smilehip_spectral_op_destroy(op);
     for (auto *op : ax_op_) if (op) smilehip_spectral_axis_op_destroy(op);
   }
   static cSmileComponent *create(const char *n) {

@@ -836,7 +836,7 @@ def _run_bytes(oracle, pcm, env_extra, conf, out_opt="-O"):
                                   "mediaeval12/MediaEval_Audio_IS12based_subwin2.conf"])
 def test_plugin_general_spectral_sets(oracle, conf):
     """The shipped files whose cSpectral instance asks for another descriptor set than ComParE_2016's or GeMAPS' (four bands, maxPos /
-    minPos, no centroid ...): the general operator (smilehip_spectral_op_*) takes them -- the file the plugin run writes equals the
+    minPos, no centroid ...): the any-axis operator (smilehip_spectral_axis_op_*) takes them on the level's own FFT axis -- the file the plugin run writes equals the
     plain binary's byte for byte, and nothing ran on the CPU."""
     from opensmile_amd import synth
     pcm = synth.utterance(71, 24000)

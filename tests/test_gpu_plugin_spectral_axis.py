@@ -1,6 +1,6 @@
 """cSpectral on any spectrum inside the UNMODIFIED reference binary (oracle/_ref/SMILExtract) through the plugin, every override on
 and no component on the reference's CPU code: the file the run writes equals the plain binary's byte for byte. Both graphs hold
-cSpectral instances that the three older routes (ComParE's set, the two GeMAPS sets, the linear general set) do not take; before
+cSpectral instances that the wave-parallel routes (ComParE's set, the two GeMAPS sets) do not take; before
 smilehip_spectral_axis_op_* such a run ended with the plugin's cSpectral refusal."""
 import os
 import shutil

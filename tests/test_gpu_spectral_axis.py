@@ -1,6 +1,7 @@
 """cSpectral on any spectrum on the device (smilehip_spectral_axis_op_*, csrc/lld_spectral_axis.hip): against the real binary's levels
 (tests/golden/spectral_axis_synth.npz), against the numpy restatement of tests/test_spectral_axis_host.py (which that file holds
-bit-equal to the same goldens), and against the two older operators on the option sets they share. The kernel's operations are the
+bit-equal to the same goldens), against the oracle's cSpectral for the linear option sets, and against the GeMAPS operator on
+the option sets the two share. The kernel's operations are the
 reference's correctly rounded operations in its order and the tables come from the same C library: everything is compared bit for
 bit (both-zero counts as equal)."""
 import ctypes as C
@@ -106,7 +107,7 @@ SETS = {
 # (K, rows): every K of the issue; 1, 63, 64, 65 and 130 rows around the 64 frames of a workgroup; 26, 32 and 33 bins around the
 # 32-bin tile of the LDS-staged variant that was measured against this kernel (narrower, as wide, one bin wider), 257 and up many
 # tiles wide. The large sizes take the small row counts: the restatement is a Python loop per row.
-SHAPES = ((4, 130), (9, 64), (26, 65), (32, 65), (33, 64), (257, 63), (257, 130), (1025, 65), (8193, 1))
+SHAPES = ((4, 130), (9, 64), (26, 65), (32, 65), (33, 64), (257, 63), (257, 130), (1025, 65), (8193, 1), (16385, 1))
 
 
 def spectra(K, rows, seed, power=False):
@@ -181,7 +182,7 @@ def test_stream_carry(env, which):
     assert_bits(run_op(env, o, x, fs, frq, pieces=[1, 1, 5, 2, 15]), ref, "pieces")
 
 
-# ---- consistency with the existing operators
+# ---- consistency with the oracle of the linear sets and with the GeMAPS operator
 OLD_SETS = {
     "mediaeval": ([(40, 150), (250, 650), (1000, 4000), (5000, 15000)], (0.25, 0.5, 0.75, 0.9), (),
                   dict(flux=1, centroid=1, entropy=1, variance=1, skewness=1, kurtosis=1, slope=1, harmonicity=1, sharpness=1)),
@@ -193,29 +194,17 @@ OLD_SETS = {
 
 @pytest.mark.parametrize("K", [129, 257])
 @pytest.mark.parametrize("name", list(OLD_SETS))
-def test_equals_the_general_operator(env, name, K):
-    """linear options: the same bits as smilehip_spectral_op_frames. That operator is cSpectral on an FFT magnitude level, whose
-    axis cTransformFFT attaches (frq[i] = i / frameSizeSec, transformFft.cpp:102-117): it IS the axis form on that axis, so that
-    axis is what the new operator gets here (without one the reference takes its index-based branches: another roll-off
-    rounding, a running-sum centroid axis)."""
-    torch, capi, ctx = env
-    L = capi.load()
+def test_equals_the_general_oracle(env, name, K, oracle):
+    """linear options: the same bits as the oracle's lldo_spectral_general, which tests/test_oracle_pin_spectral_sets.py pins on the
+    real binary. That is cSpectral on an FFT magnitude level, whose axis cTransformFFT attaches (frq[i] = i / frameSizeSec,
+    transformFft.cpp:102-117), so that axis is what the operator gets here (without one the reference takes its index-based
+    branches: another roll-off rounding, a running-sum centroid axis)."""
     bands, rolloff, slopes, flags = OLD_SETS[name]
     fs = 2.0 * (K - 1) / 16000.0
     x = spectra(K, 70, 3)
-    oo = capi.spectral_opts(bands, rolloff, slopes, **flags)
-    op = C.c_void_p()
-    capi._check(L.smilehip_spectral_op_create(ctx._h, C.byref(oo), K, fs, C.byref(op)))
-    no = L.smilehip_spectral_op_n_out(op)
-    d_src = torch.from_numpy(x).cuda()
-    d_dst = torch.zeros((70, no), dtype=torch.float32, device="cuda")
-    d_state = torch.zeros((K,), dtype=torch.float32, device="cuda")
-    capi._check(L.smilehip_spectral_op_frames(op, d_src.data_ptr(), K, d_state.data_ptr(), 1, d_dst.data_ptr(), no, 70, None))
-    torch.cuda.synchronize()
-    old = d_dst.cpu().numpy()
-    capi._check(L.smilehip_spectral_op_destroy(op))
+    want = oracle.spectral_general_rows(x, fs, bands, rolloff, slopes=slopes, **flags)
     o = opts(bands=tuple(bands), rolloff=rolloff, slopes=tuple(slopes), **flags)
-    assert_bits(run_op(env, o, x, fs, np.arange(K, dtype=f64) / fs), old, name)
+    assert_bits(run_op(env, o, x, fs, np.arange(K, dtype=f64) / fs), want, name)
 
 
 def test_equals_the_gemaps_operator(env, golden):
@@ -246,7 +235,7 @@ REFUSALS = {
     "bands": (opts(bands=((650, 250),)), 16, None),
     "slopes": (opts(slopes=((5, 5),)), 16, None),
     "rollOff": (opts(rolloff=(1.5,)), 16, None),
-    "K": (opts(flux=1), 8194, None),
+    "K": (opts(flux=1), (1 << 20) + 1, None),
 }
 
 

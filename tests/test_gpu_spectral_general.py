@@ -1,4 +1,5 @@
-"""R11, general option set on the device (smilehip_spectral_op_*, csrc/lld_spectral_general.hip) against the oracle's
+"""R11, general option set on the device (smilehip_spectral_op_*: the any-axis operator of csrc/lld_spectral_axis.hip with squareInput
+and oldSlopeScale on, everything else off, on the FFT axis i / frameSizeSec) against the oracle's
 lldo_spectral_general, which tests/test_oracle_pin_spectral_sets.py pins bit for bit on the real binary's own cSpectral levels of
 avec2011, emo_large and the MediaEval files: the same three option sets, a few more (every flag alone, no band, sixteen bands),
 spectra of speech-like frames plus an all-zero and a constant one, the frames of a stream in one launch and frame by frame

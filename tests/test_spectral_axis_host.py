@@ -128,7 +128,7 @@ def n_out(o):
 
 def ref_setup(o, K, fs_sec, frq=None):
     """what processVector derives from the options and the axis before it looks at a spectrum; frq: K doubles or None"""
-    if not 4 <= K <= 8193 or not fs_sec > 0.0 or o["tonality"]:
+    if not 4 <= K <= 1 << 20 or not fs_sec > 0.0 or o["tonality"]:
         raise Refused("K / frame size / tonality")
     if len(o["bands"]) > 16 or len(o["slopes"]) > 16 or len(o["rolloff"]) > 16 or n_out(o) < 1:
         raise Refused("counts")
@@ -582,7 +582,7 @@ def lib_tables(o, K, fs_sec, frq=None, n_scale=None):
     L = capi.load()
     kw = {k: v for k, v in o.items() if k not in ("bands", "slopes", "rolloff")}
     co = capi.spectral_axis_opts(o["bands"], o["rolloff"], o["slopes"], **kw)
-    geo, edges, sums, sharp = np.zeros(12, np.int32), np.zeros((32, 5)), np.zeros(2), np.zeros(8193)
+    geo, edges, sums, sharp = np.zeros(12, np.int32), np.zeros((32, 5)), np.zeros(2), np.zeros(max(K, 4))
     fa = None if frq is None else np.ascontiguousarray(frq, f64)
     ns = (0 if fa is None else fa.size) if n_scale is None else n_scale
     rc = L.smilehip_spectral_axis_tables(C.byref(co), K, fs_sec, None if fa is None else fa.ctypes.data, ns, geo.ctypes.data, edges.ctypes.data,
@@ -618,7 +618,7 @@ AXIS_FREE = opts(bands=((250, 650), (0, 90), (7000, 9000)), slopes=((0, 500), (5
                  hammarberg_index=1, centroid=1, slope=1, sharpness=1, variance=1)
 
 
-@pytest.mark.parametrize("K", [4, 9, 26, 257, 1025, 8193])
+@pytest.mark.parametrize("K", [4, 9, 26, 257, 1025, 8193, 16385])
 @pytest.mark.parametrize("ctr", [0, 1])
 def test_table_builder_without_an_axis(K, ctr):
     """the index-based branches; the sharpness weights continue the centroid's running f (spectral.cpp:1261, :1291-1294, :1464-1466)"""
@@ -652,6 +652,7 @@ REFUSALS = {
     "specFloor": dict(o=opts(flux=1, use_log_spectrum=1, spec_floor=0.0), K=16, frq=None),
     "bands": dict(o=opts(bands=((650, 250),)), K=16, frq=None),
     "K": dict(o=opts(flux=1), K=3, frq=None),
+    "K:": dict(o=opts(flux=1), K=(1 << 20) + 1, frq=None),
 }
 
 
