@@ -77,14 +77,18 @@ constexpr int kWavesPerBlock = 8;
 constexpr int kTileFrames = 32;       // frames per wave tile (8 passes)
 constexpr int kTB2Row = 65;           // float2 per 4-group row of the transpose buffer (520 B)
 constexpr int kTB2Floats = 2 * (15 * kTB2Row + 3 * 16 + 16);   // 2078 floats: footprint of the transpose buffer
-constexpr int kLmelFloats = 64;       // per frame group: log-mel [32] | PLP acf [16] | PLP cepstra [16]
+constexpr int kLmelFloats = 68;       // per frame group: log-mel [32] | PLP acf [16] | PLP cepstra [16] | 4 floats that move the next
+                                      // group's vector one bank quad on: a b128 lane group spans two frame groups, whose
+                                      // broadcast reads of the DCT met on one quad at 64 (tools/lds_bank_sim.py)
 constexpr int kOctetFloats = 12;      // an octet of power bins starts every 12 floats: octet o sits on bank quad 3 o mod 16
 constexpr int kPbFloats = 448;        // power buffer of one frame group (33 octets = 396 floats) rounded to a multiple of 64
                                       // dwords: the four groups of a wave see the same banks
-constexpr int kWaveFloats = 2080;     // per-wave LDS: max(transpose buffer, 4 x (kLmelFloats + kPbFloats) = 2048), 16-byte multiple
+constexpr int kWaveFloats = 2080;     // per-wave LDS: max(transpose buffer, 4 x (kLmelFloats + kPbFloats) = 2064), 16-byte multiple
 
 static_assert(kWaveFloats >= kTB2Floats && kWaveFloats >= 4 * (kLmelFloats + kPbFloats) && kWaveFloats % 4 == 0, "per-wave LDS region");
 static_assert(kPbFloats % 64 == 0 && kPbFloats >= 33 * kOctetFloats, "power buffer");
+static_assert(kLmelFloats >= 64 && kLmelFloats % 4 == 0 && (kLmelFloats / 4) % 2 == 1,
+              "band vectors: room for the PLP vectors at +32 and +48, 16-byte aligned, neighbouring groups on different bank quads");
 
 constexpr float C1 = 0.92387953251128673848f;   // cos(pi/8)
 constexpr float S1 = 0.38268343236508978178f;   // sin(pi/8)
@@ -906,6 +910,11 @@ int fast512_build_host(const smilehip_lld_config &cfg, const Geometry &geo, cons
         h.melo[idx] = uint32_t(o) * uint32_t(kOctetFloats * 4);
       }
     }
+  }
+  if (getenv("SMILEHIP_DEBUG_TABLES")) {             // the table tools/lds_bank_sim.py prices the power-buffer reads with
+    fprintf(stderr, "fast512: unit octets [step][lane]:");
+    for (size_t idx = 0; idx < h.melo.size(); ++idx) fprintf(stderr, " %u", h.melo[idx] / uint32_t(kOctetFloats * 4));
+    fprintf(stderr, "\n");
   }
   for (size_t l = 0; l < lanes.size(); ++l) {
     uint32_t mask = 0;
