@@ -65,13 +65,34 @@ __device__ __forceinline__ float seq_sum_f32(const float *x, int lo, int hi) {
   return s;
 }
 
+// sum of x[0 .. n) in index order, one double addition after the other (n even, x 16-byte aligned); the loads run a block ahead.
+// For the one double sum of cSpectral whose terms cancel: the third central moment (skewness, spectral.cpp:1344-1364) of a flat
+// spectrum -- a single click inside digital silence -- is rounding noise only, so the ORDER of the additions decides every bit of
+// the result; the sums of one-signed terms (energy, centroid, variance, kurtosis, entropy, flux) keep their fixed trees. (The slope
+// is a difference of two of those and cancels on a flat spectrum as well; it came out the binary's on every hard signal
+// (tests/test_gpu_hard_signals.py) and stays as it is. Cost of the chain: the W = 8 wave kernel of 32 .. 48 kHz input holds the
+// W terms across the float chains, 169 registers, two waves per SIMD instead of three.)
+__device__ __forceinline__ double seq_sum_f64(const double *x, int n) {
+  double s = 0.0;
+  double2 u = *reinterpret_cast<const double2 *>(x);
+  for (int i = 2; i <= n; i += 2) {
+    double2 un = u;                                      // the next block's load is in flight while this block's adds run
+    if (i < n) un = *reinterpret_cast<const double2 *>(x + i);
+    s += u.x;
+    s += u.y;
+    u = un;
+  }
+  return s;
+}
+
 // R11 cSpectral::processVector with ComParE_2016's option set ([is13_spectral]: bands 250-650 and
 // 1000-4000, roll-off .25/.5/.75/.9, flux, centroid, entropy, variance, skewness, kurtosis, slope,
 // sharpness, harmonicity; squareInput = 1, freqRange 0-0, oldSlopeScale = 1; spectral.cpp:586-1560).
 // Thread i of 256 owns bin j = i+1. mg / pw: magnitudes and powers of the K = 257 bins, prev: the
 // previous frame's magnitudes (ignored when first). red: 64 doubles, cum: 256 doubles, pk_val[4],
 // pk_has[4] of LDS scratch. Writes sp[0..14]; thread 0 returns valid frameSum-based values; ends
-// with a block barrier. The sums are double like the reference's, combined in a fixed tree order.
+// with a block barrier. The sums are double like the reference's, combined in a fixed tree order (the third moment's terms
+// cancel: thread 0 adds them bin after bin, seq_sum_f64).
 __device__ __forceinline__ void spectral_frame(const float *mg, const float *pw, const float *prev, bool first,
                                                const SpectralConsts &C, int K, double *red, double *cum, float *pk_val,
                                                int *pk_has, float *sp) {
@@ -141,7 +162,7 @@ __device__ __forceinline__ void spectral_frame(const float *mg, const float *pw,
           if (pk_has[w]) { hc = fabsf(pf - pk_val[w]); break; }
     }
   }
-  double v2[5];
+  double v2[5], m3t;
   {                                                     // entropy (smileStat_entropy, smileUtil.c:2079-2124; powers: min = 0)
     const double entropy_floor = 0.0000001;
     double dn = frameSum;
@@ -152,7 +173,8 @@ __device__ __forceinline__ void spectral_frame(const float *mg, const float *pw,
     v2[0] = (ln > 0.0) ? ln * log_d(ln) / log(2.0) : 0.0;
     const double t1 = fj - (double)ctr;                 // moments (:1338-1397)
     double m = t1 * t1 * p;
-    v2[1] = m; m *= t1; v2[2] = m; v2[3] = m * t1;
+    v2[1] = m; m *= t1; m3t = m; v2[3] = m * t1;
+    v2[2] = 0.0;                                        // (third moment: a double chain, below)
     v2[4] = 0.0;                                        // (harmonicity: a float chain, below)
   }
   // sharpness and harmonicity accumulate in FLOAT_DMEM, bin after bin: the terms go to LDS (cum is free after the roll-off:
@@ -161,9 +183,13 @@ __device__ __forceinline__ void spectral_frame(const float *mg, const float *pw,
   chain[tid] = (float)(C.sharp_w[tid] * p);             // (FLOAT_DMEM)(sharpnessWeights[j - lo] * (double)srcP[j]), :1455 / :1469
   chain[256 + tid] = hc;                                // |srcLP[j] - lastPeak| of a flagged bin, +0 elsewhere (s + 0 = s), :1493
   block_sum_n<5>(v2, red);
+  float sumAA_seq = 0.0f, ptp_seq = 0.0f;
+  if (tid == 0) seq_sum2_f32(chain, chain + 256, 256, sumAA_seq, ptp_seq);
+  __syncthreads();                                      // (the float chains are consumed: the third moment's terms take their place)
+  cum[tid] = m3t;
+  __syncthreads();
   if (tid == 0) {
-    float sumAA_seq, ptp_seq;
-    seq_sum2_f32(chain, chain + 256, 256, sumAA_seq, ptp_seq);
+    const double mom3 = seq_sum_f64(cum, 256);
     sp[0] = (float)(v1[4] / (double)nBins);
     sp[1] = (float)(v1[5] / (double)nBins);
     float c2 = 0.0f;
@@ -177,7 +203,7 @@ __device__ __forceinline__ void spectral_frame(const float *mg, const float *pw,
     const double sumB = frameSum;
     const double sigma2 = (sumB != 0.0) ? v2[1] / sumB : 0.0;
     sp[9] = (float)sigma2;
-    sp[10] = (sigma2 <= 0.0) ? 0.0f : (float)(v2[2] / (sumB * sigma2 * sqrt(sigma2)));
+    sp[10] = (sigma2 <= 0.0) ? 0.0f : (float)(mom3 / (sumB * sigma2 * sqrt(sigma2)));
     sp[11] = (sigma2 == 0.0) ? 0.0f : (float)(v2[3] / (sumB * sigma2 * sigma2));
     const double Nind = (double)nBins;
     const double deno = (Nind * C.slope_S2f - C.slope_Sf * C.slope_Sf);
@@ -209,7 +235,8 @@ __device__ __forceinline__ void wave_sum4(const double (&v)[4][NV], double (&tot
 // by lane 0 (roll-off points by the lane that owns the crossing bin).
 // chain: 128 W floats of LDS scratch (16-byte aligned) for the two float chains.
 // (The sums are double accumulators of float-derived terms whose results are rounded to float: the reference adds bin after bin, any
-// other order differs from it by a few ulps of the DOUBLE and gives the same float except with probability ~1e-9 per value. Round 3:
+// other order differs from it by a few ulps of the DOUBLE and gives the same float except with probability ~1e-9 per value -- the
+// third moment excepted, whose terms cancel: its sum keeps the reference's order, seq_sum_f64. Round 3:
 // the lane's W terms are added first and ONE wave tree follows per quantity -- a quarter of the reductions of the block form's
 // per-group trees, which cost ~1200 of the kernel's ~4000 instruction slots per frame.)
 template <int NV, int W>
@@ -324,7 +351,7 @@ __device__ __forceinline__ void spectral_frame_wave(const float *mg, const float
       }
     }
   }
-  double v2[W][5];
+  double v2[W][5], m3t[W];
 #pragma unroll
   for (int w = 0; w < W; ++w) {
     const double entropy_floor = 0.0000001;
@@ -337,7 +364,8 @@ __device__ __forceinline__ void spectral_frame_wave(const float *mg, const float
     v2[w][0] = (ln > 0.0) ? ln * log_d<true>(ln, C.log_tab ? static_cast<const double2 *>(C.log_tab) : kLogTab) / log(2.0) : 0.0;
     const double t1 = fj[w] - (double)ctr;
     double m = t1 * t1 * p[w];
-    v2[w][1] = m; m *= t1; v2[w][2] = m; v2[w][3] = m * t1;
+    v2[w][1] = m; m *= t1; m3t[w] = m; v2[w][3] = m * t1;
+    v2[w][2] = 0.0;                                         // (third moment: a double chain, below)
     v2[w][4] = 0.0;
   }
   double t2v[5];
@@ -352,9 +380,18 @@ __device__ __forceinline__ void spectral_frame_wave(const float *mg, const float
   }
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
+  float sumAA_seq = 0.0f, ptp_seq = 0.0f;
+  if (lane == 0) seq_sum2_f32(chain, chain + 64 * W, 64 * W, sumAA_seq, ptp_seq);
+  // the third moment's terms take the float chains' place (128 W floats = 64 W doubles), bin after bin like the reference's loop
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  double *chain_d = reinterpret_cast<double *>(chain);
+#pragma unroll
+  for (int w = 0; w < W; ++w) chain_d[lane + 64 * w] = m3t[w];
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
   if (lane == 0) {
-    float sumAA_seq, ptp_seq;
-    seq_sum2_f32(chain, chain + 64 * W, 64 * W, sumAA_seq, ptp_seq);
+    const double mom3 = seq_sum_f64(chain_d, 64 * W);
     sp[0] = (float)(t1v[4] / (double)nBins);
     sp[1] = (float)(t1v[5] / (double)nBins);
     float c2 = 0.0f;
@@ -368,7 +405,7 @@ __device__ __forceinline__ void spectral_frame_wave(const float *mg, const float
     const double sumB = frameSum;
     const double sigma2 = (sumB != 0.0) ? t2v[1] / sumB : 0.0;
     sp[9] = (float)sigma2;
-    sp[10] = (sigma2 <= 0.0) ? 0.0f : (float)(t2v[2] / (sumB * sigma2 * sqrt(sigma2)));
+    sp[10] = (sigma2 <= 0.0) ? 0.0f : (float)(mom3 / (sumB * sigma2 * sqrt(sigma2)));
     sp[11] = (sigma2 == 0.0) ? 0.0f : (float)(t2v[3] / (sumB * sigma2 * sigma2));
     const double Nind = (double)nBins;
     const double deno = (Nind * C.slope_S2f - C.slope_Sf * C.slope_Sf);

@@ -18,7 +18,10 @@
 // Sums of doubles are associated otherwise than in the wave form (as that one's are otherwise than the block form's and the
 // reference's bin-after-bin loops): every one of them is rounded to float or compared with a threshold afterwards, and differs
 // from the sequential sum only where the double's last bits decide that rounding (lld_blocks_compare.hpp; ~1e-9 per value --
-// the bench's accuracy object counts the cells). Float chains keep the reference's order operation for operation.
+// the bench's accuracy object counts the cells). That holds for sums of non-negative terms only: the third central moment's
+// terms cancel (a click in digital silence has a flat spectrum, its skewness is the rounding noise of the sum), so lane 0 adds
+// them bin after bin like the reference's loop (seq_sum_f64; tests/test_gpu_hard_signals.py, clicks_in_zeros). Float chains keep
+// the reference's order operation for operation.
 // The shipped geometry only (16 kHz: N = 320, hop 160, FFT 512, 96 zeros in front, 60 ms = 960 samples, 26 bands, 14 cepstra,
 // int16 input, reference-order tables): launch_compare checks it.
 #pragma once
@@ -39,7 +42,9 @@
 namespace smilehip {
 
 namespace cq {
-constexpr int kWavesPerSimd = 3;                             // waves per SIMD the register budget is set for
+// waves per SIMD the register budget is set for: 178 registers since the third moment's terms go through LDS (below) -- ten more than
+// three waves allow, and a budget of three spills ~300 registers' worth to scratch around the transform (twice the step time)
+constexpr int kWavesPerSimd = 2;
 constexpr int kBinsGroup = 3;                                // bins of the entropy / moments loop whose operations may interleave
 constexpr int kN = 320, kH = 160, kPad = 96, kN60 = 960, kM = 256, kK = 257, kBands = 26, kMfcc = 14;
 constexpr int kRowFloats = 2 * kQuadZPairs + 64 + 16;      // z (544 floats: transform, then mel terms / powers / chains) | lmel[32] | aud[32] | the row's state[16]
@@ -372,7 +377,7 @@ __device__ __forceinline__ void compare_frame_quad_body(const LldParams &P, cons
       }
       QPHASE(6);
       // the per-bin terms of entropy, variance, skewness, kurtosis, and sharpness' chain terms
-      double e0 = 0.0, e1 = 0.0, e2m = 0.0, e3 = 0.0;
+      double e0 = 0.0, e1 = 0.0, e3 = 0.0;
       {
         const double entropy_floor = 0.0000001;
         double dn = frameSum;
@@ -397,12 +402,12 @@ __device__ __forceinline__ void compare_frame_quad_body(const LldParams &P, cons
             e0 += (ln > 0.0) ? div_markstein(xl, kLog2, kInvLog2) : 0.0;
             const double t1 = F0e * fresh(k) - (double)ctr;
             double mm = t1 * t1 * p;
-            e1 += mm; mm *= t1; e2m += mm; e3 += mm * t1;
+            e1 += mm; mm *= t1; e3 += mm * t1;
           }
           if (m % kBinsGroup == kBinsGroup - 1) __builtin_amdgcn_sched_barrier(0);
         }
       }
-      const double ent = QuadG::sum(e0, nullptr), mom2 = QuadG::sum(e1, nullptr), mom3 = QuadG::sum(e2m, nullptr), mom4 = QuadG::sum(e3, nullptr);
+      const double ent = QuadG::sum(e0, nullptr), mom2 = QuadG::sum(e1, nullptr), mom4 = QuadG::sum(e3, nullptr);
       QPHASE(7);
       // the two FLOAT_DMEM chains (:1435-1471 sharpness, :1485-1499 harmonicity): terms of bins 1 .. 256 in order, lane 0 adds the
       // first chain, lane 1 the second
@@ -410,6 +415,28 @@ __device__ __forceinline__ void compare_frame_quad_body(const LldParams &P, cons
       float chain = 0.0f;
       if (j < 2) chain = seq_sum_f32(zf + 256 * j, 0, 256);
       const float sumAA = lane_f(chain, row_base4, 0), ptp = lane_f(chain, row_base4, 1);
+      // the third moment (:1344-1364): its terms cancel -- a flat spectrum leaves rounding noise only -- so the order of the additions
+      // decides the result. The terms (the expressions of the loop above, again: seventeen doubles kept would be spilled) take the
+      // consumed float chains' place, 256 doubles in the row's 544 floats, and lane 0 adds them bin after bin
+      QuadG::sync();
+      {
+        double *zd = reinterpret_cast<double *>(zf);
+        const double F0m = fresh(F0);
+#pragma unroll
+        for (int m = 0; m < 17; ++m) {
+          const int k = j + 16 * m;
+          const float me = fresh(mv[m]);
+          const double p = (double)(me * me);
+          const double t1 = F0m * fresh(k) - (double)ctr;
+          double mm = t1 * t1 * p;
+          mm *= t1;
+          if (k >= 1 && k <= kM) zd[k - 1] = mm;
+          if (m % kBinsGroup == kBinsGroup - 1) __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      QuadG::sync();
+      double mom3 = 0.0;
+      if (j == 0) mom3 = seq_sum_f64(reinterpret_cast<const double *>(zf), kM);
       if (store && j == 0) {
         const int nBins = kK - 1;
         float *sp = rawB + 26;
