@@ -426,7 +426,9 @@ __global__ void __launch_bounds__(256) lld_gemaps_lpc(GemapsParams G) {
     float *o = G.lpc + (g0 + threadIdx.x) * G.lpc_ld;
 #pragma unroll
     for (int i = 0; i < kLpcP; ++i) o[i] = a[i];
-    if (G.lpc_ld > kLpcP) o[kLpcP] = 0.0f;
+    // the batch scratch's rows are 12 wide and its twelfth column is kept zero; a caller's row (smilehip_lpc_frames) ends at its
+    // 11 coefficients whatever its leading dimension
+    if (G.op_mode == 0 && G.lpc_ld > kLpcP) o[kLpcP] = 0.0f;
   }
 }
 

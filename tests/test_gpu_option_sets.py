@@ -87,6 +87,19 @@ def ref_magphase(a, flags, dbp_norm, min_dbp):
     return np.concatenate(out, axis=1)
 
 
+def check_magphase(got, ref, flags, K):
+    """the comparison of one mode with ref_magphase (tests/test_gpu_operator_layouts.py uses it too)"""
+    if flags & 16 or flags & 2:          # log10f / atan2f: the float functions against float64-then-rounded values
+        both = np.isfinite(ref) & np.isfinite(got)
+        assert (np.isfinite(ref) == np.isfinite(got)).all()
+        assert np.abs(got[both] - ref[both]).max() <= 2e-5
+        if not flags & 2 or flags & 1:
+            exact = slice(0, K) if not flags & 16 else slice(0, 0)
+            assert np.array_equal(bits(got[:, exact]), bits(ref[:, exact]))
+    else:
+        assert np.array_equal(bits(got), bits(ref))
+
+
 @pytest.mark.parametrize("flags", [1, 1 | 4, 1 | 8, 1 | 4 | 8, 1 | 16, 2, 1 | 2, 1 | 2 | 16])
 def test_fftmagphase_every_mode(flags):
     import torch
@@ -102,16 +115,7 @@ def test_fftmagphase_every_mode(flags):
                                                         len(a), None))
     torch.cuda.synchronize()
     got = d_o.cpu().numpy()
-    ref = ref_magphase(a, flags, 90.302, -29.698)
-    if flags & 16 or flags & 2:          # log10f / atan2f: the float functions against float64-then-rounded values
-        both = np.isfinite(ref) & np.isfinite(got)
-        assert (np.isfinite(ref) == np.isfinite(got)).all()
-        assert np.abs(got[both] - ref[both]).max() <= 2e-5
-        if not flags & 2 or flags & 1:
-            exact = slice(0, K) if not flags & 16 else slice(0, 0)
-            assert np.array_equal(bits(got[:, exact]), bits(ref[:, exact]))
-    else:
-        assert np.array_equal(bits(got), bits(ref))
+    check_magphase(got, ref_magphase(a, flags, 90.302, -29.698), flags, K)
 
 
 def ref_mzcr(x, flags):
