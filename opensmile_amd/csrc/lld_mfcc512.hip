@@ -55,6 +55,7 @@
 #include <hip/hip_runtime.h>
 #include "kernel_timing.hpp"
 #include "phase_timing.hpp"
+#include "wave_lifetimes.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -283,6 +284,27 @@ __device__ __forceinline__ void pcm_prefetch(const int16_t *pcm, int64_t pcm_tot
 
 // the phases of the pass loop (phase_timing.hpp; tools/ubench/variant.sh phase -DSMILEHIP_PHASE_TIMING, tools/ubench/phase_timing.py)
 SMILEHIP_PHASE_COUNTERS(g_phase, 16, smilehip_debug_phase)
+// every wave's lifetime in the pass loop and where it ran (wave_lifetimes.hpp; tools/ubench/variant.sh lifetimes -DSMILEHIP_PHASE_TIMING=2,
+// tools/ubench/wave_lifetimes.py)
+SMILEHIP_WAVE_LIFE_RECORDS(g_wave_life, smilehip_debug_wave_life)
+
+// Issue priority of the wave, level & 3 (wave-uniform): s_setprio takes an immediate, hence a scalar branch -- no vector instruction.
+// The pass loop rotates it: a SIMD arbitrates vector issue by priority, then by AGE, the loop has no barrier and gives every
+// wave the same work, so at equal priority the age order of a SIMD's four waves held for the whole launch -- the oldest ran at
+// nearly single-wave speed and left first, the SIMD ended the launch with three, two, one wave (lifetimes 0.59 / 0.68 / 0.82 /
+// 0.96 of the longest by start order, finish order = start order on 1023 of 1024 SIMDs: profiles/wave_lifetimes_parent.json).
+// With level = passes done + the wave's slot on its SIMD, the four waves of a SIMD hold four different levels in every pass and
+// each level for a quarter of its passes; a wave that runs ahead hurries through its high passes and lingers in its low ones,
+// so no wave needs to know another's progress. Lifetimes 0.86 / 0.88 / 0.93 / 0.96, resident waves per SIMD 2.97 -> 3.52 of the
+// pass loop (profiles/wave_lifetimes.json), the bench step -3.7 % and -4.6 % in two visits (profiles/wave_order_ab.txt).
+__device__ __forceinline__ void wave_set_prio(int level) {
+  switch (level & 3) {
+    case 0: __builtin_amdgcn_s_setprio(0); break;
+    case 1: __builtin_amdgcn_s_setprio(1); break;
+    case 2: __builtin_amdgcn_s_setprio(2); break;
+    default: __builtin_amdgcn_s_setprio(3); break;
+  }
+}
 
 // LDS layout (dynamic), sizes in floats:
 //   shared tables : tw512 [256 f2] | win [MP*16 f2] | tw256 [256 f2, index k1*16+j] |
@@ -446,7 +468,15 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
     drow = from_group((g + 2) & 3, g >= 2 ? dp : dn);
   };
 
+  // the wave's slot on its SIMD (HW_REG_HW_ID, WAVE_ID): the four resident waves of a SIMD hold four different ones
+  // (slots 0 .. 3 on every SIMD of the bench launch, two waves of each of the CU's two blocks: the lifetime record)
+  const int slot = (int)(__builtin_amdgcn_s_getreg((3 << 11) | 4) & 3u);
+  int passes_done = 0;                                 // never reset: runs on across tile changes (tp does not)
+  WaveLife WL;
+  WL.begin();
   for (;;) {
+    wave_set_prio(passes_done + slot);
+    passes_done += 1;
     const bool live = tp + g < (DELTA ? cur_live : cur_n);
     PH(0);                                   // loop overhead
     // ------------------------------------------------------------ frame from registers: R0 (scale folded), R2, R3
@@ -739,6 +769,7 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
     *reinterpret_cast<float *>(pend_row + oo) = pend_val;
   }
   PH.flush(g_phase);
+  WL.end(g_wave_life, blockIdx.x, (unsigned)wave, (unsigned)passes_done);
 }
 
 template <int MP, bool PREEMPH, bool USE_POWER, bool ALIGNED, bool PLP, int UC, bool DELTA = false>

@@ -2,6 +2,8 @@
 // read by tools/ubench/phase_timing*.py): s_memtime at the phase boundaries, summed over all waves by one lane per wave.
 // It measures wave RESIDENCE, not issue slots: a phase that waits for memory shows large here and may cost little.
 // Without the switch everything here is empty and nothing of it reaches the product.
+// The switch has levels: -DSMILEHIP_PHASE_TIMING (= 1) the phase stamps below; -DSMILEHIP_PHASE_TIMING=2 NO phase stamp (they cost
+// ~10 % and force waits) and the per-wave lifetime records of wave_lifetimes.hpp instead.
 //   SMILEHIP_PHASE_COUNTERS(g_x, 16, smilehip_debug_phase_x)   the counters and their read / reset entry point
 //   PhaseTimer<8> PH;  ..  PH(3);  ..  PH.flush(g_x);           per thread: stamp the end of phase 3; add the sums to g_x[0 .. 7]
 //   PH.flush(g_x, 8);                                           .. to g_x[8 .. 15], where two kernels share the counters
@@ -10,7 +12,7 @@
 
 namespace smilehip {
 
-#ifdef SMILEHIP_PHASE_TIMING
+#if defined(SMILEHIP_PHASE_TIMING) && SMILEHIP_PHASE_TIMING != 2
 #define SMILEHIP_PHASE_COUNTERS(array, len, entry)                                                                   \
   __device__ unsigned long long array[len];                                                                         \
   extern "C" int entry(unsigned long long *out, int reset) {                                                        \

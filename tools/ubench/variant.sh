@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: variant.sh <name> [extra hipcc flags...]  -> tools/ubench/build/libsmilehip_<name>.so
 # A private copy of libsmilehip whose fast kernel is compiled with instrumentation flags
-# (-DSMILEHIP_PHASE_TIMING, -DSMILEHIP_DEBUG_KNOBS). Run with SMILEHIP_LIB=<path> python bench.py.
+# (-DSMILEHIP_PHASE_TIMING, -DSMILEHIP_PHASE_TIMING=2, -DSMILEHIP_DEBUG_KNOBS). Run with SMILEHIP_LIB=<path> python bench.py.
 set -e
 cd "$(dirname "$0")"
 NAME=$1; shift
