@@ -428,6 +428,43 @@ int smilehip_batch_funcspec(smilehip_plan *plan, smilehip_batch *batch, const sm
                             const float *d_lld, int64_t ld_lld, int32_t col_first, int32_t n_cols, int32_t rows_cut,
                             const float *d_extra, int64_t ld_extra, float *d_func, int64_t ld_func, void *stream);
 
+/* ---- functionals over fixed windows: cWinToVecProcessor frameMode = fixed, frameCenterSpecial = left ----
+ * One vector per WINDOW instead of one per utterance (src/core/winToVecProcessor.cpp:435-574 sets the geometry, :868-1098
+ * hands out the windows): window k of a level is its rows [k step, k step + size), windows that do not fit are dropped
+ * (noPostEOIprocessing = 1), and each goes through cFunctionals::doProcess like a full-mode contour of `size` rows -- time
+ * norms "segment" see the window length. Not built: frameCenterSpecial other than left, frameMode var / list / meta,
+ * allowLastFrameIncomplete.
+ *
+ * The geometry (winToVecProcessor.cpp:439-456), host only, no device needed: size_rows = (long)round(frame_size_sec / period),
+ * step_rows = (long)round(frame_step_sec / period) in double, a step of 0 rows becomes the size; n_windows = the windows of a
+ * level of `rows` rows, (rows - size) / step + 1 if rows >= size else 0. Any output pointer may be NULL.
+ * SMILEHIP_ERR_INVALID, naming the option: frameSize below one row; frameStep = 0 seconds, which is frameMode = full. */
+int smilehip_func_window_geometry(double period, double frame_size_sec, double frame_step_sec, int64_t rows,
+                                  int64_t *size_rows, int64_t *step_rows, int64_t *n_windows);
+/* Windows before each utterance of a batch, win_off[n_utt + 1] (host): utterance u has the windows of its first
+ * rows_u - rows_cut rows (winToVecProcessor.cpp:868-1098). For the IS09 chain the windows run over all T + 1 rows of the
+ * LLD matrix: rows_cut = 0. */
+int smilehip_batch_func_windows(const smilehip_batch *batch, int64_t size_rows, int64_t step_rows, int32_t rows_cut,
+                                int64_t *win_off);
+/* smilehip_batch_funcspec over those windows (winToVecProcessor.cpp:868-1098 + functionals.cpp:320-389): d_func receives
+ * win_off[n_utt] rows of n_cols * count(spec) values, leading dimension ld_func, in utterance order, then window order,
+ * element-major; utterances shorter than a window contribute no row. Every window has its own scratch; the scratch of one
+ * launch is bounded (512 MiB; SMILEHIP_FUNC_WINDOWS_SCRATCH_MB in the environment moves the bound) and the windows run in
+ * chunks of whole windows on `stream`. A spec with the Modulation family and size_rows < 34 is refused by name. Scratch
+ * rules as for smilehip_funcspec_matrix; a call with another geometry than the batch's last one waits for `stream` once. */
+int smilehip_batch_funcspec_windows(smilehip_plan *plan, smilehip_batch *batch, const smilehip_func_spec *spec,
+                                    const float *d_lld, int64_t ld_lld, int32_t col_first, int32_t n_cols, int32_t rows_cut,
+                                    int64_t size_rows, int64_t step_rows, float *d_func, int64_t ld_func, void *stream);
+/* The same over ONE matrix (rows x cols, leading dimension ld_lld; winToVecProcessor.cpp:868-1098): (rows - size) / step + 1
+ * rows of cols * count(spec) values, none if rows < size_rows. */
+int smilehip_funcspec_matrix_windows(smilehip_context *ctx, const smilehip_func_spec *spec, const float *d_lld, int64_t ld_lld,
+                                     int64_t rows, int32_t cols, int64_t size_rows, int64_t step_rows, float *d_func,
+                                     int64_t ld_func, void *stream);
+/* The one cFunctionals instance of config/is09-13/IS09_emotion_core.func.conf.inc as a spec of the general engine:
+ * Extremes max min range maxPos minPos amean (norm = frame); Regression linregc1 linregc2 linregerrQ (oldBuggyQerr = 1, no
+ * ratio limits); Moments stddev skewness kurtosis; period 0.01 s. 12 values per column. */
+int smilehip_funcspec_is09(smilehip_func_spec *spec);
+
 /* The whole functionals level of config/compare16/ComParE_2016.conf: 6373 values per utterance in the reference's own
  * order ([functionals] concatenates is13_functionalsA, B, Nz, F0, LLD, Delta; names: smilehip_host func_names_compare16).
  * d_lld: the 130-column matrix smilehip_lld_run produced for THIS batch on a smilehip_config_compare16 plan (the run also

@@ -216,6 +216,11 @@ SYMBOLS = {
     "smilehip_viterbi_stream_destroy": (C.c_int, [_vp]),
     "smilehip_funcspec_matrix": (C.c_int, [_vp, _vp, _vp, _i64, _i64, C.c_int32, _vp, _vp]),
     "smilehip_batch_funcspec": (C.c_int, [_vp, _vp, _vp, _vp, _i64, C.c_int32, C.c_int32, C.c_int32, _vp, _i64, _vp, _i64, _vp]),
+    "smilehip_func_window_geometry": (C.c_int, [_dbl, _dbl, _dbl, _i64, _vp, _vp, _vp]),
+    "smilehip_batch_func_windows": (C.c_int, [_vp, _i64, _i64, C.c_int32, _vp]),
+    "smilehip_batch_funcspec_windows": (C.c_int, [_vp, _vp, _vp, _vp, _i64, C.c_int32, C.c_int32, C.c_int32, _i64, _i64, _vp, _i64, _vp]),
+    "smilehip_funcspec_matrix_windows": (C.c_int, [_vp, _vp, _vp, _i64, _i64, C.c_int32, _i64, _i64, _vp, _i64, _vp]),
+    "smilehip_funcspec_is09": (C.c_int, [_vp]),
     "smilehip_lld_run": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp]),
     "smilehip_lld_run_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp]),
     "smilehip_lld_run_host": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
@@ -560,6 +565,53 @@ def funcspec_matrix_host(ctx, spec, x):
     return out
 
 
+def funcspec_is09():
+    """IS09_emotion's cFunctionals instance as a spec of the general engine."""
+    s = FuncSpec()
+    _check(load().smilehip_funcspec_is09(C.byref(s)))
+    return s
+
+
+def func_window_geometry(period, frame_size_sec, frame_step_sec, rows=0):
+    """(size_rows, step_rows, n_windows) of frameMode = fixed over a level of `rows` rows (host only)."""
+    size, step, n = C.c_int64(), C.c_int64(), C.c_int64()
+    _check(load().smilehip_func_window_geometry(period, frame_size_sec, frame_step_sec, rows, C.byref(size), C.byref(step), C.byref(n)))
+    return size.value, step.value, n.value
+
+
+def funcspec_matrix_windows_host(ctx, spec, x, size_rows, step_rows, ld_lld=None, ld_func=None):
+    """rows x cols host matrix -> n_windows x (cols * count(spec)) through smilehip_funcspec_matrix_windows. With ld_lld /
+    ld_func the device matrices get those strides and NaN pads; the padded output comes back as a second value."""
+    L = load()
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    rows, cols = x.shape
+    per = funcspec_count(spec)
+    n = (rows - size_rows) // step_rows + 1 if rows >= size_rows else 0
+    ldx = cols if ld_lld is None else ld_lld
+    ldf = cols * per if ld_func is None else ld_func
+    xin = np.full((rows, ldx), np.nan, np.float32)
+    xin[:, :cols] = x
+    out = np.full((n, ldf), np.nan, np.float32)
+    d_x, d_out = _vp(), _vp()
+    _check(L.smilehip_alloc(ctx._h, max(xin.nbytes, 4), C.byref(d_x)))
+    _check(L.smilehip_alloc(ctx._h, max(out.nbytes, 4), C.byref(d_out)))
+    try:
+        if xin.nbytes:
+            _check(L.smilehip_copy_to_device(ctx._h, d_x, xin.ctypes.data, xin.nbytes, None))
+        if out.nbytes:
+            _check(L.smilehip_copy_to_device(ctx._h, d_out, out.ctypes.data, out.nbytes, None))
+        _check(L.smilehip_funcspec_matrix_windows(ctx._h, C.byref(spec), d_x, ldx, rows, cols, size_rows, step_rows, d_out, ldf, None))
+        _check(L.smilehip_stream_synchronize(ctx._h, None))
+        if out.nbytes:
+            _check(L.smilehip_copy_to_host(ctx._h, out.ctypes.data, d_out, out.nbytes, None))
+    finally:
+        L.smilehip_free(ctx._h, d_x)
+        L.smilehip_free(ctx._h, d_out)
+    if ld_lld is None and ld_func is None:
+        return out
+    return np.ascontiguousarray(out[:, :cols * per]), out
+
+
 def is09_lld_config():
     c = LldConfig()
     load().smilehip_config_is09_lld(C.byref(c))
@@ -885,6 +937,43 @@ class Batch:
             if extra is not None:
                 L.smilehip_free(ctx, d_ex)
         return out
+
+    def func_windows(self, size_rows, step_rows, rows_cut=0):
+        """Windows before each utterance, [n_utt + 1] (smilehip_batch_func_windows)."""
+        w = np.zeros(self.n_utt + 1, np.int64)
+        _check(load().smilehip_batch_func_windows(self._h, size_rows, step_rows, rows_cut, w.ctypes.data))
+        return w
+
+    def funcspec_windows_host(self, lld, spec, col_first, n_cols, rows_cut, size_rows, step_rows, ld_func=None):
+        """lld: the matrix run_host returned -> (win_off[n_utt] x (n_cols * count(spec)), win_off) through
+        smilehip_batch_funcspec_windows: one row per window, utterance after utterance. With ld_func the device output gets that
+        stride, NaN-filled beforehand, and comes back whole (values in the first n_cols * count(spec) columns)."""
+        L = load()
+        per = funcspec_count(spec)
+        lld = np.ascontiguousarray(lld, dtype=np.float32)
+        ld = lld.shape[1]
+        assert lld.shape[0] == self.total_rows
+        win_off = self.func_windows(size_rows, step_rows, rows_cut)
+        ldf = n_cols * per if ld_func is None else ld_func
+        out = np.full((int(win_off[-1]), ldf), 0.0 if ld_func is None else np.nan, np.float32)
+        ctx = self.plan.ctx._h
+        d_lld, d_out = _vp(), _vp()
+        _check(L.smilehip_alloc(ctx, max(lld.nbytes, 4), C.byref(d_lld)))
+        _check(L.smilehip_alloc(ctx, max(out.nbytes, 4), C.byref(d_out)))
+        try:
+            if lld.nbytes:
+                _check(L.smilehip_copy_to_device(ctx, d_lld, lld.ctypes.data, lld.nbytes, None))
+            if out.nbytes and ld_func is not None:
+                _check(L.smilehip_copy_to_device(ctx, d_out, out.ctypes.data, out.nbytes, None))
+            _check(L.smilehip_batch_funcspec_windows(self.plan._h, self._h, C.byref(spec), d_lld, ld, col_first, n_cols, rows_cut,
+                                                     size_rows, step_rows, d_out, ldf, None))
+            _check(L.smilehip_stream_synchronize(ctx, None))
+            if out.nbytes:
+                _check(L.smilehip_copy_to_host(ctx, out.ctypes.data, d_out, out.nbytes, None))
+        finally:
+            L.smilehip_free(ctx, d_lld)
+            L.smilehip_free(ctx, d_out)
+        return out, win_off
 
     def close(self):
         if self._h:

@@ -20,6 +20,7 @@
 
 #include <cfloat>
 #include <cmath>
+#include <type_traits>
 
 #include "lld_launch.hpp"
 #include "lld_params.hpp"
@@ -66,6 +67,7 @@ struct Where {                     // what a thread works on
   int64_t srow0;                   // first scratch row of the utterance
   int64_t rows;                    // rows before nonZeroFuncts
   bool on;
+  int64_t xrow0;                   // item form: the window's first row in the input matrix
 };
 
 __device__ __forceinline__ void utt_rows(const FsParams &P, Where &w) {
@@ -86,18 +88,72 @@ __device__ __forceinline__ void utt_rows(const FsParams &P, Where &w) {
   w.rows = n;
 }
 
-__device__ __forceinline__ Where locate(const FsParams &P) {
+// Item form (FsItemParams): item i of the launch is window it_first + i of the call. Everything the kernels index by utterance
+// -- stats slot, output row, scratch rows -- is indexed by the ITEM, so overlapping windows never share scratch; only the input
+// rows are found through the window's utterance (the last one whose window count prefix is <= the window's index).
+template <bool ITEM> using FsP = typename std::conditional<ITEM, FsItemParams, FsParams>::type;   // a kernel's parameter block
+
+__device__ __forceinline__ void item_rows(const FsItemParams &P, Where &w, int item) {
+  w.u = item;
+  w.srow0 = (int64_t)item * P.it_size;
+  w.rows = P.it_size;
+  const int64_t g = P.it_first + item;
+  if (!P.it_win_off) {
+    w.xrow0 = g * P.it_step;
+    return;
+  }
+  int lo = 0, hi = P.it_n_utt;                     // win_off[lo] <= g < win_off[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (P.it_win_off[mid] <= g) lo = mid; else hi = mid;
+  }
+  w.xrow0 = P.row_off[lo] + (g - P.it_win_off[lo]) * P.it_step;
+}
+
+// one (item, column) per workgroup / wave: fs_percentiles, fs_percentiles_wave, fs_modulation
+template <bool ITEM, typename Index>                       // (Index: the caller's own index type -- its division is the one it had)
+__device__ __forceinline__ Where locate_one(const FsP<ITEM> &P, Index idx) {
   Where w;
+  w.u = idx / P.n_cols;
+  w.c = idx % P.n_cols;
+  w.on = true;
+  if constexpr (ITEM) item_rows(P, w, w.u);
+  else utt_rows(P, w);
+  return w;
+}
+
+template <bool ITEM>
+__device__ __forceinline__ Where locate(const FsP<ITEM> &P) {
+  Where w;
+  if constexpr (ITEM) if (P.it_pack > 1) {
+    // lane packing: n_cols <= 32 leaves half a wave or more idle, and consecutive windows fill it -- lane l serves column
+    // l % n_cols of the wave's window l / n_cols; each window's step is still one contiguous row segment
+    const int k = threadIdx.x / P.n_cols;
+    const int item = blockIdx.x * P.it_pack + k;
+    w.c = threadIdx.x - k * P.n_cols;
+    w.on = k < P.it_pack && item < P.it_n;
+    if (w.on) item_rows(P, w, item);
+    return w;
+  }
   const int groups = (P.n_cols + kColsPerBlock - 1) / kColsPerBlock;
   w.u = blockIdx.x / groups;
   w.c = (blockIdx.x % groups) * kColsPerBlock + threadIdx.x;
   w.on = w.c < P.n_cols;
-  utt_rows(P, w);
+  if constexpr (ITEM) item_rows(P, w, w.u);
+  else utt_rows(P, w);
   return w;
 }
 
+template <bool ITEM>
 __device__ __forceinline__ Col raw_col(const FsParams &P, const Where &w) {
   Col x;
+  if (ITEM) {
+    x.p = P.x + w.xrow0 * P.ld_x + P.col_first + w.c;
+    x.ld = P.ld_x;
+    x.N = x.n_main = w.rows;
+    x.pe = x.p;
+    return x;
+  }
   const int64_t r0 = P.single_rows >= 0 ? 0 : P.row_off[w.u];
   x.p = P.x + r0 * P.ld_x + P.col_first + w.c;
   x.ld = P.ld_x;
@@ -108,8 +164,9 @@ __device__ __forceinline__ Col raw_col(const FsParams &P, const Where &w) {
 }
 
 // the column the families see: the compacted copy if nonZeroFuncts, else the input itself
+template <bool ITEM>
 __device__ __forceinline__ Col data_col(const FsParams &P, const Where &w) {
-  if (!P.spec.non_zero_functs) return raw_col(P, w);
+  if (!P.spec.non_zero_functs) return raw_col<ITEM>(P, w);
   Col x;
   x.p = P.nz + w.srow0 * P.n_cols + w.c;
   x.ld = P.n_cols;
@@ -138,10 +195,11 @@ __device__ float fs_ratio_limit(float x, float limit1, float excess) {
 }  // namespace
 
 // ------------------------------------------------------------------ stats
-__global__ void __launch_bounds__(kColsPerBlock) fs_stats(FsParams P) {
-  const Where w = locate(P);
+template <bool ITEM>
+__global__ void __launch_bounds__(kColsPerBlock) fs_stats(FsP<ITEM> P) {
+  const Where w = locate<ITEM>(P);
   if (!w.on) return;
-  const Col r = raw_col(P, w);
+  const Col r = raw_col<ITEM>(P, w);
   const int64_t si = (int64_t)w.u * P.n_cols + w.c;
   int64_t NN = r.N;
   if (P.spec.non_zero_functs) {
@@ -159,7 +217,7 @@ __global__ void __launch_bounds__(kColsPerBlock) fs_stats(FsParams P) {
     for (int i = 0; i < P.per; ++i) o[i] = 0.0f;
     return;
   }
-  const Col x = data_col(P, w);
+  const Col x = data_col<ITEM>(P, w);
   float mn = x[0], mx = mn;
   double mean = mn;
   for_rows(x, 1, NN, [&](int64_t, float v) {
@@ -1284,13 +1342,13 @@ __device__ int f_peaks2(const smilehip_func_spec &s, const Col &in, float min, f
 
 }  // namespace
 
-template <int FAM>
-__global__ void __launch_bounds__(kColsPerBlock) fs_family(FsParams P, int out_off, int want) {
-  const Where w = locate(P);
+template <int FAM, bool ITEM>
+__global__ void __launch_bounds__(kColsPerBlock) fs_family(FsP<ITEM> P, int out_off, int want) {
+  const Where w = locate<ITEM>(P);
   if (!w.on) return;
   const int64_t si = (int64_t)w.u * P.n_cols + w.c;
   if (P.st_n[si] <= 0) return;                          // zero-filled by fs_stats
-  const Col x = data_col(P, w);
+  const Col x = data_col<ITEM>(P, w);
   const float mn = P.st_min[si], mx = P.st_max[si], mean = P.st_mean[si];
   float *o = P.out + (int64_t)w.u * P.ld_out + (int64_t)w.c * P.per + out_off;
   int got = 0;
@@ -1381,17 +1439,14 @@ __device__ void pctl_readout(const FsParams &P, const Where &w, const float *a, 
   }
 }
 
-__global__ void __launch_bounds__(kSortThreads) fs_percentiles(FsParams P, int out_off) {
+template <bool ITEM>
+__global__ void __launch_bounds__(kSortThreads) fs_percentiles(FsP<ITEM> P, int out_off) {
   __shared__ float lds[kSortLds];
-  Where w;
-  w.u = blockIdx.x / P.n_cols;
-  w.c = blockIdx.x % P.n_cols;
-  w.on = true;
-  utt_rows(P, w);
+  const Where w = locate_one<ITEM>(P, blockIdx.x);
   const int64_t si = (int64_t)w.u * P.n_cols + w.c;
   const int64_t N = P.st_n[si];
   if (N <= 0 || N <= kWaveSortMaxDecl) return;           // (up to 1024 rows: fs_percentiles_wave)
-  const Col x = data_col(P, w);
+  const Col x = data_col<ITEM>(P, w);
   int n2 = 1;
   while (n2 < N) n2 <<= 1;
   // global scratch beyond the LDS capacity: the utterance's region holds 2 * (rows + 1) * n_cols floats; the column slots
@@ -1475,20 +1530,17 @@ __device__ __forceinline__ void wave_bitonic_sort(const Col &x, int64_t N, int l
 }
 
 constexpr int kWaveSortMax = 1024;
-__global__ void __launch_bounds__(256) fs_percentiles_wave(FsParams P, int out_off, int n_items) {
+template <bool ITEM>
+__global__ void __launch_bounds__(256) fs_percentiles_wave(FsP<ITEM> P, int out_off, int n_items) {
   __shared__ float lds_all[4 * kWaveSortMax];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int item = blockIdx.x * 4 + wave;
   if (item >= n_items) return;
-  Where w;
-  w.u = item / P.n_cols;
-  w.c = item % P.n_cols;
-  w.on = true;
-  utt_rows(P, w);
+  const Where w = locate_one<ITEM>(P, item);
   const int64_t N = P.st_n[(int64_t)w.u * P.n_cols + w.c];
   if (N <= 0 || N > kWaveSortMax) return;                // longer contours: fs_percentiles
-  const Col x = data_col(P, w);
+  const Col x = data_col<ITEM>(P, w);
   float *a = lds_all + wave * kWaveSortMax;
   int lg = 1;
   while ((1 << lg) < N) ++lg;
@@ -1530,19 +1582,16 @@ struct ModG {
 };
 }  // namespace
 
-__global__ void __launch_bounds__(64) fs_modulation(FsParams P, int out_off) {
+template <bool ITEM>
+__global__ void __launch_bounds__(64) fs_modulation(FsP<ITEM> P, int out_off) {
   __shared__ float2 z[512];
   __shared__ double yv[516], y2[516], uu[516];
   __shared__ float acc[128];
-  Where w;
-  w.u = blockIdx.x / P.n_cols;
-  w.c = blockIdx.x % P.n_cols;
-  w.on = true;
-  utt_rows(P, w);
+  const Where w = locate_one<ITEM>(P, blockIdx.x);
   const smilehip_func_spec &s = P.spec;
   const int64_t Nin = P.st_n[(int64_t)w.u * P.n_cols + w.c];
   if (Nin <= 0) return;
-  const Col x = data_col(P, w);
+  const Col x = data_col<ITEM>(P, w);
   const int lane = threadIdx.x & 63, nb = s.mod_n_bins, W = s.mod_win_frames, step = s.mod_step_frames;
   float *out = P.out + (int64_t)w.u * P.ld_out + (int64_t)w.c * P.per + out_off;
   float mean = 0.0f;
@@ -1605,39 +1654,63 @@ __global__ void __launch_bounds__(64) fs_modulation(FsParams P, int out_off) {
     out[i] = bad ? __int_as_float(0x7fc00000) : (n_spec > 0 ? acc[i] / (float)n_spec : acc[i]);
 }
 
-hipError_t launch_funcspec(const FsParams &P, int n_utt, const int *fam_off, const int *fam_want, hipStream_t s) {
-  if (n_utt <= 0 || P.n_cols <= 0) return hipSuccess;
+namespace {
+// n = utterances (full mode) or items of this launch (item form)
+template <bool ITEM>
+hipError_t launch_fs(const FsP<ITEM> &P, int n, const int *fam_off, const int *fam_want, hipStream_t s) {
+  if (n <= 0 || P.n_cols <= 0) return hipSuccess;
   const int groups = (P.n_cols + kColsPerBlock - 1) / kColsPerBlock;
-  const dim3 grid((unsigned)(n_utt * groups)), block(kColsPerBlock);
-  SMILEHIP_KLAUNCH(fs_stats, grid, block, 0, s, P);
+  unsigned blocks = (unsigned)(n * groups);
+  if constexpr (ITEM) if (P.it_pack > 1) blocks = (unsigned)((n + P.it_pack - 1) / P.it_pack);
+  const dim3 grid(blocks), block(kColsPerBlock);
+  // (the timing report keeps the kernels' names; the item form's carry "/item")
+#define FS_LAUNCH(name, kernel, grid, block, ...)                                \
+  do {                                                                           \
+    smilehip::KernelMark kernel_mark_(ITEM ? name "/item" : name, s);            \
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, __VA_ARGS__);                  \
+  } while (0)
+  FS_LAUNCH("fs_stats", fs_stats<ITEM>, grid, block, P);
+#define FS_FAMILY_CASE(F) case F: FS_LAUNCH("fs_family<" #F ">", (fs_family<F, ITEM>), grid, block, P, off, want); break;
   for (int i = 0; i < P.spec.n_fam; ++i) {
     const int off = fam_off[i], want = fam_want[i];
     switch (P.spec.fam[i]) {
-      case SMILEHIP_FAM_EXTREMES: SMILEHIP_KLAUNCH(fs_family<SMILEHIP_FAM_EXTREMES>, grid, block, 0, s, P, off, want); break;
-      case SMILEHIP_FAM_MEANS: SMILEHIP_KLAUNCH(fs_family<SMILEHIP_FAM_MEANS>, grid, block, 0, s, P, off, want); break;
-      case SMILEHIP_FAM_MOMENTS: SMILEHIP_KLAUNCH(fs_family<SMILEHIP_FAM_MOMENTS>, grid, block, 0, s, P, off, want); break;
-      case SMILEHIP_FAM_REGRESSION: SMILEHIP_KLAUNCH(fs_family<SMILEHIP_FAM_REGRESSION>, grid, block, 0, s, P, off, want); break;
-      case SMILEHIP_FAM_TIMES: SMILEHIP_KLAUNCH(fs_family<SMILEHIP_FAM_TIMES>, grid, block, 0, s, P, off, want); break;
-      case SMILEHIP_FAM_SEGMENTS: SMILEHIP_KLAUNCH(fs_family<SMILEHIP_FAM_SEGMENTS>, grid, block, 0, s, P, off, want); break;
-      case SMILEHIP_FAM_LPC: SMILEHIP_KLAUNCH(fs_family<SMILEHIP_FAM_LPC>, grid, block, 0, s, P, off, want); break;
-      case SMILEHIP_FAM_PEAKS2: SMILEHIP_KLAUNCH(fs_family<SMILEHIP_FAM_PEAKS2>, grid, block, 0, s, P, off, want); break;
-      case SMILEHIP_FAM_ONSET: SMILEHIP_KLAUNCH(fs_family<SMILEHIP_FAM_ONSET>, grid, block, 0, s, P, off, want); break;
-      case SMILEHIP_FAM_PEAKS: SMILEHIP_KLAUNCH(fs_family<SMILEHIP_FAM_PEAKS>, grid, block, 0, s, P, off, want); break;
-      case SMILEHIP_FAM_CROSSINGS: SMILEHIP_KLAUNCH(fs_family<SMILEHIP_FAM_CROSSINGS>, grid, block, 0, s, P, off, want); break;
-      case SMILEHIP_FAM_DCT: SMILEHIP_KLAUNCH(fs_family<SMILEHIP_FAM_DCT>, grid, block, 0, s, P, off, want); break;
-      case SMILEHIP_FAM_SAMPLES: SMILEHIP_KLAUNCH(fs_family<SMILEHIP_FAM_SAMPLES>, grid, block, 0, s, P, off, want); break;
+      FS_FAMILY_CASE(SMILEHIP_FAM_EXTREMES)
+      FS_FAMILY_CASE(SMILEHIP_FAM_MEANS)
+      FS_FAMILY_CASE(SMILEHIP_FAM_MOMENTS)
+      FS_FAMILY_CASE(SMILEHIP_FAM_REGRESSION)
+      FS_FAMILY_CASE(SMILEHIP_FAM_TIMES)
+      FS_FAMILY_CASE(SMILEHIP_FAM_SEGMENTS)
+      FS_FAMILY_CASE(SMILEHIP_FAM_LPC)
+      FS_FAMILY_CASE(SMILEHIP_FAM_PEAKS2)
+      FS_FAMILY_CASE(SMILEHIP_FAM_ONSET)
+      FS_FAMILY_CASE(SMILEHIP_FAM_PEAKS)
+      FS_FAMILY_CASE(SMILEHIP_FAM_CROSSINGS)
+      FS_FAMILY_CASE(SMILEHIP_FAM_DCT)
+      FS_FAMILY_CASE(SMILEHIP_FAM_SAMPLES)
       case SMILEHIP_FAM_MODULATION:
-        SMILEHIP_KLAUNCH(fs_modulation, dim3((unsigned)(n_utt * P.n_cols)), dim3(64), 0, s, P, off);
+        FS_LAUNCH("fs_modulation", fs_modulation<ITEM>, dim3((unsigned)(n * P.n_cols)), dim3(64), P, off);
         break;
       case SMILEHIP_FAM_PERCENTILES:
-        SMILEHIP_KLAUNCH(fs_percentiles_wave, dim3((unsigned)((n_utt * P.n_cols + 3) / 4)), dim3(256), 0, s, P, off, n_utt * P.n_cols);
+        FS_LAUNCH("fs_percentiles_wave", fs_percentiles_wave<ITEM>, dim3((unsigned)((n * P.n_cols + 3) / 4)), dim3(256), P, off, n * P.n_cols);
         if (P.max_rows > kWaveSortMax)                   // some contour may be longer than one wave sorts
-          SMILEHIP_KLAUNCH(fs_percentiles, dim3((unsigned)(n_utt * P.n_cols)), dim3(kSortThreads), 0, s, P, off);
+          FS_LAUNCH("fs_percentiles", fs_percentiles<ITEM>, dim3((unsigned)(n * P.n_cols)), dim3(kSortThreads), P, off);
         break;
       default: return hipErrorInvalidValue;
     }
   }
+#undef FS_FAMILY_CASE
+#undef FS_LAUNCH
   return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_funcspec(const FsParams &P, int n_utt, const int *fam_off, const int *fam_want, hipStream_t s) {
+  return launch_fs<false>(P, n_utt, fam_off, fam_want, s);
+}
+
+// the item form: P.it_n windows (FsItemParams), each a contour of it_size rows with its own scratch and output row
+hipError_t launch_funcspec_items(const FsItemParams &P, const int *fam_off, const int *fam_want, hipStream_t s) {
+  return launch_fs<true>(P, P.it_n, fam_off, fam_want, s);
 }
 
 }  // namespace smilehip

@@ -281,6 +281,18 @@ struct FsParams {
   ModTables mod;             // Modulation family only
 };
 
+// The item form of the same kernels (fixed windows, cWinToVecProcessor frameMode = fixed; launch_funcspec_items): one item = one
+// window of it_size rows. A launch covers windows [it_first, it_first + it_n) of the call; item i of the launch owns scratch rows
+// [i * it_size, (i + 1) * it_size), stats slot i and output row i. Its own parameter type: the full-mode kernels keep FsParams as it is.
+struct FsItemParams : FsParams {
+  int64_t it_size, it_step;  // rows per window, rows between the first rows of consecutive windows
+  int64_t it_first;          // index of the launch's first window among all windows of the call
+  int32_t it_n;              // windows in this launch
+  int32_t it_n_utt;          // utterances behind it_win_off
+  const int64_t *it_win_off; // [it_n_utt + 1] windows before each utterance; null: ONE matrix, window g starts at row g * it_step
+  int32_t it_pack;           // windows per wave: floor(64 / n_cols) where n_cols <= 32, else 1
+};
+
 // R13: chain of window processors (cDeltaRegression / cContourSmoother) over the
 // rows of each utterance. Level 0 = the input block x (T rows, D columns);
 // stage s (kind 0 = delta regression with deltawin W, 1 = simple moving average

@@ -720,3 +720,166 @@ extern "C" int smilehip_batch_functionals_egemaps(smilehip_plan *plan, smilehip_
   if (e != hipSuccess) return fail(SMILEHIP_ERR_HIP, "dBp kernel launch failed: %s", hipGetErrorString(e));
   return SMILEHIP_OK;
 }
+
+// ---- functionals over fixed windows (cWinToVecProcessor frameMode = fixed, frameCenterSpecial = left)
+// src/core/winToVecProcessor.cpp:435-574 (the geometry) and :868-1098 (the windows a level yields: window k is rows
+// [k step, k step + size), windows that do not fit are dropped); each window then goes through cFunctionals::doProcess like a
+// full-mode contour of `size` rows.
+namespace {
+int64_t window_count(int64_t rows, int64_t size, int64_t step) { return rows >= size ? (rows - size) / step + 1 : 0; }
+
+// The scratch of one launch is bounded and the windows run in chunks of whole items (lld_specscale's 512 MiB is the precedent).
+// SMILEHIP_FUNC_WINDOWS_SCRATCH_MB lowers (or raises) the bound; fractions are taken, and a chunk holds at least one window.
+double windows_scratch_bytes() {
+  double mb = 512.0;
+  if (const char *e = getenv("SMILEHIP_FUNC_WINDOWS_SCRATCH_MB")) {
+    const double v = atof(e);
+    if (v > 0.0) mb = v;
+  }
+  return mb * 1048576.0;
+}
+
+// what both entry points refuse before they look at the device: values per column, or < 0 with the message
+int windows_spec_check(const smilehip_func_spec *spec, int64_t size, int64_t step, const char *who) {
+  const int per = spec_layout(spec, nullptr, nullptr);
+  if (per < 0) return per;
+  if (size < 1 || step < 1) return fail(SMILEHIP_ERR_INVALID, "%s: size_rows and step_rows must be >= 1", who);
+  if (has_family(*spec, SMILEHIP_FAM_MODULATION) && size < 34)
+    return fail(SMILEHIP_ERR_INVALID, "%s: Modulation needs windows of at least 34 rows (size_rows %lld): contours of fewer than 34 "
+                "values have no transform built", who, (long long)size);
+  return per;
+}
+
+int run_windows(smilehip_context *ctx, FsItemParams &P, int64_t total, int64_t size, int64_t step, float *d_func, int64_t ld_func,
+                hipStream_t stream, const char *who) {
+  int fam_off[12], fam_want[12];
+  const int per = spec_layout(&P.spec, fam_off, fam_want);
+  if (per < 0) return per;
+  if (total <= 0) return SMILEHIP_OK;
+  P.per = per;
+  P.it_size = size;
+  P.it_step = step;
+  P.it_pack = P.n_cols <= 32 ? 64 / P.n_cols : 1;          // consecutive windows fill the lanes a narrow column set leaves idle
+  P.max_rows = size;
+  // only what the spec's families need: the compacted copy, Peaks2's alive bytes, the sort buffer beyond the LDS capacity
+  FsNeed need = spec_need(P, 1, size, size);
+  const double per_item = (double)P.n_cols * (16.0 + (double)size * ((need.nz ? 4.0 : 0.0) + (need.alive ? 1.0 : 0.0) + (need.sorted ? 8.0 : 0.0)));
+  const int64_t grid_cap = (int64_t(1) << 30) / std::max(P.n_cols, 64);       // items x columns and items x groups stay ints
+  int64_t chunk = (int64_t)std::min((double)grid_cap, std::floor(windows_scratch_bytes() / per_item));
+  chunk = std::max<int64_t>(1, std::min(chunk, total));
+  need.rows = chunk * size;
+  need.n_utt = (int)chunk;
+  int rc = fs_reserve(ctx, fs_bytes(P, need), stream);
+  if (rc) return rc;
+  fs_carve(static_cast<char *>(ctx->fs_scratch), P, need);
+  std::memset(&P.mod, 0, sizeof(P.mod));
+  if (has_family(P.spec, SMILEHIP_FAM_MODULATION) && (rc = mod_prepare(ctx, P.spec, P.mod))) return rc;
+  for (int64_t first = 0; first < total; first += chunk) {      // chunks follow each other on the stream and share the scratch
+    P.it_first = first;
+    P.it_n = (int32_t)std::min(chunk, total - first);
+    P.out = d_func + first * ld_func;
+    P.ld_out = ld_func;
+    hipError_t e = launch_funcspec_items(P, fam_off, fam_want, stream);
+    if (e != hipSuccess) return fail(SMILEHIP_ERR_HIP, "%s: functionals kernel launch failed: %s", who, hipGetErrorString(e));
+  }
+  return SMILEHIP_OK;
+}
+}  // namespace
+
+extern "C" int smilehip_func_window_geometry(double period, double frame_size_sec, double frame_step_sec, int64_t rows,
+                                             int64_t *size_rows, int64_t *step_rows, int64_t *n_windows) {
+  if (!(period > 0.0)) return fail(SMILEHIP_ERR_INVALID, "smilehip_func_window_geometry: period must be > 0");
+  if (rows < 0) return fail(SMILEHIP_ERR_INVALID, "smilehip_func_window_geometry: rows must be >= 0");
+  if (!(frame_size_sec >= 0.0) || !(frame_step_sec >= 0.0))
+    return fail(SMILEHIP_ERR_INVALID, "smilehip_func_window_geometry: frameSize / frameStep must be >= 0");
+  if (frame_step_sec == 0.0)
+    return fail(SMILEHIP_ERR_INVALID, "frameStep = 0 is frameMode = full (one vector per utterance): use the full-mode entry points");
+  const int64_t size = (int64_t)std::round(frame_size_sec / period);          // winToVecProcessor.cpp:439-440, in double
+  if (size < 1)
+    return fail(SMILEHIP_ERR_INVALID, "frameSize %g s is less than one row of period %g s (frameSizeFrames = %lld)", frame_size_sec,
+                period, (long long)size);
+  int64_t step = (int64_t)std::round(frame_step_sec / period);               // :446-448
+  if (step == 0) step = size;                                                 // :455-456
+  if (size_rows) *size_rows = size;
+  if (step_rows) *step_rows = step;
+  if (n_windows) *n_windows = window_count(rows, size, step);
+  return SMILEHIP_OK;
+}
+
+extern "C" int smilehip_batch_func_windows(const smilehip_batch *b, int64_t size_rows, int64_t step_rows, int32_t rows_cut,
+                                           int64_t *win_off) {
+  if (!b || !win_off) return fail(SMILEHIP_ERR_INVALID, "smilehip_batch_func_windows: null argument");
+  if (size_rows < 1 || step_rows < 1) return fail(SMILEHIP_ERR_INVALID, "smilehip_batch_func_windows: size_rows and step_rows must be >= 1");
+  if (rows_cut < 0) return fail(SMILEHIP_ERR_INVALID, "smilehip_batch_func_windows: rows_cut must be >= 0");
+  win_off[0] = 0;
+  for (int32_t u = 0; u < b->n_utt; ++u)
+    win_off[u + 1] = win_off[u] + window_count(b->h_row_off[u + 1] - b->h_row_off[u] - rows_cut, size_rows, step_rows);
+  return SMILEHIP_OK;
+}
+
+extern "C" int smilehip_batch_funcspec_windows(smilehip_plan *plan, smilehip_batch *b, const smilehip_func_spec *spec,
+                                               const float *d_lld, int64_t ld_lld, int32_t col_first, int32_t n_cols, int32_t rows_cut,
+                                               int64_t size_rows, int64_t step_rows, float *d_func, int64_t ld_func, void *stream) {
+  const char *who = "smilehip_batch_funcspec_windows";
+  if (!plan || !b || b->plan != plan) return fail(SMILEHIP_ERR_INVALID, "%s: plan/batch mismatch", who);
+  const int per = windows_spec_check(spec, size_rows, step_rows, who);
+  if (per < 0) return per;
+  if (!plan->ctx) return fail(SMILEHIP_ERR_NO_DEVICE, "%s: host-only plan", who);
+  if (col_first < 0 || n_cols < 1 || col_first + n_cols > ld_lld)
+    return fail(SMILEHIP_ERR_INVALID, "%s: columns [%d, %d) outside the matrix (ld %lld)", who, col_first, col_first + n_cols, (long long)ld_lld);
+  if (rows_cut < 0) return fail(SMILEHIP_ERR_INVALID, "%s: rows_cut must be >= 0", who);
+  if (ld_func < (int64_t)n_cols * per) return fail(SMILEHIP_ERR_INVALID, "ld_func %lld < %d values per window", (long long)ld_func, n_cols * per);
+  std::vector<int64_t> win_off(size_t(b->n_utt) + 1);
+  int rc = smilehip_batch_func_windows(b, size_rows, step_rows, rows_cut, win_off.data());
+  if (rc) return rc;
+  const int64_t total = win_off[b->n_utt];
+  FsItemParams P;
+  std::memset(&P, 0, sizeof(P));
+  P.spec = *spec;
+  if (total > 0) {
+    if (!d_func || !d_lld) return fail(SMILEHIP_ERR_INVALID, "%s: null device pointer", who);
+    hipStream_t st = (hipStream_t)stream;
+    if (b->win_key[0] != size_rows || b->win_key[1] != step_rows || b->win_key[2] != rows_cut || !b->d_win_off.p) {
+      if (b->d_win_off.p) HIP_TRY(hipStreamSynchronize(st));      // an earlier call's kernels may still read the old prefix
+      b->win_key[0] = 0;
+      if ((rc = b->d_win_off.upload(win_off))) return rc;
+      b->win_key[0] = size_rows; b->win_key[1] = step_rows; b->win_key[2] = rows_cut;
+    }
+  }
+  P.x = d_lld;
+  P.ld_x = ld_lld;
+  P.col_first = col_first;
+  P.n_cols = n_cols;
+  P.row_off = b->d_row_off.p;
+  P.single_rows = -1;
+  P.it_win_off = b->d_win_off.p;
+  P.it_n_utt = b->n_utt;
+  return run_windows(plan->ctx, P, total, size_rows, step_rows, d_func, ld_func, (hipStream_t)stream, who);
+}
+
+extern "C" int smilehip_funcspec_matrix_windows(smilehip_context *ctx, const smilehip_func_spec *spec, const float *d_lld, int64_t ld_lld,
+                                                int64_t rows, int32_t cols, int64_t size_rows, int64_t step_rows, float *d_func,
+                                                int64_t ld_func, void *stream) {
+  const char *who = "smilehip_funcspec_matrix_windows";
+  const int per = windows_spec_check(spec, size_rows, step_rows, who);
+  if (per < 0) return per;
+  if (!ctx) return fail(SMILEHIP_ERR_NO_DEVICE, "%s: no device context", who);
+  if (rows < 0 || cols < 1 || ld_lld < cols) return fail(SMILEHIP_ERR_INVALID, "%s: bad argument", who);
+  if (ld_func < (int64_t)cols * per) return fail(SMILEHIP_ERR_INVALID, "ld_func %lld < %d values per window", (long long)ld_func, cols * per);
+  const int64_t total = window_count(rows, size_rows, step_rows);
+  if (total > 0 && (!d_lld || !d_func)) return fail(SMILEHIP_ERR_INVALID, "%s: null device pointer", who);
+  FsItemParams P;
+  std::memset(&P, 0, sizeof(P));
+  P.spec = *spec;
+  P.x = d_lld;
+  P.ld_x = ld_lld;
+  P.n_cols = cols;
+  P.single_rows = -1;
+  return run_windows(ctx, P, total, size_rows, step_rows, d_func, ld_func, (hipStream_t)stream, who);
+}
+
+// config/is09-13/IS09_emotion_core.func.conf.inc
+extern "C" int smilehip_funcspec_is09(smilehip_func_spec *s) {
+  if (!s) return fail(SMILEHIP_ERR_INVALID, "smilehip_funcspec_is09: null argument");
+  return smilehip_funcspec_from_mask(smilehip_functionals_is09_mask(), 0.01, s);
+}

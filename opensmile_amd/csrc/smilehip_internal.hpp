@@ -251,6 +251,9 @@ struct smilehip_batch {
   int32_t n_ftiles = 0;
   int32_t n_tiles = 0, n_dtiles = 0;
   bool all_even = true;      // every utterance with frames starts at an even sample offset
+  // fixed-window functionals (smilehip_batch_funcspec_windows): windows before each utterance for the geometry last asked for
+  DevBuf<int64_t> d_win_off;
+  int64_t win_key[3] = {0, 0, 0};   // size_rows, step_rows, rows_cut behind d_win_off (size_rows 0: none yet)
 };
 
 // helpers shared by the translation units (defined in smilehip_plan.cpp)

@@ -8,6 +8,9 @@
 //   smilextract_hip --set mfcc12_0_d_a|mfcc12_e_d_a|mfcc12_0_d_a_z|mfcc12_e_d_a_z|plp_0_d_a|plp_e_d_a|plp_0_d_a_z|plp_e_d_a_z
 //                   (-I in.wav | -filelist list.txt) [-O lld.htk] [-csvoutput lld.csv]
 //   smilextract_hip --set is09_emotion  (-I in.wav | -filelist list.txt) [-O func.arff] [-csvoutput func.csv]
+//                   [-frameMode fixed -frameSize s -frameStep s [-frameCenterSpecial left]]   functionals over fixed windows: what
+//                   replacing config/shared/FrameModeFunctionals.conf.inc does in the reference -- one row per window in the
+//                   ARFF / CSV / functionals HTK file (is09_emotion only; -frameMode full is the default)
 //   smilextract_hip --set compare16_lld (-I in.wav | -filelist list.txt) [-lldcsvoutput lld.csv] [-lldhtkoutput lld.htk]
 //                   (the 130-column LLD level of ComParE_2016 only)
 //   smilextract_hip --set compare16     same options as is09_emotion: the whole ComParE_2016.conf, LLD level + 6373 functionals
@@ -112,7 +115,8 @@ struct Persist {
 static int run_main(int argc, char **argv, Persist *ps) {
   std::map<std::string, std::string> opt, conf_cmdline;
   const char *with_value[] = {"--set", "-C", "-I", "-filelist", "-O", "-csvoutput", "-htkoutput", "-lldcsvoutput", "-lldhtkoutput",
-                              "-instname", "-N", "-outdir", "--device", "--rank", "--world", "--chunk-files", "--master-addr", "--master-port"};
+                              "-instname", "-N", "-outdir", "--device", "--rank", "--world", "--chunk-files", "--master-addr", "--master-port",
+                              "-frameMode", "-frameSize", "-frameStep", "-frameCenterSpecial"};
   bool with_conf = false, print_fingerprint = false, describe_only = false, gather = false;
   for (int i = 1; i < argc; ++i)
     if (!strcmp(argv[i], "-C")) with_conf = true;
@@ -229,6 +233,24 @@ static int run_main(int argc, char **argv, Persist *ps) {
   const bool out_subset = egm_subset || cmp_subset;
   if (out_subset && gather) die("--gather is not available with a set that writes a column selection (" + set + "): gather the whole vectors and select");
   const bool has_func = is09 || cmp16f || egm;
+  // ---- functionals over fixed windows (cWinToVecProcessor frameMode = fixed): IS09_emotion's one instance
+  const std::string frame_mode = opt.count("-frameMode") ? opt["-frameMode"] : "full";
+  if (frame_mode != "full" && frame_mode != "fixed")
+    die("-frameMode " + frame_mode + ": full and fixed are built (var, list and meta are not)");
+  const bool windows = frame_mode == "fixed";
+  if (opt.count("-frameCenterSpecial") && opt["-frameCenterSpecial"] != "left")
+    die("-frameCenterSpecial " + opt["-frameCenterSpecial"] + ": only left is built");
+  if (windows && !is09)
+    die("-frameMode fixed is built for --set is09_emotion only (" + (set.empty() ? std::string("-C file") : "--set " + set) +
+        ": its functionals levels read levels of different lengths, see DESIGN.md)");
+  if (windows && gather) die("--gather is not available with -frameMode fixed (the rows per file vary): write per-rank files and concatenate");
+  if (windows && (!opt.count("-frameSize") || !opt.count("-frameStep"))) die("-frameMode fixed needs -frameSize and -frameStep (seconds)");
+  const double frame_size_sec = windows ? atof(opt["-frameSize"].c_str()) : 0.0, frame_step_sec = windows ? atof(opt["-frameStep"].c_str()) : 0.0;
+  if (windows) {                                            // refused before any file is read: a size below one row, a step of 0 s (= full mode)
+    smilehip_lld_config c9;
+    smilehip_config_is09_lld(&c9);
+    check(smilehip_func_window_geometry(c9.frame_step_sec, frame_size_sec, frame_step_sec, 0, nullptr, nullptr, nullptr), "-frameSize / -frameStep");
+  }
   // the eight files of config/mfcc and config/plp, by their names in lower case
   std::string variant;                             // upper-case config name for smilehip_config_htk_variant
   for (char ch : set) variant += (char)toupper((unsigned char)ch);
@@ -385,6 +407,7 @@ static int run_main(int argc, char **argv, Persist *ps) {
            : (egm ? (egm_subset ? select_names(func_names_egemaps(), sel_func) : func_names_egemaps()) : std::vector<std::string>()));
   const uint32_t fmask = smilehip_functionals_is09_mask();
   std::string err;
+  double func_period = 0.0;                                 // -frameMode fixed: seconds between a file's function rows (frameTime); 0 in full mode
 
   // ---- staging (round 5). The route is bound by the host, not the device (the MFCC kernel takes 0.4 ms per 1000 x 10 s files,
   // PCIe 6 ms): the samples are read straight into PAGE-LOCKED memory (probe the headers, lay the chunk out, pread every data
@@ -500,6 +523,8 @@ static int run_main(int argc, char **argv, Persist *ps) {
   struct SinkWork {
     std::vector<size_t> idx;
     std::vector<int64_t> row_off, true_off;
+    std::vector<int64_t> win_off;                            // -frameMode fixed: function rows before each file of the group
+    double func_period = 0.0;                                // ... and the seconds between them (frameStep in rows x the level's period)
     std::vector<float> func, lld_vec;
     const float *lld = nullptr;
     int n_out = 0, n_func = 0;
@@ -642,7 +667,23 @@ static int run_main(int argc, char **argv, Persist *ps) {
                               : (cmp16f ? smilehip_functionals_compare16_count() : (egm ? smilehip_functionals_egemaps_count() : 0));
       w->n_func = n_func;
       std::vector<float> &func = w->func;
-      if (has_func) {
+      if (has_func && windows) {
+        // one function row per window, win_off[i + 1] - win_off[i] of them for file i: IS09's windows run over all rows of the LLD level
+        int64_t size_rows = 0, step_rows = 0;
+        check(smilehip_func_window_geometry(g.frame_period, frame_size_sec, frame_step_sec, 0, &size_rows, &step_rows, nullptr), "-frameSize / -frameStep");
+        w->win_off.assign(idx.size() + 1, 0);
+        w->func_period = (double)step_rows * g.frame_period;
+        func_period = w->func_period;
+        check(smilehip_batch_func_windows(b, size_rows, step_rows, 0, w->win_off.data()), "smilehip_batch_func_windows");
+        const int64_t n_win = w->win_off.back();
+        smilehip_func_spec spec09;
+        check(smilehip_funcspec_is09(&spec09), "smilehip_funcspec_is09");
+        d_func = dev_reserve(dev_func[slot], (uint64_t)std::max<int64_t>(n_win, 1) * n_func * 4);
+        check(smilehip_batch_funcspec_windows(plan, b, &spec09, (const float *)d_lld, n_out, 0, n_out, 0, size_rows, step_rows,
+                                              (float *)d_func, n_func, st), "smilehip_batch_funcspec_windows");
+        func.resize((size_t)n_win * (size_t)n_func);
+        if (n_win > 0) check(smilehip_copy_to_host(ctx, func.data(), d_func, (uint64_t)func.size() * 4, st), "copy_to_host");
+      } else if (has_func) {
         d_func = dev_reserve(dev_func[slot], (uint64_t)idx.size() * n_func * 4);
         if (is09)
           check(smilehip_batch_functionals(plan, b, (const float *)d_lld, n_out, fmask, (float *)d_func, n_func, st),
@@ -691,7 +732,11 @@ static int run_main(int argc, char **argv, Persist *ps) {
       smilehip_batch_destroy(b);
       dlap(t_dev_create);
       // the summary rows of the chunk (appended in list order below)
-      for (size_t i = 0; i < idx.size() && has_func; ++i) {
+      for (size_t i = 0; i < idx.size() && has_func && windows; ++i) {     // a file's windows, none if it is shorter than one
+        const float *fv = func.data() + (size_t)w->win_off[i] * (size_t)n_func;
+        func_rows[idx[i] - j0].assign(fv, fv + (size_t)(w->win_off[i + 1] - w->win_off[i]) * (size_t)n_func);
+      }
+      for (size_t i = 0; i < idx.size() && has_func && !windows; ++i) {
         if (row_off[i + 1] - row_off[i] <= 0) continue;     // no frame -> the reference writes no instance
         const float *fv = func.data() + i * (size_t)n_func;
         if (out_subset) func_rows[idx[i] - j0] = select_columns(fv, 1, n_func, sel_func);
@@ -735,7 +780,12 @@ static int run_main(int argc, char **argv, Persist *ps) {
               return;
             }
           }
-          if (has_func && r > 0) {                          // no frame -> the reference writes no instance
+          if (has_func && windows) {
+            const int64_t n_win = w->win_off[i + 1] - w->win_off[i];
+            if (n_win > 0 && opt.count("-htkoutput") && opt.at("-htkoutput") != "?")
+              if (!write_htk(per_file(job, "-htkoutput", ".func.htk"), w->func.data() + (size_t)w->win_off[i] * (size_t)n_func, n_win, n_func,
+                             n_func, w->func_period, 9, err)) { die(err); return; }
+          } else if (has_func && r > 0) {                   // no frame -> the reference writes no instance
             const float *fv = w->func.data() + i * (size_t)n_func;
             int n_fw = n_func;
             std::vector<float> f_sel;
@@ -773,17 +823,20 @@ static int run_main(int argc, char **argv, Persist *ps) {
     for (size_t j = j0; j < j1 && has_func && !gather; ++j) {
       const std::vector<float> &fv = func_rows[j - j0];
       if (fv.empty()) continue;
-      const int n_func = (int)fv.size();
+      // full mode: one row of fv.size() values; fixed windows: as many rows of the set's width as the file has windows, frameTime
+      // = the time of the window's first row
+      const int n_func = windows ? (int)fnames.size() : (int)fv.size();
+      const int64_t n_rows = (int64_t)(fv.size() / (size_t)n_func);
       if (opt.count("-O") && opt["-O"] != "?") {
         ArffOptions ao;
         ao.instance_name = jobs[j].inst;
-        if (!write_arff(summary_path(opt["-O"]), fnames, fv.data(), 1, n_func, n_func, 0.0, ao, err)) die(err);
+        if (!write_arff(summary_path(opt["-O"]), fnames, fv.data(), n_rows, n_func, n_func, func_period, ao, err)) die(err);
       }
       if (opt.count("-csvoutput") && opt["-csvoutput"] != "?") {
         CsvOptions co;
         co.instance_name = jobs[j].inst;
         co.append = true;
-        if (!write_csv(summary_path(opt["-csvoutput"]), fnames, fv.data(), 1, n_func, n_func, 0.0, nullptr, co, err)) die(err);
+        if (!write_csv(summary_path(opt["-csvoutput"]), fnames, fv.data(), n_rows, n_func, n_func, func_period, nullptr, co, err)) die(err);
       }
     }
     t_device += now() - tf0;
