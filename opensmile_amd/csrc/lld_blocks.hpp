@@ -117,8 +117,8 @@ struct WaveG {                                           // (all 64 lanes call t
 
 // Sixteen consecutive lanes (a DPP row) work on one frame, four frames per wave: the reductions are butterflies of row
 // rotations (row_ror 8, 4, 2, 1 -- vector-ALU moves), after which every lane of the row holds the row's result. (Sums of doubles:
-// another association than WaveG's tree; like that one it differs from the reference's sequential sum by nothing that
-// survives the rounding to float that follows every use.)
+// another association than WaveG's tree; like that one it is for ONE-SIGNED sums only, where it stays within one float ulp of the
+// reference's sequential sum -- sums that cancel or feed a threshold take the reference's order, lld_blocks_compare.hpp.)
 template <int ROR>
 __device__ __forceinline__ int row_ror_i(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x120 + ROR, 0xf, 0xf, true); }
 template <int ROR>

@@ -65,13 +65,20 @@ __device__ __forceinline__ float seq_sum_f32(const float *x, int lo, int hi) {
   return s;
 }
 
+// cSpectral's double sums fall in two classes (tests/golden/order_witnesses.npz holds spectra that tell the orders apart,
+// tests/test_gpu_order_witnesses.py runs them):
+//   sequence-decided  sums whose ORDER can move the float result by more than an ulp, so they are added bin after bin like the
+//                     reference's loops, by one thread: the third central moment (skewness, spectral.cpp:1344-1364: on a flat
+//                     spectrum its terms cancel and the order decides every bit); frameSum = sumB and the centroid numerator sumA
+//                     (:762-767, :1093-1097, :1256-1311: the slope N sumA - Sf sumB cancels on a mirrored spectrum, the float
+//                     centroid feeds every moment -- d m3 / d ctr = -3 m2 --, and the running sumB is compared with a share of
+//                     its own total for the roll-off points, :1102-1122, where one ulp of a double moves the result by a bin)
+//   one-signed        band energies, flux, entropy, second and fourth moment: sums of non-negative terms that keep their fixed
+//                     trees. A tree and the chain differ by at most K 2^-53 relative, the float results are equal or adjacent:
+//                     within ONE float ulp of the reference, bit-equal except where the exact value lies within ~1e-16 of a float
+//                     rounding midpoint.
 // sum of x[0 .. n) in index order, one double addition after the other (n even, x 16-byte aligned); the loads run a block ahead.
-// For the one double sum of cSpectral whose terms cancel: the third central moment (skewness, spectral.cpp:1344-1364) of a flat
-// spectrum -- a single click inside digital silence -- is rounding noise only, so the ORDER of the additions decides every bit of
-// the result; the sums of one-signed terms (energy, centroid, variance, kurtosis, entropy, flux) keep their fixed trees. (The slope
-// is a difference of two of those and cancels on a flat spectrum as well; it came out the binary's on every hard signal
-// (tests/test_gpu_hard_signals.py) and stays as it is. Cost of the chain: the W = 8 wave kernel of 32 .. 48 kHz input holds the
-// W terms across the float chains, 169 registers, two waves per SIMD instead of three.)
+// (What the chains cost -- registers, occupancy, step time: DESIGN.md 4.3, profiles/order_chains_kernel_resources_diff.txt.)
 __device__ __forceinline__ double seq_sum_f64(const double *x, int n) {
   double s = 0.0;
   double2 u = *reinterpret_cast<const double2 *>(x);
@@ -85,14 +92,63 @@ __device__ __forceinline__ double seq_sum_f64(const double *x, int n) {
   return s;
 }
 
+// frameSum (= sumB) and the centroid numerator sumA in the reference's order, with every running value of sumB kept: ONE thread
+// walks the bins, the two chains interleaved. pw1[i]: the power of bin i + 1; x[0 .. n): on entry the terms fj p of bins 1 .. n
+// (formed by all threads), on return the inclusive prefix of the powers, x[i] = p_1 + .. + p_(i+1) as the reference's running sumC
+// holds it after bin i + 1 (the same additions as sumB's, so x[n - 1] == sumB). n a multiple of 4, x 16-byte aligned; the loads run
+// a block ahead of the adds.
+__device__ __forceinline__ void seq_chains_f64(const float *pw1, double *x, int n, double &sumB, double &sumA) {
+  double sb = 0.0, sa = 0.0;
+  double2 a0 = *reinterpret_cast<const double2 *>(x), a1 = *reinterpret_cast<const double2 *>(x + 2);
+  float p0 = pw1[0], p1 = pw1[1], p2 = pw1[2], p3 = pw1[3];
+  for (int i = 4; i <= n; i += 4) {
+    double2 b0 = a0, b1 = a1;
+    float q0 = p0, q1 = p1, q2 = p2, q3 = p3;
+    if (i < n) {
+      b0 = *reinterpret_cast<const double2 *>(x + i); b1 = *reinterpret_cast<const double2 *>(x + i + 2);
+      q0 = pw1[i]; q1 = pw1[i + 1]; q2 = pw1[i + 2]; q3 = pw1[i + 3];
+    }
+    double2 c0, c1;
+    sb += (double)p0; sa += a0.x; c0.x = sb;
+    sb += (double)p1; sa += a0.y; c0.y = sb;
+    sb += (double)p2; sa += a1.x; c1.x = sb;
+    sb += (double)p3; sa += a1.y; c1.y = sb;
+    *reinterpret_cast<double2 *>(x + i - 4) = c0;
+    *reinterpret_cast<double2 *>(x + i - 2) = c1;
+    a0 = b0; a1 = b1; p0 = q0; p1 = q1; p2 = q2; p3 = q3;
+  }
+  sumB = sb; sumA = sa;
+}
+
+// The same two chains where there is no room for the sumA terms: the thread forms fj p = (F0 j) p itself. x[0 .. n) receives the
+// running sumB; pw1 may lie INSIDE x's memory as long as (float *)(x + i) <= pw1 + i + 4 for every i <= n (the powers of a block are
+// read before the previous block's running sums are written).
+__device__ __forceinline__ void seq_chains_axis_f64(const float *pw1, double F0, double *x, int n, double &sumB, double &sumA) {
+  double sb = 0.0, sa = 0.0, jd = 1.0;
+  float p0 = pw1[0], p1 = pw1[1], p2 = pw1[2], p3 = pw1[3];
+  for (int i = 4; i <= n; i += 4) {
+    float q0 = p0, q1 = p1, q2 = p2, q3 = p3;
+    if (i < n) { q0 = pw1[i]; q1 = pw1[i + 1]; q2 = pw1[i + 2]; q3 = pw1[i + 3]; }
+    double2 c0, c1;
+    sb += (double)p0; sa += (F0 * jd) * (double)p0; c0.x = sb; jd += 1.0;
+    sb += (double)p1; sa += (F0 * jd) * (double)p1; c0.y = sb; jd += 1.0;
+    sb += (double)p2; sa += (F0 * jd) * (double)p2; c1.x = sb; jd += 1.0;
+    sb += (double)p3; sa += (F0 * jd) * (double)p3; c1.y = sb; jd += 1.0;
+    *reinterpret_cast<double2 *>(x + i - 4) = c0;
+    *reinterpret_cast<double2 *>(x + i - 2) = c1;
+    p0 = q0; p1 = q1; p2 = q2; p3 = q3;
+  }
+  sumB = sb; sumA = sa;
+}
+
 // R11 cSpectral::processVector with ComParE_2016's option set ([is13_spectral]: bands 250-650 and
 // 1000-4000, roll-off .25/.5/.75/.9, flux, centroid, entropy, variance, skewness, kurtosis, slope,
 // sharpness, harmonicity; squareInput = 1, freqRange 0-0, oldSlopeScale = 1; spectral.cpp:586-1560).
 // Thread i of 256 owns bin j = i+1. mg / pw: magnitudes and powers of the K = 257 bins, prev: the
 // previous frame's magnitudes (ignored when first). red: 64 doubles, cum: 256 doubles, pk_val[4],
 // pk_has[4] of LDS scratch. Writes sp[0..14]; thread 0 returns valid frameSum-based values; ends
-// with a block barrier. The sums are double like the reference's, combined in a fixed tree order (the third moment's terms
-// cancel: thread 0 adds them bin after bin, seq_sum_f64).
+// with a block barrier. The sums are double like the reference's: the sequence-decided ones added bin after bin by thread 0
+// (seq_chains_f64, seq_sum_f64), the one-signed ones combined in a fixed tree order (the two classes: above seq_sum_f64).
 __device__ __forceinline__ void spectral_frame(const float *mg, const float *pw, const float *prev, bool first,
                                                const SpectralConsts &C, int K, double *red, double *cum, float *pk_val,
                                                int *pk_has, float *sp) {
@@ -102,11 +158,16 @@ __device__ __forceinline__ void spectral_frame(const float *mg, const float *pw,
   const int lane = tid & 63, wave = tid >> 6;
   const float pf = pw[j];
   const double p = (double)pf, fj = F0 * j;
-  double v1[6];
-  v1[0] = p;                                            // frame energy (:762-767), centroid denominator
-  v1[1] = fj * p;                                       // centroid numerator (:1256-1330)
-  v1[2] = 0.0;                                          // (sharpness: a float chain, below)
-  { const double myB = (double)mg[j] - (double)prev[j]; v1[3] = first ? 0.0 : myB * myB; }   // flux (:1124-1254)
+  // frame energy (:762-767) = centroid denominator, centroid numerator (:1256-1330) and the roll-off prefix: the reference's chains
+  cum[tid] = fj * p;
+  __syncthreads();
+  if (tid == 0) {
+    double sb, sa;
+    seq_chains_f64(pw + 1, cum, 256, sb, sa);
+    red[62] = sb; red[63] = sa;                         // (block_sum_n uses red[0 .. 4 NV); its barriers publish these and cum)
+  }
+  double v1[3];
+  { const double myB = (double)mg[j] - (double)prev[j]; v1[0] = first ? 0.0 : myB * myB; }   // flux (:1124-1254)
 #pragma unroll
   for (int b = 0; b < 2; ++b) {                         // band energies (:779-853), edges resolved on the host
     auto part = [&](int k) {
@@ -117,22 +178,15 @@ __device__ __forceinline__ void spectral_frame(const float *mg, const float *pw,
       if (k == C.band_iR[b]) c += pk * C.band_wR[b];
       return c;
     };
-    v1[4 + b] = part(j) + (tid == 0 ? part(0) : 0.0);
+    v1[1 + b] = part(j) + (tid == 0 ? part(0) : 0.0);
   }
-  block_sum_n<6>(v1, red);
-  const double frameSum = v1[0], sumA = v1[1];
+  block_sum_n<3>(v1, red);
+  const double frameSum = red[62], sumA = red[63];
   float ctr = 0.0f;
   if (frameSum != 0.0) ctr = (float)(sumA / frameSum);
-  // roll-off (:1102-1122): inclusive prefix of the power in double, first bin whose prefix reaches the share
+  // roll-off (:1102-1122): the first bin whose running sum reaches the share (the running sum never falls: one bin at most)
   {
-    double c = p;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const double o = __shfl_up(c, off, 64); if (lane >= off) c += o; }
-    if (lane == 63) red[wave] = c;
-    __syncthreads();
-    for (int w = 0; w < wave; ++w) c += red[w];
-    cum[tid] = c;
-    __syncthreads();
+    const double c = cum[tid];
     const double before = tid ? cum[tid - 1] : -1.0;
     const double rollOff[4] = {0.25, 0.50, 0.75, 0.90};
 #pragma unroll
@@ -190,13 +244,13 @@ __device__ __forceinline__ void spectral_frame(const float *mg, const float *pw,
   __syncthreads();
   if (tid == 0) {
     const double mom3 = seq_sum_f64(cum, 256);
-    sp[0] = (float)(v1[4] / (double)nBins);
-    sp[1] = (float)(v1[5] / (double)nBins);
+    sp[0] = (float)(v1[1] / (double)nBins);
+    sp[1] = (float)(v1[2] / (double)nBins);
     float c2 = 0.0f;
     const float sumAA = sumAA_seq;
     if (frameSum != 0.0) c2 = (float)(sumAA / frameSum);
     sp[13] = (float)(0.11 * c2);
-    const double flux = v1[3] / (double)nBins;
+    const double flux = v1[0] / (double)nBins;
     sp[6] = (!first && flux > 0.0) ? (float)sqrt(flux) : 0.0f;
     sp[7] = ctr;
     sp[8] = (float)(-v2[0]);
@@ -233,12 +287,12 @@ __device__ __forceinline__ void wave_sum4(const double (&v)[4][NV], double (&tot
 // spectral_frame for one wave, K = 64 W + 1 bins (W = 4: the 512-point spectrum of 20 ms frames at 16 kHz, the tuned case; W = 2 / 8:
 // the 256- / 1024-point spectra of other sample rates): no LDS scratch, no barriers. mg / pw / prev as above; sp[0..14] written
 // by lane 0 (roll-off points by the lane that owns the crossing bin).
-// chain: 128 W floats of LDS scratch (16-byte aligned) for the two float chains.
-// (The sums are double accumulators of float-derived terms whose results are rounded to float: the reference adds bin after bin, any
-// other order differs from it by a few ulps of the DOUBLE and gives the same float except with probability ~1e-9 per value -- the
-// third moment excepted, whose terms cancel: its sum keeps the reference's order, seq_sum_f64. Round 3:
-// the lane's W terms are added first and ONE wave tree follows per quantity -- a quarter of the reductions of the block form's
-// per-group trees, which cost ~1200 of the kernel's ~4000 instruction slots per frame.)
+// chain: 128 W floats of LDS scratch (16-byte aligned): the sumA terms / the running sumB, then the two float chains, then the
+// third moment's terms.
+// (The two classes of sums: above seq_sum_f64. The sequence-decided ones -- frameSum, sumA with the roll-off prefix, the third
+// moment -- are added bin after bin by lane 0; the one-signed ones keep a tree. Round 3: the lane's W terms are added first and ONE
+// wave tree follows per quantity -- a quarter of the reductions of the block form's per-group trees, which cost ~1200 of the
+// kernel's ~4000 instruction slots per frame.)
 template <int NV, int W>
 __device__ __forceinline__ void wave_sumw(const double (&v)[W][NV], double (&tot)[NV]) {
 #pragma unroll
@@ -256,18 +310,17 @@ __device__ __forceinline__ void spectral_frame_wave(const float *mg, const float
   const int lo = 1, hi = K - 1, nBins = K - 1;
   const int lane = threadIdx.x & 63;
   float pf[W], tsh[W];
-  double p[W], fj[W], v1[W][6];
+  double p[W], fj[W], v1[W][3];
+  double *chain_d = reinterpret_cast<double *>(chain);
 #pragma unroll
   for (int w = 0; w < W; ++w) {
     const int tid = lane + 64 * w, j = tid + 1;
     pf[w] = pw[j];
     p[w] = (double)pf[w];
     fj[w] = F0 * j;
-    v1[w][0] = p[w];
-    v1[w][1] = fj[w] * p[w];
-    v1[w][2] = 0.0;
+    chain_d[tid] = fj[w] * p[w];                        // centroid numerator terms, for lane 0's chain
     tsh[w] = (float)(C.sharp_w[tid] * p[w]);            // sharpness term, :1455 / :1469
-    { const double myB = (double)mg[j] - (double)prev[j]; v1[w][3] = first ? 0.0 : myB * myB; }
+    { const double myB = (double)mg[j] - (double)prev[j]; v1[w][0] = first ? 0.0 : myB * myB; }
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
       auto part = [&](int k) {
@@ -278,43 +331,39 @@ __device__ __forceinline__ void spectral_frame_wave(const float *mg, const float
         if (k == C.band_iR[b]) c += pk * C.band_wR[b];
         return c;
       };
-      v1[w][4 + b] = part(j) + (tid == 0 ? part(0) : 0.0);
+      v1[w][1 + b] = part(j) + (tid == 0 ? part(0) : 0.0);
     }
   }
-  double t1v[6];
-  wave_sumw<6, W>(v1, t1v);
-  const double frameSum = t1v[0], sumA = t1v[1];
+  // frame energy = centroid denominator, centroid numerator and the roll-off prefix: the reference's chains, lane 0 walks the bins
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  double frameSum = 0.0, sumA = 0.0;
+  if (lane == 0) seq_chains_f64(pw + 1, chain_d, 64 * W, frameSum, sumA);
+  frameSum = wave_first_d(frameSum);
+  sumA = wave_first_d(sumA);
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  double t1v[3];
+  wave_sumw<3, W>(v1, t1v);
   float ctr = 0.0f;
   if (frameSum != 0.0) ctr = (float)(sumA / frameSum);
-  // roll-off: inclusive prefix in the block version's order (scan inside each group of 64, then + the earlier groups' totals)
+  // roll-off (:1102-1122): the first bin whose running sum reaches the share (the running sum never falls: one bin at most)
   {
-    double c[W], red[W];
-#pragma unroll
-    for (int w = 0; w < W; ++w) {
-      double x = p[w];
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) { const double o = __shfl_up(x, off, 64); if (lane >= off) x += o; }
-      red[w] = __shfl(x, 63, 64);
-      c[w] = x;
-    }
-#pragma unroll
-    for (int w = 1; w < W; ++w)
-#pragma unroll
-      for (int w2 = 0; w2 < w; ++w2) c[w] += red[w2];
     const double rollOff[4] = {0.25, 0.50, 0.75, 0.90};
 #pragma unroll
     for (int w = 0; w < W; ++w) {
       const int tid = lane + 64 * w, j = tid + 1;
-      const double up1 = __shfl_up(c[w], 1, 64);
-      const double prev63 = __shfl(c[w > 0 ? w - 1 : 0], 63, 64);
-      const double before = (lane == 0) ? (w == 0 ? -1.0 : prev63) : up1;
+      const double c = chain_d[tid];
+      const double before = tid ? chain_d[tid - 1] : -1.0;
 #pragma unroll
       for (int i = 0; i < 4; i++) {
         const double th = rollOff[i] * frameSum;
-        if (c[w] >= th && (tid == 0 || !(before >= th))) sp[2 + i] = (float)(F0 * j);
+        if (c >= th && (tid == 0 || !(before >= th))) sp[2 + i] = (float)(F0 * j);
       }
     }
   }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // (the running sums have been read: the float chains' terms take their place below)
+  __builtin_amdgcn_wave_barrier();
   // harmonicity: alternating peaks/valleys, distance to the previous one
   float hc[W];
   {
@@ -385,20 +434,19 @@ __device__ __forceinline__ void spectral_frame_wave(const float *mg, const float
   // the third moment's terms take the float chains' place (128 W floats = 64 W doubles), bin after bin like the reference's loop
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
-  double *chain_d = reinterpret_cast<double *>(chain);
 #pragma unroll
   for (int w = 0; w < W; ++w) chain_d[lane + 64 * w] = m3t[w];
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
   if (lane == 0) {
     const double mom3 = seq_sum_f64(chain_d, 64 * W);
-    sp[0] = (float)(t1v[4] / (double)nBins);
-    sp[1] = (float)(t1v[5] / (double)nBins);
+    sp[0] = (float)(t1v[1] / (double)nBins);
+    sp[1] = (float)(t1v[2] / (double)nBins);
     float c2 = 0.0f;
     const float sumAA = sumAA_seq;
     if (frameSum != 0.0) c2 = (float)(sumAA / frameSum);
     sp[13] = (float)(0.11 * c2);
-    const double flux = t1v[3] / (double)nBins;
+    const double flux = t1v[0] / (double)nBins;
     sp[6] = (!first && flux > 0.0) ? (float)sqrt(flux) : 0.0f;
     sp[7] = ctr;
     sp[8] = (float)(-t2v[0]);

@@ -13,15 +13,14 @@
 //               positions that entered (11 samples per lane, neighbours by row rotation); integers: any order is the reference's sum
 //   transform   oo_quad256 (the reference's rdft network, 16 points per lane), magnitudes in registers
 //   mel / PLP   terms to LDS, a lane takes band j and band 25 - j (narrow + wide), DCT on 14 lanes, the auditory sum on lane 15
-//   descriptors sums over bins: per lane, then four row rotations; roll-off: a row scan per register + running offset; harmonicity's
+//   descriptors sums over bins: per lane, then four row rotations; frame energy, centroid numerator and the roll-off prefix: lane 0's chains; harmonicity's
 //               "previous flagged bin" from row ballots; the two FLOAT_DMEM chains by lanes 0 and 1 of the row, one chain each
-// Sums of doubles are associated otherwise than in the wave form (as that one's are otherwise than the block form's and the
-// reference's bin-after-bin loops): every one of them is rounded to float or compared with a threshold afterwards, and differs
-// from the sequential sum only where the double's last bits decide that rounding (lld_blocks_compare.hpp; ~1e-9 per value --
-// the bench's accuracy object counts the cells). That holds for sums of non-negative terms only: the third central moment's
-// terms cancel (a click in digital silence has a flat spectrum, its skewness is the rounding noise of the sum), so lane 0 adds
-// them bin after bin like the reference's loop (seq_sum_f64; tests/test_gpu_hard_signals.py, clicks_in_zeros). Float chains keep
-// the reference's order operation for operation.
+// The one-signed double sums (band energies, flux, entropy, second and fourth moment) are associated otherwise than in the wave form
+// (as that one's are otherwise than the block form's and the reference's bin-after-bin loops): within one float ulp of the
+// reference, bit-equal except where the exact value lies on a float rounding midpoint. The sequence-decided ones (frame energy,
+// centroid numerator, roll-off prefix, third moment: the two classes are set out in lld_blocks_compare.hpp above seq_sum_f64) are
+// added bin after bin like the reference's loops by lane 0 of the row. Float chains keep the reference's order operation for
+// operation.
 // The shipped geometry only (16 kHz: N = 320, hop 160, FFT 512, 96 zeros in front, 60 ms = 960 samples, 26 bands, 14 cepstra,
 // int16 input, reference-order tables): launch_compare checks it.
 #pragma once
@@ -47,6 +46,7 @@ namespace cq {
 constexpr int kWavesPerSimd = 2;
 constexpr int kBinsGroup = 3;                                // bins of the entropy / moments loop whose operations may interleave
 constexpr int kN = 320, kH = 160, kPad = 96, kN60 = 960, kM = 256, kK = 257, kBands = 26, kMfcc = 14;
+constexpr int kPowTop = 2 * kQuadZPairs - 257;               // second copy of the 257 powers: the last 257 floats of the row's z (bin 1 sixteen-byte aligned)
 constexpr int kRowFloats = 2 * kQuadZPairs + 64 + 16;      // z (544 floats: transform, then mel terms / powers / chains) | lmel[32] | aud[32] | the row's state[16]
 // shared tables: log table (128 double2 = 512 floats, first: 16-byte aligned) | sharpness weights (256 doubles = 512 floats) |
 // window[320] | mel coef[260] | band ranges[128] | DCT rows[16 x 32]
@@ -275,26 +275,33 @@ __device__ __forceinline__ void compare_frame_quad_body(const LldParams &P, cons
       // ---- R11 cSpectral (spectral.cpp:586-1560, ComParE's option set)
       const bool first = t == 0;
 #pragma unroll
-      for (int m = 0; m < 17; ++m) { const int k = j + 16 * m; if (k <= kM) zf[k] = mv[m] * mv[m]; }
+      for (int m = 0; m < 17; ++m) { const int k = j + 16 * m; if (k <= kM) { const float pk = mv[m] * mv[m]; zf[k] = pk; zf[kPowTop + k] = pk; } }
       QuadG::sync();
-      double s0 = 0.0, s1 = 0.0, s4 = 0.0, s5 = 0.0;
+      double s4 = 0.0, s5 = 0.0;
       if (first) s3 = 0.0;
 #pragma unroll
       for (int m = 0; m < 17; ++m) {
         const int k = j + 16 * m;
         const double p = (double)(mv[m] * mv[m]);
-        if (k >= 1 && k <= kM) {
-          s0 += p;
-          s1 += (F0 * k) * p;
-        }
         // band energies (:779-853): the bins strictly inside a band here, its two edge bins (weighted) once per row below
         if (k > Q.band_iL[0] && k < Q.band_iR[0]) s4 += p;
         if (k > Q.band_iL[1] && k < Q.band_iR[1]) s5 += p;
       }
-      const double frameSum = QuadG::sum(s0, nullptr), sumA = QuadG::sum(s1, nullptr), fluxS = QuadG::sum(s3, nullptr);
+      const double fluxS = QuadG::sum(s3, nullptr);
       double bandE0 = QuadG::sum(s4, nullptr), bandE1 = QuadG::sum(s5, nullptr);
       bandE0 += (double)zf[Q.band_iL[0]] * Q.band_wL[0]; bandE0 += (double)zf[Q.band_iR[0]] * Q.band_wR[0];      // (launch_compare: iL < iR <= 256)
       bandE1 += (double)zf[Q.band_iL[1]] * Q.band_wL[1]; bandE1 += (double)zf[Q.band_iR[1]] * Q.band_wR[1];
+      // frame energy (:762-767) = centroid denominator, centroid numerator (:1256-1330) and the roll-off prefix are sequence-decided
+      // (lld_blocks_compare.hpp): lane 0 of the row walks bins 1 .. 256 with the reference's two chains and leaves every running
+      // sumB as a double in the row's z -- over the powers' first copy; it reads their second copy at the top of z, which the
+      // running sums reach only behind the reads (seq_chains_axis_f64)
+      QuadG::sync();                                       // (the first copy's edge bins have been read)
+      double *zd = reinterpret_cast<double *>(zf);
+      double frameSum = 0.0, sumA = 0.0;
+      if (j == 0) seq_chains_axis_f64(zf + kPowTop + 1, F0, zd, kM, frameSum, sumA);
+      frameSum = lane_d(frameSum, row_base4, 0);
+      sumA = lane_d(sumA, row_base4, 0);
+      QuadG::sync();
       float ctr = 0.0f;
       if (frameSum != 0.0) ctr = (float)(sumA / frameSum);
       // (what is final already is written now: the sums it comes from need not live to the end of the pass)
@@ -313,35 +320,32 @@ __device__ __forceinline__ void compare_frame_quad_body(const LldParams &P, cons
         sp[12] = (float)(slope * (Nind - 1.0));
       }
       QPHASE(4);
-      // roll-off (:1102-1122): inclusive prefix of the powers of bins 1 .. 256, first bin whose prefix reaches the share
+      // roll-off (:1102-1122): the first bin whose running sum reaches the share (the running sum never falls: one bin of the row at most)
       {
         const double rollOff[4] = {0.25, 0.50, 0.75, 0.90};
-        double off = 0.0;
-        int kro[4] = {0, 0, 0, 0};                           // the bin at which share i is reached (one bin of the row meets the test)
+        int kro[4] = {0, 0, 0, 0};
 #pragma unroll
         for (int m = 0; m < 17; ++m) {
           const int k = j + 16 * m;
-          const float mq = fresh(mv[m]);
-          double c = (k >= 1 && k <= kM) ? (double)(mq * mq) : 0.0;
-          c += shr0_d<1>(c); c += shr0_d<2>(c); c += shr0_d<4>(c); c += shr0_d<8>(c);
-          const double tot = lane_d(c, row_base4, 15);
-          c += off;
-          const double up = shr0_d<1>(c);
-          const double before = (j == 0) ? off : up;      // the prefix at bin k - 1
           if (k >= 1 && k <= kM) {
+            const double c = zd[k - 1];
+            const double before = (k == 1) ? -1.0 : zd[k - 2];      // the running sum at bin k - 1
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
               const double th = rollOff[i] * frameSum;
               if (c >= th && (k == 1 || !(before >= th))) kro[i] = k;
             }
           }
-          off += tot;
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int kk = QuadG::sum_i(kro[i], nullptr);
           if (store && j == i) rawB[26 + 2 + i] = (float)(F0 * kk);
         }
+        QuadG::sync();                                     // (the running sums have been read: the powers take their place again)
+#pragma unroll
+        for (int m = 0; m < 17; ++m) { const int k = j + 16 * m; if (k <= kM) zf[k] = mv[m] * mv[m]; }
+        QuadG::sync();
       }
       QPHASE(5);
       // harmonicity (:1484-1513): alternating peaks / valleys, distance to the previous flagged bin
@@ -420,7 +424,6 @@ __device__ __forceinline__ void compare_frame_quad_body(const LldParams &P, cons
       // consumed float chains' place, 256 doubles in the row's 544 floats, and lane 0 adds them bin after bin
       QuadG::sync();
       {
-        double *zd = reinterpret_cast<double *>(zf);
         const double F0m = fresh(F0);
 #pragma unroll
         for (int m = 0; m < 17; ++m) {

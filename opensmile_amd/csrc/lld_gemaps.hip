@@ -18,7 +18,8 @@
 //                        cContourSmoother instances with the graph's end-of-input rules -> the 25-column LLD level and the
 //                        levels the functionals read
 // Reference-order arithmetic where the result is order-sensitive (float sums of cSpecResample / cLpc, the QR iteration);
-// sums the reference keeps in double are formed as double tree sums. Parity first; bounds in DESIGN.md.
+// of the sums the reference keeps in double the one-signed ones (flux, energy) are tree sums, the band slopes' the reference's chains.
+// Parity first; bounds in DESIGN.md.
 #include <hip/hip_runtime.h>
 #include "kernel_timing.hpp"
 
@@ -81,29 +82,9 @@ __device__ __forceinline__ void gemaps_spectral_wave(const float *mg, const floa
     lg[lane] = (p <= G.spec_floor) ? G.log_spec_floor : G.log_spec_factor * glibc_logf(p);
   }
   WaveG::sync();
-  // band slopes of the log spectrum (spectral.cpp:872-992), frequency axis given: four double sums per band
-#pragma unroll
-  for (int b = 0; b < 2; ++b) {
-    const int iL = G.sl_iL[b], iR = G.sl_iR[b];
-    const double wL = G.sl_wL[b], wR = G.sl_wR[b];
-    double v[4] = {0.0, 0.0, 0.0, 0.0};                // Sf, S2f, sumA, sumB
-    const int j = iL + lane;
-    if (j <= iR) {
-      const double f = F0 * (double)j, l = (double)lg[j];
-      if (j == iL) { const double fw = f * wL; v[0] = fw; v[1] = fw * fw; v[2] = fw * l; v[3] = wL * l; }
-      else if (j == iR) { const double fw = f * wR; v[0] = fw; v[1] = fw * fw; v[2] = fw * l; v[3] = wR * l; }
-      else { v[0] = f; v[1] = f * f; v[2] = f * l; v[3] = l; }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) v[q] = WaveG::sum(v[q], nullptr);
-    if (lane == 0) {
-      const double Nind = G.sl_Nind[b];
-      const double deno = (Nind * v[1] - v[0] * v[0]);
-      double slope = 0.0;
-      if (deno != 0.0) slope = (Nind * v[2] - v[0] * v[3]) / deno;
-      dst5[b] = (float)slope;                       // oldSlopeScale = 0
-    }
-  }
+  // band slopes of the log spectrum (spectral.cpp:872-992), frequency axis given: four double sums per band, added in the
+  // reference's order (the numerator cancels on a trendless band: sequence-decided) -- lanes 0 and 1 walk one band each
+  if (lane < 2) dst5[lane] = gemaps_band_slope_seq(lg, G, lane, F0);
   // alpha ratio (:995-1037) and Hammarberg index (:1039-1089) over the bins up to 5000 Hz, flux (:1124-1254) over freqRange
   {
     double fl = 0.0;

@@ -12,6 +12,40 @@
 
 namespace smilehip {
 
+// One band slope of the log spectrum (spectral.cpp:872-992 with a frequency axis, oldSlopeScale = 0) by ONE thread: the four double
+// sums Sf, S2f, sumA, sumB as the reference's loop adds them -- the left edge bin weighted, the bins between, the right edge bin
+// weighted. The numerator Nind sumA - Sf sumB cancels where the log spectrum has no trend over the band, and then the order of
+// the additions decides the float (sequence-decided, see lld_blocks_compare.hpp; witnesses: tests/golden/order_witnesses.npz,
+// gemaps_rows). lg: the log power spectrum of bins 0 .. 63 (at most 49 bins in a band of the shipped sets), F0 = 1 / frameSizeSec.
+__device__ __forceinline__ float gemaps_band_slope_seq(const float *lg, const GemapsParams &G, int b, double F0) {
+  const int iL = G.sl_iL[b], iR = G.sl_iR[b];
+  const double wL = G.sl_wL[b], wR = G.sl_wR[b];
+  double f = F0 * (double)iL, l = (double)lg[iL];
+  double Sf = f * wL;
+  double S2f = Sf * Sf, sumA = f * wL * l, sumB = wL * l;
+  float ln = lg[iL + 1 < 64 ? iL + 1 : 63];                 // (the next bin's log value is in flight while this bin's adds run)
+  for (int ii = iL + 1; ii < iR; ++ii) {
+    l = (double)ln;
+    ln = lg[ii + 1 < 64 ? ii + 1 : 63];
+    f = F0 * (double)ii;
+    S2f += f * f;
+    Sf += f;
+    sumA += f * l;
+    sumB += l;
+  }
+  f = F0 * (double)iR; l = (double)lg[iR];
+  S2f += f * wR * f * wR;
+  Sf += f * wR;
+  sumA += f * wR * l;
+  sumB += wR * l;
+  const double Nind = G.sl_Nind[b];
+  const double deno = (Nind * S2f - Sf * Sf);
+  double slope = 0.0;
+  if (deno != 0.0) slope = (Nind * sumA - Sf * sumB) / deno;
+  return (float)slope;
+}
+
+
 namespace gq {
 constexpr int kN = 320, kH = 160, kM = 256, kK = 257, kBands = 26, kMfcc = 4, kRsB = 109, kRsI = 220;
 constexpr int kRowFloats = 2 * kQuadZPairs + 64 + 64;      // z | lmel[32] | aud[32] | lg[64]
@@ -143,30 +177,8 @@ __device__ __forceinline__ void gemaps_frame20_quad_body(const LldParams &P, con
         lg[j + 16 * m] = (p <= G.spec_floor) ? G.log_spec_floor : G.log_spec_factor * glibc_logf(p);
       }
       QuadG::sync();
-      float slope[2] = {0.0f, 0.0f};
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {                        // band slopes of the log spectrum (spectral.cpp:872-992)
-        const int iL = G.sl_iL[b], iR = G.sl_iR[b];
-        const double wL = G.sl_wL[b], wR = G.sl_wR[b];
-        double s[4] = {0.0, 0.0, 0.0, 0.0};              // Sf, S2f, sumA, sumB
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-          const int k = j + 16 * m;
-          if (k >= iL && k <= iR) {
-            const double f = F0 * (double)k, l = (double)lg[k];
-            if (k == iL) { const double fw = f * wL; s[0] += fw; s[1] += fw * fw; s[2] += fw * l; s[3] += wL * l; }
-            else if (k == iR) { const double fw = f * wR; s[0] += fw; s[1] += fw * fw; s[2] += fw * l; s[3] += wR * l; }
-            else { s[0] += f; s[1] += f * f; s[2] += f * l; s[3] += l; }
-          }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) s[q] = QuadG::sum(s[q], nullptr);
-        const double Nind = G.sl_Nind[b];
-        const double deno = (Nind * s[1] - s[0] * s[0]);
-        double sl = 0.0;
-        if (deno != 0.0) sl = (Nind * s[2] - s[0] * s[3]) / deno;
-        slope[b] = (float)sl;                              // oldSlopeScale = 0
-      }
+      // band slopes of the log spectrum (spectral.cpp:872-992): lanes 0 and 1 of the row walk one band each, the reference's chains
+      if (j < 2) { const float sl = gemaps_band_slope_seq(lg, G, j, F0); if (store) raw[1 + j] = sl; }
       // alpha ratio (:995-1037) and Hammarberg index (:1039-1089) over the bins up to 5000 Hz
       float m02 = 0.0f, m25 = 0.0f;
 #pragma unroll
@@ -200,8 +212,6 @@ __device__ __forceinline__ void gemaps_frame20_quad_body(const LldParams &P, con
           if (m02 > G.spec_floor) h = (float)(10.0 * (double)glibc_logf(m02 / m25) / log(10.0));
           else h = (float)(10.0 * (double)(glibc_logf(G.spec_floor) - glibc_logf(m25)) / log(10.0));
         }
-        raw[1] = slope[0];
-        raw[2] = slope[1];
         raw[3] = a;
         raw[4] = h;
         const int nBins = G.rng_hi - G.rng_lo + 1;
