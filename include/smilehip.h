@@ -465,6 +465,46 @@ int smilehip_funcspec_matrix_windows(smilehip_context *ctx, const smilehip_func_
  * ratio limits); Moments stddev skewness kurtosis; period 0.01 s. 12 values per column. */
 int smilehip_funcspec_is09(smilehip_func_spec *spec);
 
+/* ---- functionals over listed segments: cWinToVecProcessor frameMode = list, frameCenterSpecial = left ----
+ * One vector per SEGMENT of a list (src/core/winToVecProcessor.cpp:123-296 reads the list, :530-545 turns seconds into rows,
+ * :940-962 hands out the segments): a segment is the rows [start, end] INCLUSIVE of the level, the vectors come in list order
+ * (segments may overlap, nest and repeat), and each goes through cFunctionals::doProcess like a full-mode contour of its own
+ * length. Not built: a segment to the end of the input (E), frameCenterSpecial other than left.
+ *
+ * The list (parseFrameList / stringToTimeval, winToVecProcessor.cpp:123-296; the conversion of :530-545), host only, no device
+ * needed. Tokens are separated by commas, blanks around a value are dropped. "a-b" is an interval, "n" a length (the segments
+ * of a list of lengths are contiguous from row 0: [last, last + n - 1] in rows, floor / ceil of last and last + n in seconds);
+ * values with the suffix s / S are seconds, others rows taken as given. Seconds become rows as start = floor(sec / period),
+ * end = ceil(sec / period) in double, period 0 taken as 1. As the reference: an interval of rows with end - start < 3 gets
+ * end = start + 3, one of seconds with end - start < 0.01 gets end = start + 0.01, a length below 3 rows becomes 3.
+ * first_rows[i] / n_rows[i] (cap entries) receive start and end - start + 1 of segment i, *n_segments the count; cap = 0 only
+ * counts. SMILEHIP_ERR_INVALID, naming the token: E; seconds and rows in one list; intervals and lengths in one list; a
+ * length in seconds below 0.01 (the reference logs an error and sets no minimum); an empty token or value; a value strtod does
+ * not consume whole; more segments than cap. */
+int smilehip_func_list_parse(const char *frame_list, double period, int64_t *first_rows, int64_t *n_rows, int32_t cap,
+                             int32_t *n_segments);
+/* The segments of a list a level of `rows` rows yields (winToVecProcessor.cpp:951-962: the list position only advances when the
+ * segment could be read): *n_emitted = the index of the first segment whose last row is >= rows -- it and all after it are
+ * never emitted -- or n if every segment fits. */
+int smilehip_func_list_fit(const int64_t *first_rows, const int64_t *n_rows, int32_t n, int64_t rows, int32_t *n_emitted);
+/* smilehip_funcspec_matrix over n_seg segments of ONE matrix (rows x cols, leading dimension ld_lld;
+ * winToVecProcessor.cpp:940-962 + functionals.cpp:320-389): segment s is rows [h_first[s], h_first[s] + h_rows[s]) (host
+ * arrays), row s of d_func (leading dimension ld_func) receives its cols * count(spec) values, element-major. Every segment has
+ * its own scratch; the engine runs them longest first, in chunks of whole segments whose scratch is bounded as for the windows
+ * (512 MiB; SMILEHIP_FUNC_WINDOWS_SCRATCH_MB), on `stream`. Nothing is dropped silently: SMILEHIP_ERR_INVALID before anything is
+ * launched or written, naming utterance (0) and segment, for a segment of fewer than 1 row, a negative first row, a last row
+ * beyond the matrix, and a Modulation spec with a segment of fewer than 34 rows. n_seg = 0: SMILEHIP_OK, nothing written. */
+int smilehip_funcspec_matrix_segments(smilehip_context *ctx, const smilehip_func_spec *spec, const float *d_lld, int64_t ld_lld,
+                                      int64_t rows, int32_t cols, int32_t n_seg, const int64_t *h_first, const int64_t *h_rows,
+                                      float *d_func, int64_t ld_func, void *stream);
+/* The same over a batch (winToVecProcessor.cpp:940-962): utterance u owns segments [h_seg_off[u], h_seg_off[u + 1]) of
+ * h_first / h_rows, rows relative to the utterance's first row, all inside its first rows_u - rows_cut rows; output row s is
+ * segment s. A non-monotone h_seg_off is refused like the segments above. */
+int smilehip_batch_funcspec_segments(smilehip_plan *plan, smilehip_batch *batch, const smilehip_func_spec *spec,
+                                     const float *d_lld, int64_t ld_lld, int32_t col_first, int32_t n_cols, int32_t rows_cut,
+                                     const int64_t *h_seg_off /* [n_utt + 1] */, const int64_t *h_first, const int64_t *h_rows,
+                                     float *d_func, int64_t ld_func, void *stream);
+
 /* The whole functionals level of config/compare16/ComParE_2016.conf: 6373 values per utterance in the reference's own
  * order ([functionals] concatenates is13_functionalsA, B, Nz, F0, LLD, Delta; names: smilehip_host func_names_compare16).
  * d_lld: the 130-column matrix smilehip_lld_run produced for THIS batch on a smilehip_config_compare16 plan (the run also

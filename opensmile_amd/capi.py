@@ -221,6 +221,10 @@ SYMBOLS = {
     "smilehip_batch_funcspec_windows": (C.c_int, [_vp, _vp, _vp, _vp, _i64, C.c_int32, C.c_int32, C.c_int32, _i64, _i64, _vp, _i64, _vp]),
     "smilehip_funcspec_matrix_windows": (C.c_int, [_vp, _vp, _vp, _i64, _i64, C.c_int32, _i64, _i64, _vp, _i64, _vp]),
     "smilehip_funcspec_is09": (C.c_int, [_vp]),
+    "smilehip_func_list_parse": (C.c_int, [C.c_char_p, _dbl, _vp, _vp, C.c_int32, _vp]),
+    "smilehip_func_list_fit": (C.c_int, [_vp, _vp, C.c_int32, _i64, _vp]),
+    "smilehip_funcspec_matrix_segments": (C.c_int, [_vp, _vp, _vp, _i64, _i64, C.c_int32, C.c_int32, _vp, _vp, _vp, _i64, _vp]),
+    "smilehip_batch_funcspec_segments": (C.c_int, [_vp, _vp, _vp, _vp, _i64, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "smilehip_lld_run": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp]),
     "smilehip_lld_run_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp]),
     "smilehip_lld_run_host": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
@@ -612,6 +616,75 @@ def funcspec_matrix_windows_host(ctx, spec, x, size_rows, step_rows, ld_lld=None
     return np.ascontiguousarray(out[:, :cols * per]), out
 
 
+def func_list_parse(frame_list, period):
+    """(first_rows, n_rows) of a frameMode = list string over a level of `period` seconds per row (host only)."""
+    L = load()
+    text = frame_list.encode() if isinstance(frame_list, str) else bytes(frame_list)
+    n = C.c_int32()
+    _check(L.smilehip_func_list_parse(text, period, None, None, 0, C.byref(n)))
+    first, rows = np.zeros(n.value, np.int64), np.zeros(n.value, np.int64)
+    if n.value:
+        _check(L.smilehip_func_list_parse(text, period, first.ctypes.data, rows.ctypes.data, n.value, C.byref(n)))
+    return first, rows
+
+
+def func_list_fit(first_rows, n_rows, rows):
+    """How many segments of the list a level of `rows` rows yields: all before the first one that does not fit."""
+    first = np.ascontiguousarray(first_rows, dtype=np.int64)
+    nr = np.ascontiguousarray(n_rows, dtype=np.int64)
+    assert first.shape == nr.shape and first.ndim == 1
+    n = C.c_int32()
+    _check(load().smilehip_func_list_fit(first.ctypes.data, nr.ctypes.data, len(first), rows, C.byref(n)))
+    return n.value
+
+
+def funcspec_matrix_segments_host(ctx, spec, x, first_rows, n_rows, ld_lld=None, ld_func=None, fill=np.nan):
+    """rows x cols host matrix -> n_seg x (cols * count(spec)) through smilehip_funcspec_matrix_segments. With ld_lld / ld_func
+    the device matrices get those strides and NaN pads; the padded output comes back as a second value. The output buffer holds
+    `fill` beforehand. ctx may be None (what the entry point refuses before it looks for a device)."""
+    L = load()
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    rows, cols = x.shape
+    per = funcspec_count(spec)
+    first = np.ascontiguousarray(first_rows, dtype=np.int64)
+    nr = np.ascontiguousarray(n_rows, dtype=np.int64)
+    assert first.shape == nr.shape and first.ndim == 1
+    n = len(first)
+    ldx = cols if ld_lld is None else ld_lld
+    ldf = cols * per if ld_func is None else ld_func
+    if ctx is None:
+        _check(L.smilehip_funcspec_matrix_segments(None, C.byref(spec), None, ldx, rows, cols, n, first.ctypes.data, nr.ctypes.data, None, ldf, None))
+        raise SmileHipError("smilehip_funcspec_matrix_segments accepted a null context")
+    xin = np.full((rows, ldx), np.nan, np.float32)
+    xin[:, :cols] = x
+    out = np.full((n, ldf), fill, np.float32)
+    d_x, d_out = _vp(), _vp()
+    _check(L.smilehip_alloc(ctx._h, max(xin.nbytes, 4), C.byref(d_x)))
+    _check(L.smilehip_alloc(ctx._h, max(out.nbytes, 4), C.byref(d_out)))
+    try:
+        if xin.nbytes:
+            _check(L.smilehip_copy_to_device(ctx._h, d_x, xin.ctypes.data, xin.nbytes, None))
+        if out.nbytes:
+            _check(L.smilehip_copy_to_device(ctx._h, d_out, out.ctypes.data, out.nbytes, None))
+        try:
+            _check(L.smilehip_funcspec_matrix_segments(ctx._h, C.byref(spec), d_x, ldx, rows, cols, n, first.ctypes.data, nr.ctypes.data, d_out, ldf, None))
+        except SmileHipError as e:                      # a refusal: the buffer as the call left it travels with the error
+            _check(L.smilehip_stream_synchronize(ctx._h, None))
+            if out.nbytes:
+                _check(L.smilehip_copy_to_host(ctx._h, out.ctypes.data, d_out, out.nbytes, None))
+            e.output = out
+            raise
+        _check(L.smilehip_stream_synchronize(ctx._h, None))
+        if out.nbytes:
+            _check(L.smilehip_copy_to_host(ctx._h, out.ctypes.data, d_out, out.nbytes, None))
+    finally:
+        L.smilehip_free(ctx._h, d_x)
+        L.smilehip_free(ctx._h, d_out)
+    if ld_lld is None and ld_func is None:
+        return out
+    return np.ascontiguousarray(out[:, :cols * per]), out
+
+
 def is09_lld_config():
     c = LldConfig()
     load().smilehip_config_is09_lld(C.byref(c))
@@ -974,6 +1047,47 @@ class Batch:
             L.smilehip_free(ctx, d_lld)
             L.smilehip_free(ctx, d_out)
         return out, win_off
+
+    def funcspec_segments(self, lld, spec, col_first, n_cols, rows_cut, seg_off, first_rows, n_rows, ld_func=None, fill=np.nan):
+        """lld: the matrix run_host returned -> seg_off[n_utt] x (n_cols * count(spec)) through smilehip_batch_funcspec_segments:
+        row s is segment s; utterance u owns segments [seg_off[u], seg_off[u + 1]), rows relative to the utterance. The device
+        output holds `fill` beforehand (stride ld_func if given) and comes back whole; a refusal carries it as `.output`."""
+        L = load()
+        per = funcspec_count(spec)
+        lld = np.ascontiguousarray(lld, dtype=np.float32)
+        ld = lld.shape[1]
+        assert lld.shape[0] == self.total_rows
+        seg_off = np.ascontiguousarray(seg_off, dtype=np.int64)
+        first = np.ascontiguousarray(first_rows, dtype=np.int64)
+        nr = np.ascontiguousarray(n_rows, dtype=np.int64)
+        assert len(seg_off) == self.n_utt + 1 and first.shape == nr.shape and first.ndim == 1
+        ldf = n_cols * per if ld_func is None else ld_func
+        out = np.full((len(first), ldf), fill, np.float32)
+        ctx = self.plan.ctx._h
+        d_lld, d_out = _vp(), _vp()
+        _check(L.smilehip_alloc(ctx, max(lld.nbytes, 4), C.byref(d_lld)))
+        _check(L.smilehip_alloc(ctx, max(out.nbytes, 4), C.byref(d_out)))
+        try:
+            if lld.nbytes:
+                _check(L.smilehip_copy_to_device(ctx, d_lld, lld.ctypes.data, lld.nbytes, None))
+            if out.nbytes:
+                _check(L.smilehip_copy_to_device(ctx, d_out, out.ctypes.data, out.nbytes, None))
+            try:
+                _check(L.smilehip_batch_funcspec_segments(self.plan._h, self._h, C.byref(spec), d_lld, ld, col_first, n_cols, rows_cut,
+                                                          seg_off.ctypes.data, first.ctypes.data, nr.ctypes.data, d_out, ldf, None))
+            except SmileHipError as e:
+                _check(L.smilehip_stream_synchronize(ctx, None))
+                if out.nbytes:
+                    _check(L.smilehip_copy_to_host(ctx, out.ctypes.data, d_out, out.nbytes, None))
+                e.output = out
+                raise
+            _check(L.smilehip_stream_synchronize(ctx, None))
+            if out.nbytes:
+                _check(L.smilehip_copy_to_host(ctx, out.ctypes.data, d_out, out.nbytes, None))
+        finally:
+            L.smilehip_free(ctx, d_lld)
+            L.smilehip_free(ctx, d_out)
+        return out
 
     def close(self):
         if self._h:

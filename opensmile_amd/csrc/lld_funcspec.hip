@@ -68,6 +68,7 @@ struct Where {                     // what a thread works on
   int64_t rows;                    // rows before nonZeroFuncts
   bool on;
   int64_t xrow0;                   // item form: the window's first row in the input matrix
+  int orow;                        // segment form: the output row (the segment's position in the caller's list)
 };
 
 __device__ __forceinline__ void utt_rows(const FsParams &P, Where &w) {
@@ -91,7 +92,11 @@ __device__ __forceinline__ void utt_rows(const FsParams &P, Where &w) {
 // Item form (FsItemParams): item i of the launch is window it_first + i of the call. Everything the kernels index by utterance
 // -- stats slot, output row, scratch rows -- is indexed by the ITEM, so overlapping windows never share scratch; only the input
 // rows are found through the window's utterance (the last one whose window count prefix is <= the window's index).
-template <bool ITEM> using FsP = typename std::conditional<ITEM, FsItemParams, FsParams>::type;   // a kernel's parameter block
+// Segment form (FsSegParams): item i of the launch is the contour its descriptor names -- first input row, rows, first scratch
+// row, output row. Stats slot and scratch are the item's own as in the item form; only the output row is the descriptor's.
+constexpr int kFull = 0, kItem = 1, kSeg = 2;      // a kernel's form: utterances, fixed windows, listed segments
+template <int FORM>
+using FsP = typename std::conditional<FORM == kSeg, FsSegParams, typename std::conditional<FORM == kItem, FsItemParams, FsParams>::type>::type;   // a kernel's parameter block
 
 __device__ __forceinline__ void item_rows(const FsItemParams &P, Where &w, int item) {
   w.u = item;
@@ -110,22 +115,54 @@ __device__ __forceinline__ void item_rows(const FsItemParams &P, Where &w, int i
   w.xrow0 = P.row_off[lo] + (g - P.it_win_off[lo]) * P.it_step;
 }
 
+// The descriptor is loaded whole and by every lane, whatever the lane does with it afterwards: the caller clamps `item` into the
+// launch instead of putting the load under a lane condition, which would put the wait for it there as well.
+__device__ __forceinline__ void seg_rows(const FsSegParams &P, Where &w, int item) {
+  const FsSeg d = P.seg[item];
+  w.u = item;
+  w.srow0 = d.srow0;
+  w.rows = d.rows;
+  w.xrow0 = d.xrow0;
+  w.orow = d.orow;
+}
+
+template <int FORM>
+__device__ __forceinline__ void form_rows(const FsP<FORM> &P, Where &w, int item) {
+  if constexpr (FORM == kSeg) seg_rows(P, w, item);
+  else if constexpr (FORM == kItem) item_rows(P, w, item);
+  else utt_rows(P, w);
+}
+
+template <int FORM>
+__device__ __forceinline__ int out_row(const Where &w) {
+  if constexpr (FORM == kSeg) return w.orow;
+  else return w.u;
+}
+
 // one (item, column) per workgroup / wave: fs_percentiles, fs_percentiles_wave, fs_modulation
-template <bool ITEM, typename Index>                       // (Index: the caller's own index type -- its division is the one it had)
-__device__ __forceinline__ Where locate_one(const FsP<ITEM> &P, Index idx) {
+template <int FORM, typename Index>                       // (Index: the caller's own index type -- its division is the one it had)
+__device__ __forceinline__ Where locate_one(const FsP<FORM> &P, Index idx) {
   Where w;
   w.u = idx / P.n_cols;
   w.c = idx % P.n_cols;
   w.on = true;
-  if constexpr (ITEM) item_rows(P, w, w.u);
-  else utt_rows(P, w);
+  form_rows<FORM>(P, w, w.u);
   return w;
 }
 
-template <bool ITEM>
-__device__ __forceinline__ Where locate(const FsP<ITEM> &P) {
+template <int FORM>
+__device__ __forceinline__ Where locate(const FsP<FORM> &P) {
   Where w;
-  if constexpr (ITEM) if (P.it_pack > 1) {
+  if constexpr (FORM == kSeg) if (P.it_pack > 1) {
+    // lane packing as below, over consecutive items of the launch's own (length-sorted) order
+    const int k = threadIdx.x / P.n_cols;
+    const int item = blockIdx.x * P.it_pack + k;
+    w.c = threadIdx.x - k * P.n_cols;
+    w.on = k < P.it_pack && item < P.it_n;
+    seg_rows(P, w, min(item, P.it_n - 1));
+    return w;
+  }
+  if constexpr (FORM == kItem) if (P.it_pack > 1) {
     // lane packing: n_cols <= 32 leaves half a wave or more idle, and consecutive windows fill it -- lane l serves column
     // l % n_cols of the wave's window l / n_cols; each window's step is still one contiguous row segment
     const int k = threadIdx.x / P.n_cols;
@@ -139,15 +176,14 @@ __device__ __forceinline__ Where locate(const FsP<ITEM> &P) {
   w.u = blockIdx.x / groups;
   w.c = (blockIdx.x % groups) * kColsPerBlock + threadIdx.x;
   w.on = w.c < P.n_cols;
-  if constexpr (ITEM) item_rows(P, w, w.u);
-  else utt_rows(P, w);
+  form_rows<FORM>(P, w, w.u);
   return w;
 }
 
-template <bool ITEM>
+template <int FORM>
 __device__ __forceinline__ Col raw_col(const FsParams &P, const Where &w) {
   Col x;
-  if (ITEM) {
+  if (FORM != kFull) {
     x.p = P.x + w.xrow0 * P.ld_x + P.col_first + w.c;
     x.ld = P.ld_x;
     x.N = x.n_main = w.rows;
@@ -164,9 +200,9 @@ __device__ __forceinline__ Col raw_col(const FsParams &P, const Where &w) {
 }
 
 // the column the families see: the compacted copy if nonZeroFuncts, else the input itself
-template <bool ITEM>
+template <int FORM>
 __device__ __forceinline__ Col data_col(const FsParams &P, const Where &w) {
-  if (!P.spec.non_zero_functs) return raw_col<ITEM>(P, w);
+  if (!P.spec.non_zero_functs) return raw_col<FORM>(P, w);
   Col x;
   x.p = P.nz + w.srow0 * P.n_cols + w.c;
   x.ld = P.n_cols;
@@ -195,11 +231,11 @@ __device__ float fs_ratio_limit(float x, float limit1, float excess) {
 }  // namespace
 
 // ------------------------------------------------------------------ stats
-template <bool ITEM>
-__global__ void __launch_bounds__(kColsPerBlock) fs_stats(FsP<ITEM> P) {
-  const Where w = locate<ITEM>(P);
+template <int FORM>
+__global__ void __launch_bounds__(kColsPerBlock) fs_stats(FsP<FORM> P) {
+  const Where w = locate<FORM>(P);
   if (!w.on) return;
-  const Col r = raw_col<ITEM>(P, w);
+  const Col r = raw_col<FORM>(P, w);
   const int64_t si = (int64_t)w.u * P.n_cols + w.c;
   int64_t NN = r.N;
   if (P.spec.non_zero_functs) {
@@ -213,11 +249,11 @@ __global__ void __launch_bounds__(kColsPerBlock) fs_stats(FsP<ITEM> P) {
   P.st_n[si] = (int32_t)NN;
   if (NN <= 0) {
     P.st_min[si] = P.st_max[si] = P.st_mean[si] = 0.0f;
-    float *o = P.out + (int64_t)w.u * P.ld_out + (int64_t)w.c * P.per;      // every family yields nothing: zeros
+    float *o = P.out + (int64_t)out_row<FORM>(w) * P.ld_out + (int64_t)w.c * P.per;      // every family yields nothing: zeros
     for (int i = 0; i < P.per; ++i) o[i] = 0.0f;
     return;
   }
-  const Col x = data_col<ITEM>(P, w);
+  const Col x = data_col<FORM>(P, w);
   float mn = x[0], mx = mn;
   double mean = mn;
   for_rows(x, 1, NN, [&](int64_t, float v) {
@@ -1342,15 +1378,15 @@ __device__ int f_peaks2(const smilehip_func_spec &s, const Col &in, float min, f
 
 }  // namespace
 
-template <int FAM, bool ITEM>
-__global__ void __launch_bounds__(kColsPerBlock) fs_family(FsP<ITEM> P, int out_off, int want) {
-  const Where w = locate<ITEM>(P);
+template <int FAM, int FORM>
+__global__ void __launch_bounds__(kColsPerBlock) fs_family(FsP<FORM> P, int out_off, int want) {
+  const Where w = locate<FORM>(P);
   if (!w.on) return;
   const int64_t si = (int64_t)w.u * P.n_cols + w.c;
   if (P.st_n[si] <= 0) return;                          // zero-filled by fs_stats
-  const Col x = data_col<ITEM>(P, w);
+  const Col x = data_col<FORM>(P, w);
   const float mn = P.st_min[si], mx = P.st_max[si], mean = P.st_mean[si];
-  float *o = P.out + (int64_t)w.u * P.ld_out + (int64_t)w.c * P.per + out_off;
+  float *o = P.out + (int64_t)out_row<FORM>(w) * P.ld_out + (int64_t)w.c * P.per + out_off;
   int got = 0;
   if (FAM == SMILEHIP_FAM_EXTREMES) got = f_extremes(P.spec, x, mn, mx, mean, o);
   if (FAM == SMILEHIP_FAM_MEANS) got = f_means(P.spec, x, mean, o);
@@ -1409,9 +1445,10 @@ __device__ void bitonic_sort(float *a, int n2) {       // n2 = power of two, who
 
 }  // namespace
 
+template <int FORM>
 __device__ void pctl_readout(const FsParams &P, const Where &w, const float *a, int64_t N, int out_off) {
   const smilehip_func_spec &s = P.spec;
-  float *out = P.out + (int64_t)w.u * P.ld_out + (int64_t)w.c * P.per + out_off;
+  float *out = P.out + (int64_t)out_row<FORM>(w) * P.ld_out + (int64_t)w.c * P.per + out_off;
   float q1, q2, q3;
   if (s.pct_interp) { q1 = interp_pctl(0.25, a, N); q2 = interp_pctl(0.50, a, N); q3 = interp_pctl(0.75, a, N); }
   else { q1 = a[pctl_idx(0.25, N)]; q2 = a[pctl_idx(0.50, N)]; q3 = a[pctl_idx(0.75, N)]; }
@@ -1439,14 +1476,14 @@ __device__ void pctl_readout(const FsParams &P, const Where &w, const float *a, 
   }
 }
 
-template <bool ITEM>
-__global__ void __launch_bounds__(kSortThreads) fs_percentiles(FsP<ITEM> P, int out_off) {
+template <int FORM>
+__global__ void __launch_bounds__(kSortThreads) fs_percentiles(FsP<FORM> P, int out_off) {
   __shared__ float lds[kSortLds];
-  const Where w = locate_one<ITEM>(P, blockIdx.x);
+  const Where w = locate_one<FORM>(P, blockIdx.x);
   const int64_t si = (int64_t)w.u * P.n_cols + w.c;
   const int64_t N = P.st_n[si];
   if (N <= 0 || N <= kWaveSortMaxDecl) return;           // (up to 1024 rows: fs_percentiles_wave)
-  const Col x = data_col<ITEM>(P, w);
+  const Col x = data_col<FORM>(P, w);
   int n2 = 1;
   while (n2 < N) n2 <<= 1;
   // global scratch beyond the LDS capacity: the utterance's region holds 2 * (rows + 1) * n_cols floats; the column slots
@@ -1459,7 +1496,7 @@ __global__ void __launch_bounds__(kSortThreads) fs_percentiles(FsP<ITEM> P, int 
   __syncthreads();
   bitonic_sort(a, n2);
   if (threadIdx.x != 0) return;
-  pctl_readout(P, w, a, N, out_off);
+  pctl_readout<FORM>(P, w, a, N, out_off);
 }
 
 // ---- one WAVE per (utterance, column) for N <= 1024 (a 10 s contour): the SAME bitonic network as bitonic_sort above -- the
@@ -1530,17 +1567,17 @@ __device__ __forceinline__ void wave_bitonic_sort(const Col &x, int64_t N, int l
 }
 
 constexpr int kWaveSortMax = 1024;
-template <bool ITEM>
-__global__ void __launch_bounds__(256) fs_percentiles_wave(FsP<ITEM> P, int out_off, int n_items) {
+template <int FORM>
+__global__ void __launch_bounds__(256) fs_percentiles_wave(FsP<FORM> P, int out_off, int n_items) {
   __shared__ float lds_all[4 * kWaveSortMax];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int item = blockIdx.x * 4 + wave;
   if (item >= n_items) return;
-  const Where w = locate_one<ITEM>(P, item);
+  const Where w = locate_one<FORM>(P, item);
   const int64_t N = P.st_n[(int64_t)w.u * P.n_cols + w.c];
   if (N <= 0 || N > kWaveSortMax) return;                // longer contours: fs_percentiles
-  const Col x = data_col<ITEM>(P, w);
+  const Col x = data_col<FORM>(P, w);
   float *a = lds_all + wave * kWaveSortMax;
   int lg = 1;
   while ((1 << lg) < N) ++lg;
@@ -1558,7 +1595,7 @@ __global__ void __launch_bounds__(256) fs_percentiles_wave(FsP<ITEM> P, int out_
   }
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
-  if (lane == 0) pctl_readout(P, w, a, N, out_off);
+  if (lane == 0) pctl_readout<FORM>(P, w, a, N, out_off);
 }
 
 // ------------------------------------------------------------------ launch
@@ -1582,18 +1619,18 @@ struct ModG {
 };
 }  // namespace
 
-template <bool ITEM>
-__global__ void __launch_bounds__(64) fs_modulation(FsP<ITEM> P, int out_off) {
+template <int FORM>
+__global__ void __launch_bounds__(64) fs_modulation(FsP<FORM> P, int out_off) {
   __shared__ float2 z[512];
   __shared__ double yv[516], y2[516], uu[516];
   __shared__ float acc[128];
-  const Where w = locate_one<ITEM>(P, blockIdx.x);
+  const Where w = locate_one<FORM>(P, blockIdx.x);
   const smilehip_func_spec &s = P.spec;
   const int64_t Nin = P.st_n[(int64_t)w.u * P.n_cols + w.c];
   if (Nin <= 0) return;
-  const Col x = data_col<ITEM>(P, w);
+  const Col x = data_col<FORM>(P, w);
   const int lane = threadIdx.x & 63, nb = s.mod_n_bins, W = s.mod_win_frames, step = s.mod_step_frames;
-  float *out = P.out + (int64_t)w.u * P.ld_out + (int64_t)w.c * P.per + out_off;
+  float *out = P.out + (int64_t)out_row<FORM>(w) * P.ld_out + (int64_t)w.c * P.per + out_off;
   float mean = 0.0f;
   if (s.mod_remove_nz_mean) {                            // :512-541 -- a FLOAT_DMEM chain; every lane walks it (uniform loads)
     int64_t n_mean = 0;
@@ -1655,22 +1692,22 @@ __global__ void __launch_bounds__(64) fs_modulation(FsP<ITEM> P, int out_off) {
 }
 
 namespace {
-// n = utterances (full mode) or items of this launch (item form)
-template <bool ITEM>
-hipError_t launch_fs(const FsP<ITEM> &P, int n, const int *fam_off, const int *fam_want, hipStream_t s) {
+// n = utterances (full mode) or items of this launch (item and segment forms)
+template <int FORM>
+hipError_t launch_fs(const FsP<FORM> &P, int n, const int *fam_off, const int *fam_want, hipStream_t s) {
   if (n <= 0 || P.n_cols <= 0) return hipSuccess;
   const int groups = (P.n_cols + kColsPerBlock - 1) / kColsPerBlock;
   unsigned blocks = (unsigned)(n * groups);
-  if constexpr (ITEM) if (P.it_pack > 1) blocks = (unsigned)((n + P.it_pack - 1) / P.it_pack);
+  if constexpr (FORM != kFull) if (P.it_pack > 1) blocks = (unsigned)((n + P.it_pack - 1) / P.it_pack);
   const dim3 grid(blocks), block(kColsPerBlock);
   // (the timing report keeps the kernels' names; the item form's carry "/item")
 #define FS_LAUNCH(name, kernel, grid, block, ...)                                \
   do {                                                                           \
-    smilehip::KernelMark kernel_mark_(ITEM ? name "/item" : name, s);            \
+    smilehip::KernelMark kernel_mark_(FORM == kSeg ? name "/seg" : (FORM == kItem ? name "/item" : name), s);            \
     hipLaunchKernelGGL(kernel, grid, block, 0, s, __VA_ARGS__);                  \
   } while (0)
-  FS_LAUNCH("fs_stats", fs_stats<ITEM>, grid, block, P);
-#define FS_FAMILY_CASE(F) case F: FS_LAUNCH("fs_family<" #F ">", (fs_family<F, ITEM>), grid, block, P, off, want); break;
+  FS_LAUNCH("fs_stats", fs_stats<FORM>, grid, block, P);
+#define FS_FAMILY_CASE(F) case F: FS_LAUNCH("fs_family<" #F ">", (fs_family<F, FORM>), grid, block, P, off, want); break;
   for (int i = 0; i < P.spec.n_fam; ++i) {
     const int off = fam_off[i], want = fam_want[i];
     switch (P.spec.fam[i]) {
@@ -1688,12 +1725,12 @@ hipError_t launch_fs(const FsP<ITEM> &P, int n, const int *fam_off, const int *f
       FS_FAMILY_CASE(SMILEHIP_FAM_DCT)
       FS_FAMILY_CASE(SMILEHIP_FAM_SAMPLES)
       case SMILEHIP_FAM_MODULATION:
-        FS_LAUNCH("fs_modulation", fs_modulation<ITEM>, dim3((unsigned)(n * P.n_cols)), dim3(64), P, off);
+        FS_LAUNCH("fs_modulation", fs_modulation<FORM>, dim3((unsigned)(n * P.n_cols)), dim3(64), P, off);
         break;
       case SMILEHIP_FAM_PERCENTILES:
-        FS_LAUNCH("fs_percentiles_wave", fs_percentiles_wave<ITEM>, dim3((unsigned)((n * P.n_cols + 3) / 4)), dim3(256), P, off, n * P.n_cols);
+        FS_LAUNCH("fs_percentiles_wave", fs_percentiles_wave<FORM>, dim3((unsigned)((n * P.n_cols + 3) / 4)), dim3(256), P, off, n * P.n_cols);
         if (P.max_rows > kWaveSortMax)                   // some contour may be longer than one wave sorts
-          FS_LAUNCH("fs_percentiles", fs_percentiles<ITEM>, dim3((unsigned)(n * P.n_cols)), dim3(kSortThreads), P, off);
+          FS_LAUNCH("fs_percentiles", fs_percentiles<FORM>, dim3((unsigned)(n * P.n_cols)), dim3(kSortThreads), P, off);
         break;
       default: return hipErrorInvalidValue;
     }
@@ -1705,12 +1742,17 @@ hipError_t launch_fs(const FsP<ITEM> &P, int n, const int *fam_off, const int *f
 }  // namespace
 
 hipError_t launch_funcspec(const FsParams &P, int n_utt, const int *fam_off, const int *fam_want, hipStream_t s) {
-  return launch_fs<false>(P, n_utt, fam_off, fam_want, s);
+  return launch_fs<kFull>(P, n_utt, fam_off, fam_want, s);
 }
 
 // the item form: P.it_n windows (FsItemParams), each a contour of it_size rows with its own scratch and output row
 hipError_t launch_funcspec_items(const FsItemParams &P, const int *fam_off, const int *fam_want, hipStream_t s) {
-  return launch_fs<true>(P, P.it_n, fam_off, fam_want, s);
+  return launch_fs<kItem>(P, P.it_n, fam_off, fam_want, s);
+}
+
+// the segment form: P.it_n contours (FsSegParams), each the rows its descriptor names, with its own scratch and stats slot
+hipError_t launch_funcspec_segments(const FsSegParams &P, const int *fam_off, const int *fam_want, hipStream_t s) {
+  return launch_fs<kSeg>(P, P.it_n, fam_off, fam_want, s);
 }
 
 }  // namespace smilehip

@@ -86,6 +86,7 @@ hipError_t launch_pitch_contour_step(const double *d_voicing, const int32_t *d_m
                                      float *d_out4, hipStream_t s);
 hipError_t launch_funcspec(const FsParams &P, int n_utt, const int *fam_off, const int *fam_want, hipStream_t s);
 hipError_t launch_funcspec_items(const FsItemParams &P, const int *fam_off, const int *fam_want, hipStream_t s);   // the item form: fixed windows
+hipError_t launch_funcspec_segments(const FsSegParams &P, const int *fam_off, const int *fam_want, hipStream_t s);   // the segment form: listed segments
 hipError_t launch_gemaps_frames(const LldParams &P, const GemapsParams &G, int n_runs, hipStream_t s);
 hipError_t launch_gemaps_harm(const LldParams &P, const F0Params &Q, const GemapsParams &G, int max_blocks, hipStream_t s);
 hipError_t launch_gemaps_tail(const int64_t *d_frame_off20, const int64_t *d_row_off, int n_utt, const GemapsParams &G, float *d_out,

@@ -293,6 +293,23 @@ struct FsItemParams : FsParams {
   int32_t it_pack;           // windows per wave: floor(64 / n_cols) where n_cols <= 32, else 1
 };
 
+// The segment form (listed segments, cWinToVecProcessor frameMode = list; launch_funcspec_segments): one item = one contour of
+// its own first row and length. Item i of the launch owns stats slot i and the scratch rows its descriptor names; its output row
+// is the descriptor's too, so the launch order is the engine's choice. Its own parameter type again: FsParams and FsItemParams
+// stay what they are.
+struct FsSeg {               // device-resident descriptor, 32 bytes
+  int64_t xrow0;             // first input row in the matrix (absolute: utterance offset + start)
+  int64_t rows;              // rows of the contour
+  int64_t srow0;             // first scratch row: exclusive prefix sum of `rows` over the launch's items
+  int32_t orow;              // output row: the segment's position in the caller's list
+  int32_t pad_;
+};
+struct FsSegParams : FsParams {
+  const FsSeg *seg;          // [it_n] descriptors of this launch
+  int32_t it_n;              // items in this launch
+  int32_t it_pack;           // items per wave: floor(64 / n_cols) where n_cols <= 32, else 1
+};
+
 // R13: chain of window processors (cDeltaRegression / cContourSmoother) over the
 // rows of each utterance. Level 0 = the input block x (T rows, D columns);
 // stage s (kind 0 = delta regression with deltawin W, 1 = simple moving average

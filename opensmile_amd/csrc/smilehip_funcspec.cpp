@@ -883,3 +883,278 @@ extern "C" int smilehip_funcspec_is09(smilehip_func_spec *s) {
   if (!s) return fail(SMILEHIP_ERR_INVALID, "smilehip_funcspec_is09: null argument");
   return smilehip_funcspec_from_mask(smilehip_functionals_is09_mask(), 0.01, s);
 }
+
+// ---- functionals over listed segments (cWinToVecProcessor frameMode = list, frameCenterSpecial = left)
+// src/core/winToVecProcessor.cpp:123-296 (the list's tokens), :530-545 (seconds to rows), :940-962 (the segments a level yields:
+// rows [start, end] INCLUSIVE, in list order; one that does not fit is never emitted and blocks all after it). Each segment
+// goes through cFunctionals::doProcess like a full-mode contour of its own length.
+namespace {
+// stringToTimeval (:123-161): blanks trimmed at both ends, a trailing s / S marks seconds. < 0 + message for what is refused.
+int list_value(const std::string &tok_in, const std::string &whole, double *v, int *is_sec) {
+  std::string t = tok_in;
+  while (!t.empty() && t.back() == ' ') t.pop_back();
+  size_t b = 0;
+  while (b < t.size() && t[b] == ' ') ++b;
+  t.erase(0, b);
+  if (t.empty()) return fail(SMILEHIP_ERR_INVALID, "frameList: empty value in '%s'", whole.c_str());
+  if (t[0] == 'E')
+    return fail(SMILEHIP_ERR_INVALID, "frameList: '%s': a segment to the end of the input (E) is not supported (the reference emits nothing for it)",
+                whole.c_str());
+  int sec = 0;
+  if (t.back() == 's' || t.back() == 'S') {
+    sec = 1;
+    t.pop_back();
+  }
+  if (*is_sec == -1) *is_sec = sec;
+  else if (*is_sec != sec)
+    return fail(SMILEHIP_ERR_INVALID, "frameList: '%s' mixes seconds and rows with the values before it: suffix all values with s or none", whole.c_str());
+  if (t.empty() || t[0] == ' ') return fail(SMILEHIP_ERR_INVALID, "frameList: '%s' is not a number", whole.c_str());
+  char *end = nullptr;
+  const double x = strtod(t.c_str(), &end);
+  if (end == t.c_str() || *end != 0 || !std::isfinite(x) || std::fabs(x) > 1e15)
+    return fail(SMILEHIP_ERR_INVALID, "frameList: '%s' is not a number", whole.c_str());
+  *v = x;
+  return SMILEHIP_OK;
+}
+}  // namespace
+
+extern "C" int smilehip_func_list_parse(const char *frame_list, double period, int64_t *first_rows, int64_t *n_rows, int32_t cap,
+                                        int32_t *n_segments) {
+  const char *who = "smilehip_func_list_parse";
+  if (!frame_list || !n_segments) return fail(SMILEHIP_ERR_INVALID, "%s: null argument", who);
+  if (cap < 0 || (cap > 0 && (!first_rows || !n_rows))) return fail(SMILEHIP_ERR_INVALID, "%s: cap %d without arrays", who, cap);
+  if (!(period >= 0.0)) return fail(SMILEHIP_ERR_INVALID, "%s: period must be >= 0", who);
+  *n_segments = 0;
+  const double T = period == 0.0 ? 1.0 : period;                  // :534-535
+  const std::string fl(frame_list);
+  int is_iv = -1, is_sec = -1;
+  double last = 0.0;
+  int64_t n = 0;
+  size_t pos = 0;
+  for (;;) {
+    const size_t comma = fl.find(',', pos);
+    const std::string tok = fl.substr(pos, comma == std::string::npos ? std::string::npos : comma - pos);
+    if (tok.find_first_not_of(' ') == std::string::npos) return fail(SMILEHIP_ERR_INVALID, "frameList: empty token (segment %lld of '%s')", (long long)n, frame_list);
+    const size_t dash = tok.find('-');
+    const int iv = dash != std::string::npos;
+    if (is_iv == -1) is_iv = iv;
+    else if (is_iv != iv)
+      return fail(SMILEHIP_ERR_INVALID, "frameList: '%s' mixes intervals and lengths with the tokens before it (the reference calls the result unpredictable)", tok.c_str());
+    double start, end;
+    int64_t r0, r1;
+    int rc;
+    if (iv) {                                                     // :211-246
+      if ((rc = list_value(tok.substr(0, dash), tok, &start, &is_sec)) || (rc = list_value(tok.substr(dash + 1), tok, &end, &is_sec))) return rc;
+      if (is_sec) {
+        if (end - start < 0.01) end = start + 0.01;               // :228-233 "too short", the reference warns and goes on
+      } else {
+        if (end - start < 3) end = start + 3;                     // :237-242
+        start = (double)(long)start;
+        end = (double)(long)end;
+      }
+    } else {                                                      // :247-286 a length; the segments are contiguous
+      double len;
+      if ((rc = list_value(tok, tok, &len, &is_sec))) return rc;
+      if (is_sec) {
+        if (len < 0.01)
+          return fail(SMILEHIP_ERR_INVALID, "frameList: length '%s' is below 0.01 s (the reference logs an error and does not set a minimum length)", tok.c_str());
+        start = last;
+        end = last + len;
+      } else {
+        if (len < 3) len = 3;                                     // :274-279
+        start = (double)(long)last;
+        end = (double)(long)(last + len - 1);
+      }
+      last += len;
+    }
+    if (is_sec) {                                                 // :537-539, the reference's own double expressions
+      r0 = (int64_t)std::floor(start / T);
+      r1 = (int64_t)std::ceil(end / T);
+    } else {
+      r0 = (int64_t)start;
+      r1 = (int64_t)end;
+    }
+    if (cap > 0) {
+      if (n >= cap) return fail(SMILEHIP_ERR_INVALID, "%s: more than cap = %d segments in '%s'", who, cap, frame_list);
+      first_rows[n] = r0;
+      n_rows[n] = r1 - r0 + 1;                                    // getMatrix(start, end - start + 1), :947
+    }
+    ++n;
+    if (n > INT32_MAX) return fail(SMILEHIP_ERR_INVALID, "%s: too many segments", who);
+    if (comma == std::string::npos) break;
+    pos = comma + 1;
+  }
+  *n_segments = (int32_t)n;
+  return SMILEHIP_OK;
+}
+
+// :951-962: frameIdx only advances when the segment could be read
+extern "C" int smilehip_func_list_fit(const int64_t *first_rows, const int64_t *n_rows, int32_t n, int64_t rows, int32_t *n_emitted) {
+  if (n < 0 || !n_emitted || (n > 0 && (!first_rows || !n_rows))) return fail(SMILEHIP_ERR_INVALID, "smilehip_func_list_fit: bad argument");
+  int32_t i = 0;
+  while (i < n && first_rows[i] + n_rows[i] - 1 < rows) ++i;
+  *n_emitted = i;
+  return SMILEHIP_OK;
+}
+
+namespace {
+// what both compute entry points refuse before anything is launched or written: utterance u's segments [s0, s1) against its rows
+int segments_check(const smilehip_func_spec *spec, int u, int64_t s0, int64_t s1, const int64_t *h_first, const int64_t *h_rows, int64_t rows,
+                   const char *who) {
+  const bool mod = has_family(*spec, SMILEHIP_FAM_MODULATION);
+  for (int64_t s = s0; s < s1; ++s) {
+    const long long k = (long long)(s - s0), f = (long long)h_first[s], r = (long long)h_rows[s];
+    if (r < 1) return fail(SMILEHIP_ERR_INVALID, "%s: utterance %d, segment %lld: %lld rows (a segment has at least 1)", who, u, k, r);
+    if (f < 0) return fail(SMILEHIP_ERR_INVALID, "%s: utterance %d, segment %lld: first row %lld is negative", who, u, k, f);
+    if (f > rows || r > rows - f)
+      return fail(SMILEHIP_ERR_INVALID, "%s: utterance %d, segment %lld: rows [%lld, %lld] end beyond the utterance's %lld rows", who, u, k, f,
+                  f + r - 1, (long long)rows);
+    if (mod && r < 34)
+      return fail(SMILEHIP_ERR_INVALID, "%s: utterance %d, segment %lld: Modulation needs segments of at least 34 rows (%lld): contours of fewer "
+                  "than 34 values have no transform built", who, u, k, r);
+  }
+  return SMILEHIP_OK;
+}
+
+// it: one descriptor per segment in the CALLER's order (xrow0 absolute, rows, orow; srow0 is set here)
+int run_segments(smilehip_context *ctx, FsSegParams &P, std::vector<FsSeg> &it, float *d_func, int64_t ld_func, hipStream_t stream, const char *who) {
+  int fam_off[12], fam_want[12];
+  const int per = spec_layout(&P.spec, fam_off, fam_want);
+  if (per < 0) return per;
+  if (it.empty()) return SMILEHIP_OK;
+  P.per = per;
+  P.it_pack = P.n_cols <= 32 ? 64 / P.n_cols : 1;
+  // The schedule: output row = position in the caller's list, execution order = longest first (stable), so the items a packed
+  // wave takes side by side are of (nearly) one length and finish together, and each chunk's longest contour is its first.
+  int64_t longest = it.front().rows, shortest = longest;
+  bool in_order = true;                                         // (lists of one length, and lists that come sorted, are left alone)
+  for (size_t i = 0; i < it.size(); ++i) {
+    longest = std::max(longest, it[i].rows);
+    shortest = std::min(shortest, it[i].rows);
+    if (i && it[i].rows > it[i - 1].rows) in_order = false;
+  }
+  if (!in_order) {
+    // a stable radix sort on longest - rows, 11 bits a pass: the host's share of a call of 100 000 segments stays well below
+    // the kernels' (a comparison sort of the descriptors took a third of that call)
+    std::vector<FsSeg> tmp(it.size());
+    const uint64_t span = (uint64_t)(longest - shortest);
+    for (int shift = 0; shift < 64 && (span >> shift) != 0; shift += 11) {
+      size_t count[2049] = {0};
+      for (const FsSeg &q : it) ++count[(((uint64_t)(longest - q.rows) >> shift) & 2047u) + 1];
+      for (int d = 0; d < 2048; ++d) count[d + 1] += count[d];
+      for (const FsSeg &q : it) tmp[count[((uint64_t)(longest - q.rows) >> shift) & 2047u]++] = q;
+      it.swap(tmp);
+    }
+  }
+  FsNeed need = spec_need(P, 1, longest, longest);
+  const double cell = (need.nz ? 4.0 : 0.0) + (need.alive ? 1.0 : 0.0) + (need.sorted ? 8.0 : 0.0);
+  const double bound = windows_scratch_bytes();
+  const int64_t grid_cap = (int64_t(1) << 30) / std::max(P.n_cols, 64);       // items x columns and items x groups stay ints
+  // chunks of whole segments along the sorted order, at least one each; every chunk's scratch rows start at 0
+  std::vector<size_t> chunk_first;
+  int64_t max_rows_sum = 0, max_items = 0, rows_sum = 0, items = 0;
+  double bytes = 0.0;
+  for (size_t i = 0; i < it.size(); ++i) {
+    const double b = (double)P.n_cols * (16.0 + (double)it[i].rows * cell);
+    if (i == 0 || items >= grid_cap || bytes + b > bound) {
+      chunk_first.push_back(i);
+      rows_sum = 0; items = 0; bytes = 0.0;
+    }
+    it[i].srow0 = rows_sum;
+    rows_sum += it[i].rows; items += 1; bytes += b;
+    max_rows_sum = std::max(max_rows_sum, rows_sum);
+    max_items = std::max(max_items, items);
+  }
+  chunk_first.push_back(it.size());
+  need.rows = max_rows_sum;
+  need.n_utt = (int)max_items;
+  // the descriptors live in front of the call's scratch and go up once, ordered on the stream with the kernels that read them
+  const size_t desc_bytes = align256(it.size() * sizeof(FsSeg));
+  int rc = fs_reserve(ctx, desc_bytes + fs_bytes(P, need), stream);
+  if (rc) return rc;
+  char *base = static_cast<char *>(ctx->fs_scratch);
+  FsSeg *d_seg = reinterpret_cast<FsSeg *>(base);
+  fs_carve(base + desc_bytes, P, need);
+  std::memset(&P.mod, 0, sizeof(P.mod));
+  if (has_family(P.spec, SMILEHIP_FAM_MODULATION) && (rc = mod_prepare(ctx, P.spec, P.mod))) return rc;
+  // (`it` is pageable host memory: HIP performs such a copy synchronously for the host, in the stream's order for the device)
+  HIP_TRY(hipMemcpyAsync(d_seg, it.data(), it.size() * sizeof(FsSeg), hipMemcpyHostToDevice, stream));
+  P.out = d_func;
+  P.ld_out = ld_func;
+  for (size_t c = 0; c + 1 < chunk_first.size(); ++c) {         // chunks follow each other on the stream and share the scratch
+    const size_t first = chunk_first[c];
+    P.seg = d_seg + first;
+    P.it_n = (int32_t)(chunk_first[c + 1] - first);
+    P.max_rows = it[first].rows;                                // the chunk's longest: the workgroup sort only where it is needed
+    hipError_t e = launch_funcspec_segments(P, fam_off, fam_want, stream);
+    if (e != hipSuccess) return fail(SMILEHIP_ERR_HIP, "%s: functionals kernel launch failed: %s", who, hipGetErrorString(e));
+  }
+  return SMILEHIP_OK;
+}
+}  // namespace
+
+extern "C" int smilehip_funcspec_matrix_segments(smilehip_context *ctx, const smilehip_func_spec *spec, const float *d_lld, int64_t ld_lld,
+                                                 int64_t rows, int32_t cols, int32_t n_seg, const int64_t *h_first, const int64_t *h_rows,
+                                                 float *d_func, int64_t ld_func, void *stream) {
+  const char *who = "smilehip_funcspec_matrix_segments";
+  const int per = spec_layout(spec, nullptr, nullptr);
+  if (per < 0) return per;
+  if (rows < 0 || cols < 1 || ld_lld < cols || n_seg < 0 || (n_seg > 0 && (!h_first || !h_rows))) return fail(SMILEHIP_ERR_INVALID, "%s: bad argument", who);
+  if (ld_func < (int64_t)cols * per) return fail(SMILEHIP_ERR_INVALID, "ld_func %lld < %d values per segment", (long long)ld_func, cols * per);
+  int rc = segments_check(spec, 0, 0, n_seg, h_first, h_rows, rows, who);
+  if (rc) return rc;
+  if (!ctx) return fail(SMILEHIP_ERR_NO_DEVICE, "%s: no device context", who);
+  if (n_seg == 0) return SMILEHIP_OK;
+  if (!d_lld || !d_func) return fail(SMILEHIP_ERR_INVALID, "%s: null device pointer", who);
+  std::vector<FsSeg> it((size_t)n_seg);
+  for (int32_t s = 0; s < n_seg; ++s) it[s] = FsSeg{h_first[s], h_rows[s], 0, s, 0};
+  FsSegParams P;
+  std::memset(&P, 0, sizeof(P));
+  P.spec = *spec;
+  P.x = d_lld;
+  P.ld_x = ld_lld;
+  P.n_cols = cols;
+  P.single_rows = -1;
+  return run_segments(ctx, P, it, d_func, ld_func, (hipStream_t)stream, who);
+}
+
+extern "C" int smilehip_batch_funcspec_segments(smilehip_plan *plan, smilehip_batch *b, const smilehip_func_spec *spec, const float *d_lld,
+                                                int64_t ld_lld, int32_t col_first, int32_t n_cols, int32_t rows_cut, const int64_t *h_seg_off,
+                                                const int64_t *h_first, const int64_t *h_rows, float *d_func, int64_t ld_func, void *stream) {
+  const char *who = "smilehip_batch_funcspec_segments";
+  if (!plan || !b || b->plan != plan) return fail(SMILEHIP_ERR_INVALID, "%s: plan/batch mismatch", who);
+  const int per = spec_layout(spec, nullptr, nullptr);
+  if (per < 0) return per;
+  if (!h_seg_off) return fail(SMILEHIP_ERR_INVALID, "%s: null h_seg_off", who);
+  if (col_first < 0 || n_cols < 1 || col_first + n_cols > ld_lld)
+    return fail(SMILEHIP_ERR_INVALID, "%s: columns [%d, %d) outside the matrix (ld %lld)", who, col_first, col_first + n_cols, (long long)ld_lld);
+  if (rows_cut < 0) return fail(SMILEHIP_ERR_INVALID, "%s: rows_cut must be >= 0", who);
+  if (ld_func < (int64_t)n_cols * per) return fail(SMILEHIP_ERR_INVALID, "ld_func %lld < %d values per segment", (long long)ld_func, n_cols * per);
+  if (h_seg_off[0] != 0) return fail(SMILEHIP_ERR_INVALID, "%s: h_seg_off[0] must be 0", who);
+  for (int32_t u = 0; u < b->n_utt; ++u)
+    if (h_seg_off[u + 1] < h_seg_off[u])
+      return fail(SMILEHIP_ERR_INVALID, "%s: utterance %d: h_seg_off is not monotone (%lld after %lld)", who, u, (long long)h_seg_off[u + 1], (long long)h_seg_off[u]);
+  const int64_t total = h_seg_off[b->n_utt];
+  if (total > INT32_MAX) return fail(SMILEHIP_ERR_INVALID, "%s: more than 2^31 - 1 segments", who);
+  if (total > 0 && (!h_first || !h_rows)) return fail(SMILEHIP_ERR_INVALID, "%s: null segment arrays", who);
+  for (int32_t u = 0; u < b->n_utt; ++u) {
+    const int64_t rows = std::max<int64_t>(0, b->h_row_off[u + 1] - b->h_row_off[u] - rows_cut);
+    int rc = segments_check(spec, u, h_seg_off[u], h_seg_off[u + 1], h_first, h_rows, rows, who);
+    if (rc) return rc;
+  }
+  if (!plan->ctx) return fail(SMILEHIP_ERR_NO_DEVICE, "%s: host-only plan", who);
+  if (total == 0) return SMILEHIP_OK;
+  if (!d_lld || !d_func) return fail(SMILEHIP_ERR_INVALID, "%s: null device pointer", who);
+  std::vector<FsSeg> it((size_t)total);
+  for (int32_t u = 0; u < b->n_utt; ++u)
+    for (int64_t s = h_seg_off[u]; s < h_seg_off[u + 1]; ++s) it[s] = FsSeg{b->h_row_off[u] + h_first[s], h_rows[s], 0, (int32_t)s, 0};
+  FsSegParams P;
+  std::memset(&P, 0, sizeof(P));
+  P.spec = *spec;
+  P.x = d_lld;
+  P.ld_x = ld_lld;
+  P.col_first = col_first;
+  P.n_cols = n_cols;
+  P.single_rows = -1;
+  return run_segments(plan->ctx, P, it, d_func, ld_func, (hipStream_t)stream, who);
+}

@@ -315,7 +315,7 @@ bool write_arff(const std::string &path, const std::vector<std::string> &names, 
     const bool wrote = write_text_rows(f, rows, max_row, [&](int64_t t, char *p) {
       size_t n = name.size();
       std::memcpy(p, name.data(), n);
-      if (opt.timestamp) n += (size_t)snprintf(p + n, 64, "%f,", (double)t * period_sec);
+      if (opt.timestamp) n += (size_t)snprintf(p + n, 64, "%f,", opt.times ? opt.times[t] : (double)t * period_sec);
       for (int c = 0; c < cols; ++c) {
         if (c) p[n++] = ',';
         n += (size_t)format_e6(x[t * ld + c], p + n);

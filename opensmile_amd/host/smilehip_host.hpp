@@ -89,6 +89,7 @@ bool write_csv(const std::string &path, const std::vector<std::string> &names, c
 struct ArffOptions {
   bool append = true, timestamp = false;
   std::string relation = "openSMILE_features", instance_name = "unknown", class_type = "numeric", class_value = "?";
+  const double *times = nullptr;   // frameTime of each row where the rows are not period_sec apart (listed segments)
 };
 std::string arff_escape(const std::string &s);
 bool write_arff(const std::string &path, const std::vector<std::string> &names, const float *x, int64_t rows, int cols,

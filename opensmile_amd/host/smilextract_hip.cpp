@@ -11,6 +11,10 @@
 //                   [-frameMode fixed -frameSize s -frameStep s [-frameCenterSpecial left]]   functionals over fixed windows: what
 //                   replacing config/shared/FrameModeFunctionals.conf.inc does in the reference -- one row per window in the
 //                   ARFF / CSV / functionals HTK file (is09_emotion only; -frameMode full is the default)
+//                   [-frameMode list (-frameList "a-b,..." | -frameListFile file)]   functionals over listed segments: one row per
+//                   segment that fits the file, in list order (values with the suffix s are seconds, others rows of the LLD level;
+//                   "a-b" intervals or "n" contiguous lengths); the list applies to every file, a third column of a -filelist
+//                   line gives that file its own
 //   smilextract_hip --set compare16_lld (-I in.wav | -filelist list.txt) [-lldcsvoutput lld.csv] [-lldhtkoutput lld.htk]
 //                   (the 130-column LLD level of ComParE_2016 only)
 //   smilextract_hip --set compare16     same options as is09_emotion: the whole ComParE_2016.conf, LLD level + 6373 functionals
@@ -56,7 +60,11 @@ using namespace smilehip_host;
 
 namespace {
 
-struct Job { std::string wav, inst; };
+struct Job {
+  std::string wav, inst;
+  std::string list;                          // -frameMode list: the file's own list (third column of its -filelist line)
+  std::vector<int64_t> seg_first, seg_rows;  // ... and the segments the list in force for this file names
+};
 
 std::function<void()> g_before_exit;                    // waits for the ingest thread that reads ahead (exit() under a running thread is a crash at best)
 [[noreturn]] void die(const std::string &m) {
@@ -116,7 +124,7 @@ static int run_main(int argc, char **argv, Persist *ps) {
   std::map<std::string, std::string> opt, conf_cmdline;
   const char *with_value[] = {"--set", "-C", "-I", "-filelist", "-O", "-csvoutput", "-htkoutput", "-lldcsvoutput", "-lldhtkoutput",
                               "-instname", "-N", "-outdir", "--device", "--rank", "--world", "--chunk-files", "--master-addr", "--master-port",
-                              "-frameMode", "-frameSize", "-frameStep", "-frameCenterSpecial"};
+                              "-frameMode", "-frameSize", "-frameStep", "-frameCenterSpecial", "-frameList", "-frameListFile"};
   bool with_conf = false, print_fingerprint = false, describe_only = false, gather = false;
   for (int i = 1; i < argc; ++i)
     if (!strcmp(argv[i], "-C")) with_conf = true;
@@ -235,18 +243,23 @@ static int run_main(int argc, char **argv, Persist *ps) {
   const bool has_func = is09 || cmp16f || egm;
   // ---- functionals over fixed windows (cWinToVecProcessor frameMode = fixed): IS09_emotion's one instance
   const std::string frame_mode = opt.count("-frameMode") ? opt["-frameMode"] : "full";
-  if (frame_mode != "full" && frame_mode != "fixed")
-    die("-frameMode " + frame_mode + ": full and fixed are built (var, list and meta are not)");
-  const bool windows = frame_mode == "fixed";
+  if (frame_mode != "full" && frame_mode != "fixed" && frame_mode != "list")
+    die("-frameMode " + frame_mode + ": full, fixed and list are built (var and meta are not)");
+  const bool fixed = frame_mode == "fixed", listed = frame_mode == "list";
+  const bool windows = fixed || listed;                     // several function rows per file
   if (opt.count("-frameCenterSpecial") && opt["-frameCenterSpecial"] != "left")
     die("-frameCenterSpecial " + opt["-frameCenterSpecial"] + ": only left is built");
-  if (windows && !is09)
+  if (listed && !is09)
+    die("-frameMode list is built for --set is09_emotion only (" + (set.empty() ? std::string("-C file") : "--set " + set) +
+        ": its functionals levels read levels of different lengths, see DESIGN.md)");
+  if (listed && gather) die("--gather is not available with -frameMode list (the rows per file vary): write per-rank files and concatenate");
+  if (fixed && !is09)
     die("-frameMode fixed is built for --set is09_emotion only (" + (set.empty() ? std::string("-C file") : "--set " + set) +
         ": its functionals levels read levels of different lengths, see DESIGN.md)");
-  if (windows && gather) die("--gather is not available with -frameMode fixed (the rows per file vary): write per-rank files and concatenate");
-  if (windows && (!opt.count("-frameSize") || !opt.count("-frameStep"))) die("-frameMode fixed needs -frameSize and -frameStep (seconds)");
-  const double frame_size_sec = windows ? atof(opt["-frameSize"].c_str()) : 0.0, frame_step_sec = windows ? atof(opt["-frameStep"].c_str()) : 0.0;
-  if (windows) {                                            // refused before any file is read: a size below one row, a step of 0 s (= full mode)
+  if (fixed && gather) die("--gather is not available with -frameMode fixed (the rows per file vary): write per-rank files and concatenate");
+  if (fixed && (!opt.count("-frameSize") || !opt.count("-frameStep"))) die("-frameMode fixed needs -frameSize and -frameStep (seconds)");
+  const double frame_size_sec = fixed ? atof(opt["-frameSize"].c_str()) : 0.0, frame_step_sec = fixed ? atof(opt["-frameStep"].c_str()) : 0.0;
+  if (fixed) {                                            // refused before any file is read: a size below one row, a step of 0 s (= full mode)
     smilehip_lld_config c9;
     smilehip_config_is09_lld(&c9);
     check(smilehip_func_window_geometry(c9.frame_step_sec, frame_size_sec, frame_step_sec, 0, nullptr, nullptr, nullptr), "-frameSize / -frameStep");
@@ -281,11 +294,44 @@ static int run_main(int argc, char **argv, Persist *ps) {
       while (!s.empty() && (s.back() == '\n' || s.back() == '\r')) s.pop_back();
       if (s.empty()) continue;
       const size_t tab = s.find('\t');
-      jobs.push_back(tab == std::string::npos ? Job{s, basename_noext(s)} : Job{s.substr(0, tab), s.substr(tab + 1)});
+      if (tab == std::string::npos) { jobs.push_back(Job{s, basename_noext(s)}); continue; }
+      const size_t tab2 = listed ? s.find('\t', tab + 1) : std::string::npos;        // -frameMode list: wav<TAB>instname<TAB>list
+      jobs.push_back(Job{s.substr(0, tab), s.substr(tab + 1, tab2 == std::string::npos ? std::string::npos : tab2 - tab - 1)});
+      if (tab2 != std::string::npos) jobs.back().list = s.substr(tab2 + 1);
     }
     fclose(f);
   }
   if (jobs.empty()) die("no input (-I or -filelist)");
+  if (listed) {
+    // the list in force for a file: its own (third column), else -frameListFile (first line; the reference prefers it over
+    // -frameList, winToVecProcessor.cpp:336-372), else -frameList. Every list is parsed before any file is read.
+    std::string common;
+    bool have_common = false;
+    if (opt.count("-frameListFile")) {
+      FILE *f = fopen(opt["-frameListFile"].c_str(), "r");
+      if (!f) die("cannot open -frameListFile '" + opt["-frameListFile"] + "'");
+      int ch;
+      while ((ch = fgetc(f)) != EOF && ch != '\n') common += (char)ch;
+      fclose(f);
+      while (!common.empty() && common.back() == '\r') common.pop_back();
+      have_common = true;
+    } else if (opt.count("-frameList")) {
+      common = opt["-frameList"];
+      have_common = true;
+    }
+    smilehip_lld_config c9;
+    smilehip_config_is09_lld(&c9);
+    for (Job &job : jobs) {
+      if (job.list.empty() && !have_common)
+        die("-frameMode list needs a list: -frameList, -frameListFile or a third column in the -filelist line ('" + job.wav + "' has none)");
+      const std::string &fl = job.list.empty() ? common : job.list;
+      int32_t n = 0;
+      check(smilehip_func_list_parse(fl.c_str(), c9.frame_step_sec, nullptr, nullptr, 0, &n), "-frameList");
+      job.seg_first.assign((size_t)n, 0);
+      job.seg_rows.assign((size_t)n, 0);
+      if (n) check(smilehip_func_list_parse(fl.c_str(), c9.frame_step_sec, job.seg_first.data(), job.seg_rows.data(), n, &n), "-frameList");
+    }
+  }
   // one process per GPU: --rank / --world, or the RANK / WORLD_SIZE / LOCAL_RANK variables of torch.distributed.run
   auto env_int = [](const char *name, int dflt) { const char *v = getenv(name); return v && *v ? atoi(v) : dflt; };
   const int rank = opt.count("--rank") ? atoi(opt["--rank"].c_str()) : env_int("RANK", 0);
@@ -667,7 +713,35 @@ static int run_main(int argc, char **argv, Persist *ps) {
                               : (cmp16f ? smilehip_functionals_compare16_count() : (egm ? smilehip_functionals_egemaps_count() : 0));
       w->n_func = n_func;
       std::vector<float> &func = w->func;
-      if (has_func && windows) {
+      if (has_func && listed) {
+        // one function row per segment of the file's list that fits its LLD rows (all T + 1 of them); the first that does not fit
+        // ends the file's rows as it does in the reference (winToVecProcessor.cpp:951-962), with one line on stderr
+        w->win_off.assign(idx.size() + 1, 0);
+        w->func_period = 0.0;
+        func_period = g.frame_period;
+        std::vector<int64_t> seg_first, seg_rows;
+        for (size_t i = 0; i < idx.size(); ++i) {
+          const Job &job = jobs[idx[i]];
+          const int64_t rows_i = row_off[i + 1] - row_off[i];
+          int32_t fit = 0;
+          check(smilehip_func_list_fit(job.seg_first.data(), job.seg_rows.data(), (int32_t)job.seg_first.size(), rows_i, &fit), "smilehip_func_list_fit");
+          if ((size_t)fit < job.seg_first.size())
+            fprintf(stderr, "smilextract_hip: %s: segment %d of its frame list (rows %lld .. %lld) does not fit its %lld rows: it and the %d after it are not written\n",
+                    job.wav.c_str(), fit, (long long)job.seg_first[(size_t)fit], (long long)(job.seg_first[(size_t)fit] + job.seg_rows[(size_t)fit] - 1),
+                    (long long)rows_i, (int)job.seg_first.size() - fit - 1);
+          seg_first.insert(seg_first.end(), job.seg_first.begin(), job.seg_first.begin() + fit);
+          seg_rows.insert(seg_rows.end(), job.seg_rows.begin(), job.seg_rows.begin() + fit);
+          w->win_off[i + 1] = w->win_off[i] + fit;
+        }
+        const int64_t n_win = w->win_off.back();
+        smilehip_func_spec spec09;
+        check(smilehip_funcspec_is09(&spec09), "smilehip_funcspec_is09");
+        d_func = dev_reserve(dev_func[slot], (uint64_t)std::max<int64_t>(n_win, 1) * n_func * 4);
+        check(smilehip_batch_funcspec_segments(plan, b, &spec09, (const float *)d_lld, n_out, 0, n_out, 0, w->win_off.data(), seg_first.data(),
+                                               seg_rows.data(), (float *)d_func, n_func, st), "smilehip_batch_funcspec_segments");
+        func.resize((size_t)n_win * (size_t)n_func);
+        if (n_win > 0) check(smilehip_copy_to_host(ctx, func.data(), d_func, (uint64_t)func.size() * 4, st), "copy_to_host");
+      } else if (has_func && windows) {
         // one function row per window, win_off[i + 1] - win_off[i] of them for file i: IS09's windows run over all rows of the LLD level
         int64_t size_rows = 0, step_rows = 0;
         check(smilehip_func_window_geometry(g.frame_period, frame_size_sec, frame_step_sec, 0, &size_rows, &step_rows, nullptr), "-frameSize / -frameStep");
@@ -827,16 +901,19 @@ static int run_main(int argc, char **argv, Persist *ps) {
       // = the time of the window's first row
       const int n_func = windows ? (int)fnames.size() : (int)fv.size();
       const int64_t n_rows = (int64_t)(fv.size() / (size_t)n_func);
+      std::vector<double> seg_times;                          // listed segments: frameTime = the time of the segment's first row
+      for (int64_t k = 0; listed && k < n_rows; ++k) seg_times.push_back((double)jobs[j].seg_first[(size_t)k] * func_period);
       if (opt.count("-O") && opt["-O"] != "?") {
         ArffOptions ao;
         ao.instance_name = jobs[j].inst;
+        if (listed) ao.times = seg_times.data();
         if (!write_arff(summary_path(opt["-O"]), fnames, fv.data(), n_rows, n_func, n_func, func_period, ao, err)) die(err);
       }
       if (opt.count("-csvoutput") && opt["-csvoutput"] != "?") {
         CsvOptions co;
         co.instance_name = jobs[j].inst;
         co.append = true;
-        if (!write_csv(summary_path(opt["-csvoutput"]), fnames, fv.data(), n_rows, n_func, n_func, func_period, nullptr, co, err)) die(err);
+        if (!write_csv(summary_path(opt["-csvoutput"]), fnames, fv.data(), n_rows, n_func, n_func, func_period, listed ? seg_times.data() : nullptr, co, err)) die(err);
       }
     }
     t_device += now() - tf0;
