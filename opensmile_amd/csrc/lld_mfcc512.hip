@@ -31,8 +31,11 @@
 //           in index order jj = 0 .. 15). LDS operations
 //           of a wave return in order: what a wave waits for is decided by the ORDER of its requests. No instruction is added,
 //           and an instruction's lane -> bank pattern does not depend on its position (tools/lds_bank_sim.py)
-//   spect.  lanes j and 16-j own mirror-image bins: the partner's half of Z
-//           arrives by two DPP steps (row shift + row mirror), BOTH X[k] and
+//   spect.  columns c and 16-c own mirror-image bins. Lane j transforms column kc(j) = 0 .. 7, 9 .. 15, 8 (it reads that column of
+//           the transposition buffer; its twiddles and its places in the power buffer go by kc too), so lanes i and 15-i hold
+//           partner columns: the partner's half of Z arrives by ONE DPP step (row_mirror), in place; lane 15 (column 8) and lane 0
+//           (column 0) are their own partners, lane 0 one register up (untangle_partner). The PLP chain and the delta-fused MP = 16
+//           instances keep kc = j and three DPP steps (one_hop_exchange()). BOTH X[k] and
 //           X[256-k] are untangled from one (Z[k], Z[256-k]) pair (R4), power
 //           (R5, R6's square) -> LDS power buffer (octets of bins, 12 floats apart)
 //   mel     R6 as table-driven work units: a unit = one aligned octet of bins
@@ -192,6 +195,57 @@ __device__ __forceinline__ float dpp_f(float v) {
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
 }
 
+// The untangle partner's half of Z, in place on x[8 .. 15] and y[8 .. 15] (re and im of the second DFT16's outputs; lane-to-column
+// map 0 .. 7, 9 .. 15, 8): lanes 1 .. 14 of every row take the register of the lane opposite (row_mirror), lane 15 keeps its own, lane 0
+// moves its own x[r + 1] to x[r] for r = 8 .. 14 (x[15] stays: its q = 0 is the DC / Nyquist pair). Written out, because the compiler
+// resolves the join of the three lane classes with 30 to 60 register-shuffling moves: here it is 16 DPP moves + 14 moves, and seven
+// scalar moves of EXEC around them (saved and restored: the block leaves EXEC as it found it).
+// Wait states: a DPP move reads a VGPR that a vector instruction may have written right in front of the block -- two wait
+// states, which the three scalar moves in front of the first DPP move are; the DPP moves read and write disjoint registers; the plain
+// moves behind them are interlocked by the hardware. A SCALAR write of EXEC needs no wait state in front of a DPP move (only a
+// vector instruction's write of EXEC does).
+__device__ __forceinline__ void untangle_partner(float (&x)[16], float (&y)[16]) {
+  unsigned long long sv;
+  asm volatile(
+      "s_mov_b64 %[sv], exec\n"
+      "s_mov_b32 exec_lo, 0x7ffe7ffe\n"
+      "s_mov_b32 exec_hi, 0x7ffe7ffe\n"
+      "v_mov_b32_dpp %[x8], %[x8] row_mirror row_mask:0xf bank_mask:0xf\n"
+      "v_mov_b32_dpp %[x9], %[x9] row_mirror row_mask:0xf bank_mask:0xf\n"
+      "v_mov_b32_dpp %[x10], %[x10] row_mirror row_mask:0xf bank_mask:0xf\n"
+      "v_mov_b32_dpp %[x11], %[x11] row_mirror row_mask:0xf bank_mask:0xf\n"
+      "v_mov_b32_dpp %[x12], %[x12] row_mirror row_mask:0xf bank_mask:0xf\n"
+      "v_mov_b32_dpp %[x13], %[x13] row_mirror row_mask:0xf bank_mask:0xf\n"
+      "v_mov_b32_dpp %[x14], %[x14] row_mirror row_mask:0xf bank_mask:0xf\n"
+      "v_mov_b32_dpp %[x15], %[x15] row_mirror row_mask:0xf bank_mask:0xf\n"
+      "v_mov_b32_dpp %[y8], %[y8] row_mirror row_mask:0xf bank_mask:0xf\n"
+      "v_mov_b32_dpp %[y9], %[y9] row_mirror row_mask:0xf bank_mask:0xf\n"
+      "v_mov_b32_dpp %[y10], %[y10] row_mirror row_mask:0xf bank_mask:0xf\n"
+      "v_mov_b32_dpp %[y11], %[y11] row_mirror row_mask:0xf bank_mask:0xf\n"
+      "v_mov_b32_dpp %[y12], %[y12] row_mirror row_mask:0xf bank_mask:0xf\n"
+      "v_mov_b32_dpp %[y13], %[y13] row_mirror row_mask:0xf bank_mask:0xf\n"
+      "v_mov_b32_dpp %[y14], %[y14] row_mirror row_mask:0xf bank_mask:0xf\n"
+      "v_mov_b32_dpp %[y15], %[y15] row_mirror row_mask:0xf bank_mask:0xf\n"
+      "s_mov_b32 exec_lo, 0x00010001\n"
+      "s_mov_b32 exec_hi, 0x00010001\n"
+      "v_mov_b32 %[x8], %[x9]\n"
+      "v_mov_b32 %[x9], %[x10]\n"
+      "v_mov_b32 %[x10], %[x11]\n"
+      "v_mov_b32 %[x11], %[x12]\n"
+      "v_mov_b32 %[x12], %[x13]\n"
+      "v_mov_b32 %[x13], %[x14]\n"
+      "v_mov_b32 %[x14], %[x15]\n"
+      "v_mov_b32 %[y8], %[y9]\n"
+      "v_mov_b32 %[y9], %[y10]\n"
+      "v_mov_b32 %[y10], %[y11]\n"
+      "v_mov_b32 %[y11], %[y12]\n"
+      "v_mov_b32 %[y12], %[y13]\n"
+      "v_mov_b32 %[y13], %[y14]\n"
+      "v_mov_b32 %[y14], %[y15]\n"
+      "s_mov_b64 exec, %[sv]\n"
+      : [sv] "=&s"(sv), [x8] "+v"(x[8]), [x9] "+v"(x[9]), [x10] "+v"(x[10]), [x11] "+v"(x[11]), [x12] "+v"(x[12]), [x13] "+v"(x[13]), [x14] "+v"(x[14]), [x15] "+v"(x[15]), [y8] "+v"(y[8]), [y9] "+v"(y[9]), [y10] "+v"(y[10]), [y11] "+v"(y[11]), [y12] "+v"(y[12]), [y13] "+v"(y[13]), [y14] "+v"(y[14]), [y15] "+v"(y[15]));
+}
+
 }  // namespace
 
 // The next pass's samples of one lane: pair n = j + 16 m of frame tp + g for m < MP. ALIGNED (the buffer is 4-byte
@@ -225,6 +279,15 @@ __device__ __forceinline__ float dpp_f(float v) {
 // (tools/dev/kernel_resources.sh lld_mfcc512.hip).
 template <int MP, bool PLP, bool DELTA>
 constexpr bool typed_loads() {
+  return !PLP && !(MP == 16 && DELTA);
+}
+// The untangle partner by the column map and one row_mirror (untangle_partner above) or, without the map, in three DPP steps.
+// Per instance: the one-hop form holds the lane's column and bin 128's value (taken in front of the exchange) in two registers
+// more at the point where the instances at 128 VGPRs are full -- with it the 21 instances of the PLP chain and of MP = 16 with the
+// regression stages fused had 4 or 8 bytes more scratch per lane each. They keep the three-step form: the rule is typed_loads()'s,
+// and with it no instance has more scratch than before (tools/dev/kernel_resources.sh lld_mfcc512.hip).
+template <int MP, bool PLP, bool DELTA>
+constexpr bool one_hop_exchange() {
   return !PLP && !(MP == 16 && DELTA);
 }
 typedef float float2v __attribute__((ext_vector_type(2)));
@@ -376,8 +439,13 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
   const uint32_t out_off_dd = out_off + (uint32_t)P.n_mfcc * 8u;
   const float nkpre = P.de ? P.k : -P.k;       // y = x + nkpre * x'  (de: y = x + k x'), wave-uniform: the FMAs below stay v_fmac
   const int m0 = P.pad_left >> 5, j0 = (P.pad_left >> 1) & 15;       // where sample 0 of a frame sits
-  float *pb_k = s_pb + pb_pos(j);              // my bins k = j + 16 q sit 24 q floats further on
-  float *pb_m = s_pb + pb_pos(256 - j);        // their mirror images 256 - k sit 24 q floats back
+  // The column of the second DFT16 that lane j transforms: 0 .. 7, 9 .. 15, 8 (one_hop_exchange()) -- the lane's bins, their
+  // twiddles and their places in the power buffer go by kc; everything in front of the transposition's loads and behind the power
+  // buffer goes by j. kc(0) = 0: lane 0 stays the lane of DC / Nyquist and of bin 128.
+  constexpr bool kOneHop = one_hop_exchange<MP, PLP, DELTA>();
+  const int kc = !kOneHop ? j : (j < 8 ? j : (j == 15 ? 8 : j + 1));
+  float *pb_k = s_pb + pb_pos(kc);             // my bins k = kc + 16 q sit 24 q floats further on
+  float *pb_m = s_pb + pb_pos(256 - kc);       // their mirror images 256 - k sit 24 q floats back
 
   const Dft16K dk;
   PhaseTimer<12> PH;
@@ -567,7 +635,7 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
     // row-wise b64 stores (16-lane groups) and the column-wise b64 loads (32-lane groups)
     // bank-conflict free with immediate offsets only (tools/lds_bank_sim.py).
     float2 *tbw = reinterpret_cast<float2 *>(wbase) + g * 16 + j;
-    const float2 *tbr = reinterpret_cast<const float2 *>(wbase) + g * 16 + j * kTB2Row;
+    const float2 *tbr = reinterpret_cast<const float2 *>(wbase) + g * 16 + kc * kTB2Row;
     {
       // The last layer of the DFT hands out final values group by group -- q = 0 gives k1 = 0, 4, 8, 12 -- so the twiddle
       // product and the ds_write_b64 of an index follow its dft4 at once: the sixteen writes are spread over the last layer and the
@@ -614,28 +682,44 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
     PH(5);                                   // second dft16
 
     // ------------------------------------------------------------ untangle pairs + power
-    // The partner of lane j is lane (16 - j) & 15 of the same row, reached without an LDS round trip: shift the row one
-    // lane down (row_shl:1, lane j <- lane j+1), then row_mirror (lane j <- lane 15 - j). Lane 0 is its own partner one
-    // register up (bin 256 - 16 q = 0 + 16 (16 - q)): its value is parked in lane 15 first (row_ror:15), where the shift
-    // has no source and leaves it. q = 0 of lane 0 is the DC/Nyquist pair, handled below.
-    float zr[8], zi[8];
+    // Bin kc + 16 q pairs with bin 256 - kc - 16 q = (16 - kc) + 16 (15 - q): column 16 - kc, register 15 - q. Under the column
+    // map lanes 1 .. 14 hold columns i and 16 - i in lanes i and 15 - i, so ONE row_mirror per value is the exchange, in place on
+    // re[8 .. 15] / im[8 .. 15] (the owner reads only its registers 0 .. 7 from here on). Lane 15 (column 8) is its own partner in the
+    // same register and keeps what it has. Lane 0 (column 0) is its own partner one register up (bin 256 - 16 q = 0 + 16 (16 - q)):
+    // seven plain moves per component with lane 0 of each row enabled alone; its q = 0 is the DC / Nyquist pair, handled below,
+    // and its own re[8], im[8] make bin 128, taken before the shift.
+    float p128 = 0.0f;
+    if constexpr (kOneHop) {
+      const float a = re[8], b = im[8];
+      p128 = 4.0f * fmaf(b, b, a * a);
+      untangle_partner(re, im);
+    } else {
+      // (the exchange in three dependent DPP steps: instances that hold their registers only so, one_hop_exchange()) shift the row one
+      // lane down (row_shl:1, lane j <- lane j+1), then row_mirror (lane j <- lane 15 - j); lane 0's value is parked in lane 15 first
+      // (row_ror:15), where the shift has no source and leaves it
+      float zr[8], zi[8];
 #pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const float pr = q > 0 ? dpp_f<0x12f>(re[(16 - q) & 15]) : re[15];
-      const float pi = q > 0 ? dpp_f<0x12f>(im[(16 - q) & 15]) : im[15];
-      const float tr = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(pr), __float_as_int(re[15 - q]), 0x101, 0xf, 0xf, false));
-      const float ti = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(pi), __float_as_int(im[15 - q]), 0x101, 0xf, 0xf, false));
-      zr[q] = dpp_f<0x140>(tr);
-      zi[q] = dpp_f<0x140>(ti);
+      for (int q = 0; q < 8; ++q) {
+        const float pr = q > 0 ? dpp_f<0x12f>(re[(16 - q) & 15]) : re[15];
+        const float pi = q > 0 ? dpp_f<0x12f>(im[(16 - q) & 15]) : im[15];
+        const float tr = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(pr), __float_as_int(re[15 - q]), 0x101, 0xf, 0xf, false));
+        const float ti = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(pi), __float_as_int(im[15 - q]), 0x101, 0xf, 0xf, false));
+        zr[q] = dpp_f<0x140>(tr);
+        zi[q] = dpp_f<0x140>(ti);
+      }
+      const float a = re[8], b = im[8];
+      p128 = 4.0f * fmaf(b, b, a * a);
+#pragma unroll
+      for (int q = 0; q < 8; ++q) { re[15 - q] = zr[q]; im[15 - q] = zi[q]; }
     }
     float2 tw5[8];                                // e^{-2 pi i k/512} of my eight bins, all read before the first store to the
 #pragma unroll                                    // power buffer (the compiler cannot tell the two LDS regions apart)
-    for (int q = 0; q < 8; ++q) tw5[q] = s_tw512[j + 16 * q];
+    for (int q = 0; q < 8; ++q) tw5[q] = s_tw512[kc + 16 * q];
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const float2 w = tw5[q];
       const float a = re[q], b = im[q];
-      const float c = zr[q], d = zi[q];
+      const float c = re[15 - q], d = im[15 - q];
       const float sr = a + c, si = b - d, dr = a - c, di = b + d;
       const float ur = fmaf(w.x, dr, -w.y * di);
       const float ui = fmaf(w.x, di, w.y * dr);
@@ -652,9 +736,7 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
       pb_m[-(2 * kOctetFloats) * q] = pm;          // bin 256 - j - 16 q
     }
     if (j == 0) {                                  // k = 128 pairs with itself
-      const float a = re[8], b = im[8];
-      const float s = 4.0f * fmaf(b, b, a * a);
-      s_pb[pb_pos(128)] = USE_POWER ? s : sqrtf(s);
+      s_pb[pb_pos(128)] = USE_POWER ? p128 : sqrtf(p128);
     } else if (j < 8) {
       s_pb[pb_pos(256) + j] = 0.0f;                // octet 32 is read as a whole by the mel units
     }

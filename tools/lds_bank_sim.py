@@ -20,6 +20,10 @@ read two pairs at a time with ds_read_b128: 19 reads per pass at MP = 13 in plac
 j = 0 .. 15 once, so those reads are conflict-free iff a row is an odd number of bank quads long (76 floats at MP = 13, 84 at MP = 16).
 `python tools/lds_bank_sim.py` prints the three ledgers for the bench's instance lld_mfcc512<13, true, true, true, false, 6, true>.
 
+`column_map`: the instances with the one-hop untangle exchange (the kernel's one_hop_exchange(): all but the PLP chain and MP = 16
+with the regression stages fused) deal the columns of the second DFT16 to the lanes by KC = 0 .. 7, 9 .. 15, 8; the transposition's
+loads, the tw512 reads and the power buffer's stores go by it. `tree_layout` carries it; the figures do not move.
+
 The mel units' octets are the host's choice (fast512_build_host orders every lane's units so that the 16 lanes of a frame touch 16
 different bank quads). BENCH_OCTETS is that table for the bench configuration (26 bands, six units per lane), dumped once by the
 library itself: SMILEHIP_DEBUG_TABLES=1 prints it, with the builder's own conflict count, when a plan is created (`library_tables`
@@ -64,6 +68,7 @@ class Layout:
     k_wave: int = K_WAVE
     k_tb2_row: int = None            # None: the module's K_TB2_ROW at the time of the call
     lane_major: bool = False         # the tables of pairs: one row per lane (tw512 | window | tw256), read 16 bytes at a time
+    column_map: bool = False         # lane j transforms column KC[j] of the second DFT16 (the one-hop untangle exchange)
     tab_row: int = None              # floats per lane-major row; None: the smallest odd number of bank quads that holds a row
 
     # ---- the shared tables in front of the per-wave regions (float offsets)
@@ -103,8 +108,13 @@ class Layout:
         return K_TB2_ROW if self.k_tb2_row is None else self.k_tb2_row
 
 
-def tree_layout(mp=MP, uc=UC):
-    return Layout(mp=mp, uc=uc)
+def one_hop_exchange(mp, plp=False, delta=True):
+    """the kernel's rule of the same name: which instances deal the columns by KC"""
+    return not plp and not (mp == 16 and delta)
+
+
+def tree_layout(mp=MP, uc=UC, delta=True):
+    return Layout(mp=mp, uc=uc, column_map=one_hop_exchange(mp, delta=delta))
 
 
 def parent_layout(mp=MP, uc=UC):
@@ -153,6 +163,16 @@ def cost(kind, addr_bytes, active=None):
 
 lane = np.arange(64)
 g, j = lane >> 4, lane & 15
+# The column of the second DFT16 that lane j transforms under the map: 0 .. 7, 9 .. 15, 8 -- lanes i and 15 - i hold the partner
+# columns i and 16 - i (row_mirror), lane 15 the self-paired column 8, lane 0 the self-paired column 0. A permutation of the 16 lanes
+# of a frame group, and every lane group of the instructions it touches (the transposition's ds_read_b64, the tw512 ds_read_b64, the
+# power buffer's ds_write_b32: 32 lanes each) holds whole frame groups: the address multiset of a lane group is the one without the
+# map, so is every figure of the ledger (tests/test_lds_ledger_column_map.py).
+KC = np.where(j < 8, j, np.where(j == 15, 8, j + 1))
+
+
+def column(layout):
+    return KC if layout.column_map else j
 
 
 def wave_base(wave=0, layout=None):
@@ -161,16 +181,16 @@ def wave_base(wave=0, layout=None):
 
 
 def transposition(store_order=TRANSPOSE_ORDER_R8, load_order=TRANSPOSE_ORDER_R8, wave=0, layout=None):
-    """The 16 ds_write_b64 (row k1 of group g: float2 index g*16 + j + k1*65) and the 16 ds_read_b64 (column jj: g*16 + j*65 + jj)
-    in the given issue orders -> (extra cycles of the stores, of the loads, order_independent). `order_independent`: every
+    """The 16 ds_write_b64 (row k1 of group g: float2 index g*16 + j + k1*65) and the 16 ds_read_b64 (column jj: g*16 + kc*65 + jj,
+    kc = the lane's column: j, or KC[j] under the layout's column map) in the given issue orders -> (extra cycles of the stores, of the loads, order_independent). `order_independent`: every
     instruction has the conflict count it has in index order (its addresses do not depend on its position)."""
     assert sorted(store_order) == list(range(16)) and sorted(load_order) == list(range(16))
     layout = layout or tree_layout()
-    wb, row = wave_base(wave, layout), layout.tb2_row
+    wb, row, kc = wave_base(wave, layout), layout.tb2_row, column(layout)
     st = {k1: cost("w64", 4 * wb + 8 * (g * 16 + j + k1 * row)) for k1 in range(16)}
-    ld = {jj: cost("r64", 4 * wb + 8 * (g * 16 + j * row + jj)) for jj in range(16)}
+    ld = {jj: cost("r64", 4 * wb + 8 * (g * 16 + kc * row + jj)) for jj in range(16)}
     st_seq = [cost("w64", 4 * wb + 8 * (g * 16 + j + k1 * row)) for k1 in store_order]
-    ld_seq = [cost("r64", 4 * wb + 8 * (g * 16 + j * row + jj)) for jj in load_order]
+    ld_seq = [cost("r64", 4 * wb + 8 * (g * 16 + kc * row + jj)) for jj in load_order]
     same = st_seq == [st[k] for k in store_order] and ld_seq == [ld[k] for k in load_order]
     return sum(st_seq), sum(ld_seq), same
 
@@ -233,6 +253,7 @@ def ledger(layout=None, wave=0, octets=None, n_mfcc=13, n_bands=26, delta=True):
     L = layout or tree_layout()
     led = Ledger()
     wb = wave_base(wave, L)
+    kc = column(L)                              # the lane's bins kc + 16 q: their twiddles and their places in the power buffer
     lmel = wb + g * L.k_lmel
     pb = wb + 4 * L.k_lmel + g * L.k_pb
     if octets is None:
@@ -264,10 +285,10 @@ def ledger(layout=None, wave=0, octets=None, n_mfcc=13, n_bands=26, delta=True):
             led.add(TW512, "r128", cost("r128", 4 * (L.row * j + 4 * i)))
     else:
         for q in range(8):
-            led.add(TW512, "r64", cost("r64", 4 * (2 * (j + 16 * q))))
+            led.add(TW512, "r64", cost("r64", 4 * (2 * (kc + 16 * q))))
     for q in range(8):
-        led.add(POWER_WRITE, "w32", cost("w32", 4 * (pb + pb_pos(j, L.k_octet) + 2 * L.k_octet * q)))
-        led.add(POWER_WRITE, "w32", cost("w32", 4 * (pb + pb_pos(256 - j, L.k_octet) - 2 * L.k_octet * q)))
+        led.add(POWER_WRITE, "w32", cost("w32", 4 * (pb + pb_pos(kc, L.k_octet) + 2 * L.k_octet * q)))
+        led.add(POWER_WRITE, "w32", cost("w32", 4 * (pb + pb_pos(256 - kc, L.k_octet) - 2 * L.k_octet * q)))
     led.add(POWER_WRITE, "w32", cost("w32", 4 * (pb + pb_pos(128, L.k_octet)), j == 0))                       # bin 128
     led.add(POWER_WRITE, "w32", cost("w32", 4 * (pb + pb_pos(256, L.k_octet) + j), (j > 0) & (j < 8)))        # octet 32's zeros
     for i in range(L.uc):
@@ -306,7 +327,7 @@ def kernel_loop_bounds(src=None):
     out["tw256_reads"] = first + int(m.group(2)) * int(m.group(3))
     out["transpose_write"] = int(m.group(1)) * int(re.search(r"dft16_last\(re, im, q\);\s*#pragma unroll\s*for \(int p = 0; p < (\d+); \+\+p\) \{", src).group(1))
     out["transpose_read"] = int(re.search(r"for \(int jj = 0; jj < (\d+); \+\+jj\) \{\s*// one ds_read_b64 each", src).group(1))
-    out["tw512_reads"] = int(re.search(r"for \(int q = 0; q < (\d+); \+\+q\) tw5\[q\] = s_tw512\[j \+ 16 \* q\];", src).group(1))
+    out["tw512_reads"] = int(re.search(r"for \(int q = 0; q < (\d+); \+\+q\) tw5\[q\] = s_tw512\[kc \+ 16 \* q\];", src).group(1))
     out["mel_reads_per_unit"] = 4 if "const float4 p0 = pp[0], p1 = pp[1];" in src and "w0 = s_melw0[i * 16 + j], w1 = s_melw1[i * 16 + j];" in src else None
     return out
 

@@ -11,6 +11,7 @@
 #define B2(op, k) op " %" #k ", %" #k ", %8\n"
 #define B3(op, k) op " %" #k ", %" #k ", %8, %8\n"
 #define U1(op, k) op " %" #k ", %" #k "\n"
+#define D1(op, k) op " %" #k ", %" #k " row_mirror row_mask:0xf bank_mask:0xf\n"
 #define R8(F, op) F(op, 0) F(op, 1) F(op, 2) F(op, 3) F(op, 4) F(op, 5) F(op, 6) F(op, 7)
 #define F32_OPS "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(c)
 #define F64_OPS "+v"(d0), "+v"(d1), "+v"(d2), "+v"(d3), "+v"(d4), "+v"(d5), "+v"(d6), "+v"(d7) : "v"(dc)
@@ -24,6 +25,8 @@ __global__ void __launch_bounds__(512) k(float *out, int iters) {
   const float c = 1.0001f;
   const double dc = 1.0001;
   const int ic = 3;
+  unsigned long long mask = 0x0001000100010001ull;         // lane 0 of every row
+  asm volatile("" : "+s"(mask));
   for (int i = 0; i < iters; ++i) {
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
@@ -52,6 +55,15 @@ __global__ void __launch_bounds__(512) k(float *out, int iters) {
       if (MODE == 17) asm volatile(R8(B2, "v_fmac_f32") : F32_OPS);
       if (MODE == 18) asm volatile(R8(U1, "v_rcp_f64") : F64_OPS);
       if (MODE == 19) asm volatile(R8(B2, "v_max_f32") : F32_OPS);
+      // the VOP3 select with its lane mask in an SGPR pair (the form the compiler emits wherever the mask is not VCC); the mask is
+      // loop-invariant: no scalar instruction in the measured stream
+      if (MODE == 20)
+        asm volatile("v_cndmask_b32_e64 %0, %0, %8, %9\n v_cndmask_b32_e64 %1, %1, %8, %9\n v_cndmask_b32_e64 %2, %2, %8, %9\n"
+                     "v_cndmask_b32_e64 %3, %3, %8, %9\n v_cndmask_b32_e64 %4, %4, %8, %9\n v_cndmask_b32_e64 %5, %5, %8, %9\n"
+                     "v_cndmask_b32_e64 %6, %6, %8, %9\n v_cndmask_b32_e64 %7, %7, %8, %9\n"
+                     : F32_OPS, "s"(mask));
+      // the untangle exchange's move (lld_mfcc512.hip, untangle_partner): in place, each on a register of its own
+      if (MODE == 21) asm volatile(R8(D1, "v_mov_b32_dpp") : F32_OPS);
     }
   }
   out[blockIdx.x * blockDim.x + threadIdx.x] = a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7 + (float)(d0 + d1 + d2 + d3 + d4 + d5 + d6 + d7) +
@@ -87,7 +99,8 @@ int main() {
   run<3>("v_rcp_f32", "TRANS_F32"); run<4>("v_log_f32", "TRANS_F32"); run<5>("v_sqrt_f32", "TRANS_F32");
   run<6>("v_cvt_f32_i32", "CVT"); run<7>("v_add_u32", "INT32"); run<8>("v_lshlrev_b32", "INT32"); run<9>("v_mul_lo_u32", "INT32");
   run<10>("v_add_f64", "ADD_F64"); run<11>("v_mul_f64", "MUL_F64"); run<12>("v_fma_f64", "FMA_F64"); run<18>("v_rcp_f64", "TRANS_F64");
-  run<13>("v_mov_b32", "other"); run<14>("v_mov_b32_dpp", "other"); run<15>("v_cndmask_b32", "other", true);
+  run<13>("v_mov_b32", "other"); run<14>("v_mov_b32_dpp", "other"); run<15>("v_cndmask_b32", "other");
+  run<20>("v_cndmask_b32_e64_sgpr_mask", "other"); run<21>("v_mov_b32_dpp_row_mirror", "other", true);
   printf("}}\n");
   return 0;
 }

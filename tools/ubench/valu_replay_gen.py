@@ -35,7 +35,7 @@ SRC = os.path.join(ROOT, "opensmile_amd", "csrc", "lld_mfcc512.hip")
 KERNEL = "_ZN8smilehip11lld_mfcc512ILi13ELb1ELb1ELb1ELb0ELi6ELb1EEEvNS_9LldParamsENS_13Fast512TablesE"
 FLAGS = ("--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-slp-vectorize -Xclang -target-feature "
          "-Xclang -load-store-opt --cuda-device-only -gline-tables-only -S").split()
-DFT_LINES = set(range(103, 114)) | set(range(122, 127)) | set(range(144, 164))   # dft4, cmul_ns, dft16_first / _twiddles / _last of lld_mfcc512.hip (innermost inlined location); cmul (115-119) is left
+DFT_LINES = set(range(112, 123)) | set(range(131, 136)) | set(range(153, 173))   # dft4, cmul_ns, dft16_first / _twiddles / _last of lld_mfcc512.hip (innermost inlined location); cmul (124-128) is left
 # in: the line tables cannot tell the 4 cmul inside a dft16 from the 15 twiddle products between the stages, which stay on the vector ALU
 
 
