@@ -187,6 +187,21 @@ typedef struct smilehip_lld_config {
  * cPitchJitter (jitterLocal, shimmerLocalDB), cHarmonics (src/lld/harmonics.cpp:743), the voiced / unvoiced cValbasedSelector
  * gates and cContourSmoother with the graph's end-of-input rules. */
 #define SMILEHIP_CHAIN_EGEMAPS 6
+/* SMILEHIP_CHAIN_PROSODY_SHS: the lld level of config/prosody/prosodyShs.conf ([smo:cContourSmoother] reader.dmLevel = pitch;intens),
+ * 3 columns:
+ *   F0final_sma | voicingFinalUnclipped_sma | pcm_loudness_sma
+ * from the F0 front end of SMILEHIP_CHAIN_COMPARE_F0 on 50 ms frames (gauss window, cTransformFFT, cFFTmagphase, cSpecScale
+ * octave / spline, cPitchShs with nCandidates = 4 and the old peak picker), cPitchSmoother without median filter or octave
+ * correction and with its one-frame-delay post smoothing (src/lldcore/pitchSmoother.cpp:236-425; the file sets postSmoothing = 0
+ * but leaves postSmoothingMethod = simple, and the method string wins, :91-99: no output for the first frame, then the F0 and the
+ * voicing of the frame before, single-frame spikes and octave jumps removed), cIntensity loudness on the UNWINDOWED frame
+ * (src/lldcore/intensity.cpp:125-145, which sums MIN(N, number of outputs) = 1 term) and cContourSmoother
+ * (src/dspcore/contourSmoother.cpp:104-111) with noPostEOIprocessing = 0.
+ * Rows per utterance, as measured against the binary: T - 1 + smaWin / 2 for T >= 2 frames (cPitchSmoother's level holds T - 1
+ * frames and decides; the smoother adds its end-of-input rows), none for fewer. Row n carries the time of frame min(n, T - 2) + 1.
+ * No Viterbi pass, no jitter pass: every kernel of this chain is parallel over frames or rows. smilehip_batch_f0_taps serves it
+ * as well (the energies it returns are those of the 50 ms frame). */
+#define SMILEHIP_CHAIN_PROSODY_SHS 7
 
 #define SMILEHIP_STAGE_WINDOW 1u
 #define SMILEHIP_STAGE_FFT    2u
@@ -249,6 +264,15 @@ void smilehip_config_egemapsv02(smilehip_lld_config *c);
  * v02 graph): GeMAPSv01a.conf and eGeMAPSv01a.conf write column subsets of this level and of its 88 functionals, the same
  * subsets GeMAPSv01b.conf / eGeMAPSv01b.conf take of eGeMAPSv02's */
 void smilehip_config_egemapsv01a(smilehip_lld_config *c);
+/* fills c with config/prosody/prosodyShs.conf (chain_kind = PROSODY_SHS, 3 columns):
+ *   [frame:cFramer] 0.050 / 0.010 s, frameCenterSpecial = left (:30-35); [win:cWindower] gauss, sigma 0.4, gain 1 (:46-51);
+ *   [fft:cTransformFFT] zeroPadSymmetric = 0 (:53-57); [scale:cSpecScale] octave / spline, minF 25, specSmooth = specEnhance =
+ *   auditoryWeighting = 1 (:63-80); [shs:cPitchShs] minPitch 52, maxPitch 620, nCandidates 4, nHarmonics 15, compressionFactor
+ *   0.85, voicingCutoff 0.7, greedyPeakAlgo at its default 0 = shs_old_peak_algo 1 (:82-101, src/lld/pitchShs.cpp:286-302);
+ *   [smooth:cPitchSmoother] medianFilter0 = octaveCorrection = 0, postSmoothing = 0 with postSmoothingMethod = simple (= simple post
+ *   smoothing, pitchSmoother.cpp:91-99), F0final + voicingFinalUnclipped (:103-122);
+ *   [int:cIntensity] loudness 1, intensity 0 on level outp (:37-44); [smo:cContourSmoother] smaWin 3, noPostEOIprocessing 0 (:124-130) */
+void smilehip_config_prosody_shs(smilehip_lld_config *c);
 
 /* F0 group, per component, on an F0 chain plan (smilehip_config_compare16_f0; the plan's spectrum geometry -- n_bins and
  * the level's frameSizeSec, force_fft_frame_size_sec -- must be the input level's):
@@ -262,7 +286,8 @@ int smilehip_specscale_frames(smilehip_plan *plan, const float *d_mag, int64_t l
 int smilehip_pitchshs_frames(smilehip_plan *plan, const float *d_hps, int64_t ld_src, float *d_dst, int64_t ld_dst,
                              int64_t n_frames, void *stream);
 
-/* F0 chain taps (tests / diagnostics): device pointers to the per-frame scratch the last smilehip_lld_run of this
+/* F0 chain taps (tests / diagnostics; SMILEHIP_CHAIN_COMPARE_F0 and SMILEHIP_CHAIN_PROSODY_SHS batches, whose frames are then the
+ * 50 ms ones): device pointers to the per-frame scratch the last smilehip_lld_run of this
  * batch filled -- candidates [total_frames x 21] = level is13_pitchShsG60 (nCandidates | F0Cand[6] | candVoicing[6] |
  * candScores[6] | F0raw | voicingClip), energies [total_frames] = level is13_e60 -- and an optional caller-owned
  * destination [total_frames x n_bins] for level is13_hpsG60 (NULL switches the tap off). */

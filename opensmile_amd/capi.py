@@ -171,6 +171,7 @@ SYMBOLS = {
     "smilehip_config_is09_lld": (None, [C.POINTER(LldConfig)]),
     "smilehip_config_compare16_ab": (None, [C.POINTER(LldConfig)]),
     "smilehip_config_compare16_f0": (None, [C.POINTER(LldConfig)]),
+    "smilehip_config_prosody_shs": (None, [C.POINTER(LldConfig)]),
     "smilehip_config_htk_variant": (C.c_int, [C.POINTER(LldConfig), C.c_char_p]),
     "smilehip_config_compare16": (None, [C.POINTER(LldConfig)]),
     "smilehip_specscale_frames": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp]),
@@ -534,6 +535,13 @@ def compare16_f0_config():
     return c
 
 
+def prosody_shs_config():
+    """config/prosody/prosodyShs.conf (chain_kind = PROSODY_SHS): F0final_sma | voicingFinalUnclipped_sma | pcm_loudness_sma"""
+    c = LldConfig()
+    load().smilehip_config_prosody_shs(C.byref(c))
+    return c
+
+
 def funcspec_compare16(instance):
     """One of ComParE_2016's six cFunctionals instances: "A", "B", "F0", "Nz", "LLD", "Delta"."""
     s = FuncSpec()
@@ -816,7 +824,7 @@ class Batch:
         return out
 
     def f0_run_host_taps(self, pcm):
-        """F0 chain plans: run on host data and also return the intermediate levels
+        """F0 and prosodyShs chain plans: run on host data and also return the intermediate levels
         {hps: total_frames x n_bins, shs: total_frames x 21, e60: total_frames} next to the output matrix."""
         L = load()
         ctx = self.plan.ctx._h
@@ -848,6 +856,12 @@ class Batch:
             L.smilehip_free(ctx, d_out)
             L.smilehip_free(ctx, d_hps)
         return out, taps
+
+    def prosody_shs_run_host(self, pcm, taps=False):
+        """prosodyShs chain plans: the three columns [total_rows x 3] on the host; with taps also the cPitchShs rows of every
+        frame ({shs: total_frames x 21, hps, e60}, through smilehip_batch_f0_taps)."""
+        assert self.plan.geometry.n_out == 3, "not a prosodyShs chain plan"
+        return self.f0_run_host_taps(pcm) if taps else self.run_host(pcm)
 
     def func_rows(self):
         """LLD rows each utterance's functionals summarise (IS09 chain plans)."""

@@ -60,6 +60,8 @@ inline int64_t samples_60ms(double period) { return std::lround(0.060 / period);
 // framer ([is13_frame60]; what both egemapsv02_lldsetE_smo and egemapsv02_lldsetF_smo hold): none if T60 < 4 (ComParE) / < 1 (eGeMAPS).
 inline int64_t layout_rows(const BatchLayoutSpec &s, int64_t len, int64_t T) {
   const bool compare = s.chain_kind == SMILEHIP_CHAIN_COMPARE_AB || s.chain_kind == SMILEHIP_CHAIN_COMPARE;
+  // prosodyShs: cPitchSmoother's level holds T - 1 frames (no output for its first call), the smoother adds its end-of-input rows
+  if (s.chain_kind == SMILEHIP_CHAIN_PROSODY_SHS) return T >= 2 ? T - 1 + s.row_extra : 0;
   if (!compare && s.chain_kind != SMILEHIP_CHAIN_EGEMAPS) return T > 0 ? T + s.row_extra : 0;
   const int64_t T60 = layout_num_frames(len, samples_60ms(s.period), s.H);
   return T60 >= (compare ? 4 : 1) ? T60 + 1 : 0;

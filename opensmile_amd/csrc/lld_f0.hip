@@ -1491,19 +1491,24 @@ hipError_t launch_f0_chunks(const LldParams &P, const F0Params &Q0, hipStream_t 
 }
 }  // namespace
 
+hipError_t launch_f0_frames(const LldParams &P, const F0Params &Q0, hipStream_t s, const F0Pipe *pipe) {
+  if (P.total_frames <= 0) return hipSuccess;
+  if (Q0.n_harm > 17 || !Q0.ab) return hipErrorInvalidValue;
+  switch (f0_logm(Q0)) {
+    case 8: return launch_f0_chunks<8>(P, Q0, s, pipe);
+    case 9: return launch_f0_chunks<9>(P, Q0, s, pipe);
+    case 10: return launch_f0_chunks<10>(P, Q0, s, pipe);
+    case 11: return launch_f0_chunks<11>(P, Q0, s, pipe);
+    default: return hipErrorInvalidValue;                 // 60 ms frames of 8 .. 48 kHz
+  }
+}
+
 hipError_t launch_f0(const LldParams &P, const F0Params &Q0, int max_blocks, float *d_out, int64_t ld_out, hipStream_t s,
                      hipEvent_t frames_done, const F0Pipe *pipe) {
   if (P.total_frames <= 0) return hipSuccess;
   if (Q0.n_harm > 17 || Q0.vit_buf < 2 || Q0.vit_buf > kVBmax || !Q0.ab) return hipErrorInvalidValue;
   (void)max_blocks;
-  hipError_t e;
-  switch (f0_logm(Q0)) {
-    case 8: e = launch_f0_chunks<8>(P, Q0, s, pipe); break;
-    case 9: e = launch_f0_chunks<9>(P, Q0, s, pipe); break;
-    case 10: e = launch_f0_chunks<10>(P, Q0, s, pipe); break;
-    case 11: e = launch_f0_chunks<11>(P, Q0, s, pipe); break;
-    default: return hipErrorInvalidValue;                 // 60 ms frames of 8 .. 48 kHz
-  }
+  hipError_t e = launch_f0_frames(P, Q0, s, pipe);
   if (e != hipSuccess) return e;
   if (frames_done && (e = hipEventRecord(frames_done, s)) != hipSuccess) return e;
   SMILEHIP_KLAUNCH(lld_f0_viterbi, dim3((unsigned)P.n_utt), dim3(64), 0, s, P.frame_off, P.n_utt, Q0, d_out, ld_out);

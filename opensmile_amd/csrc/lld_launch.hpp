@@ -64,6 +64,10 @@ struct F0Pipe {
 };
 hipError_t launch_f0(const LldParams &P, const F0Params &Q, int max_blocks, float *d_out, int64_t ld_out, hipStream_t s,
                      hipEvent_t frames_done = nullptr, const F0Pipe *pipe = nullptr);
+// the three frame kernels alone (chunks, optional pipe): cPitchShs rows into Q.shs, no Viterbi pass (SMILEHIP_CHAIN_PROSODY_SHS)
+hipError_t launch_f0_frames(const LldParams &P, const F0Params &Q, hipStream_t s, const F0Pipe *pipe = nullptr);
+// prosodyShs.conf behind cPitchShs: cPitchSmoother, cIntensity, cContourSmoother over the output rows (lld_prosody.hip)
+hipError_t launch_prosody_tail(const ProsodyParams &R, hipStream_t s);
 int f0_chunk_tiles();
 int f0_tile_frames();
 // cPitchSmootherViterbi as a stream: one frame (or the flush) per launch, state in global memory

@@ -169,6 +169,24 @@ struct F0Params {
   int32_t *jit_ctl;                 // [2], zero between runs: lld_jitter_runs' item counter and count of finished workgroups
 };
 
+// prosodyShs.conf behind cPitchShs (lld_prosody.hip, lld_prosody_ops.hpp): cPitchSmoother + cIntensity + cContourSmoother, one lane per output row
+struct ProsodyParams {
+  const int16_t *pcm;               // packed utterances, or
+  const float *pcm_f32;             //   the same samples as floats (then pcm is not read)
+  const int64_t *samp_off;          // [n_utt+1]
+  const int64_t *frame_off;         // [n_utt+1] frames: rows of shs
+  const int64_t *row_off;           // [n_utt+1] output rows, T - 1 + W per utterance of T >= 2 frames
+  const int32_t *tile_utt, *tile_t0;   // [n_tiles] tiles of chain_tile_rows() output rows: utterance, first row
+  int32_t n_tiles;
+  int32_t H;                        // frame step in samples (frame t starts at sample t * H: frameCenterSpecial = left)
+  const float *shs;                 // [total_frames x 21] cPitchShs rows (F0Params::shs)
+  float voicing_cutoff;             // cPitchShs' voicingCutoff as cPitchSmoother reads it from the level's meta data (pitchSmoother.cpp:177)
+  int32_t W;                        // cContourSmoother smaWin / 2
+  double win0, win_sum;             // cIntensity: the Hamming window's first value and its sum in index order (intensity.cpp:99-104)
+  float *out;                       // [total_rows x ld_out] F0final_sma | voicingFinalUnclipped_sma | pcm_loudness_sma
+  int64_t ld_out;
+};
+
 // eGeMAPSv02 / GeMAPSv01b LLD level (lld_gemaps.hip): per-frame scratch and constants
 struct GemapsParams {
   // ---- 20 ms chain ----

@@ -21,7 +21,7 @@ static BatchLayoutSpec layout_spec(const smilehip_plan *plan) {
   s.fused_delta_eligible = plan->use_fast && mfcc_like(plan) && c.n_delta == 2 && c.delta_win == 2 && !c.append_log_energy && !c.cms &&
                            !getenv("SMILEHIP_NO_FUSED_DELTA");
   s.fast_slots = std::max<int64_t>(1, plan->fast.max_blocks) * 8;
-  s.tile_frames = plan->use_fast ? fast512_tile_frames() : (c.chain_kind == SMILEHIP_CHAIN_COMPARE_F0 ? f0_tile_frames() : (int64_t(1) << 40));
+  s.tile_frames = plan->use_fast ? fast512_tile_frames() : (f0_front_chain(c.chain_kind) ? f0_tile_frames() : (int64_t(1) << 40));
   s.dtile_rows = chain_tile_rows(); s.short_T = chain_short_max(); s.jitter_chunk = jitter_chunk_frames();
   if (const char *rf = getenv("SMILEHIP_RUN_FRAMES")) { const int v = atoi(rf); if (v >= 1 && v <= 4096) s.run_frames_override = v; }   // A/B switch
   return s;
@@ -56,7 +56,8 @@ static int alloc_compare_ab_scratch(smilehip_batch *b, const BatchLayout &L) {
   return SMILEHIP_OK;
 }
 
-static int alloc_f0_scratch(const smilehip_plan *plan, smilehip_batch *b, const BatchLayout &L) {
+// what the F0 front end's frame kernels write and hand to one another: the cPitchShs rows, the frame energies, a chunk of rows
+static int alloc_f0_frame_scratch(const smilehip_plan *plan, smilehip_batch *b) {
   const size_t nf = at_least_one(b->total_frames);
   if (b->d_shs.alloc(nf * 21) || b->d_e60.alloc(nf)) return fail(SMILEHIP_ERR_HIP, "hipMalloc of the F0 scratch matrices failed");
   const size_t nab = (size_t)std::max<int64_t>(f0_scratch_doubles(b->n_tiles, (int)plan->geo.K), 1);
@@ -71,7 +72,12 @@ static int alloc_f0_scratch(const smilehip_plan *plan, smilehip_batch *b, const 
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b / 4 <= nab * sizeof(double) || b->d_f0_ab2.alloc(nab))
       (void)hipGetLastError();                            // (optional: the run goes chunk after chunk without it)
   }
+  return SMILEHIP_OK;
+}
+
+static int alloc_f0_scratch(const smilehip_plan *plan, smilehip_batch *b, const BatchLayout &L) {
   int rc;
+  if ((rc = alloc_f0_frame_scratch(plan, b))) return rc;
   const std::vector<int32_t> zp(at_least_one(b->n_utt), 0);
   if ((rc = b->d_pending.upload(zp)) || (rc = b->d_jit_redo.upload(zp)) || (rc = b->d_jit_utt.upload(L.jit_utt)) ||
       (rc = b->d_jit_t0.upload(L.jit_t0)) || (rc = b->d_jit_ctl.upload(std::vector<int32_t>(2, 0))))
@@ -155,6 +161,7 @@ extern "C" int smilehip_batch_create(smilehip_plan *plan, const int64_t *h_off, 
     case SMILEHIP_CHAIN_IS09: rc = alloc_is09_scratch(b.get(), L); break;
     case SMILEHIP_CHAIN_COMPARE_AB: rc = alloc_compare_ab_scratch(b.get(), L); break;
     case SMILEHIP_CHAIN_COMPARE_F0: rc = alloc_f0_scratch(plan, b.get(), L); break;
+    case SMILEHIP_CHAIN_PROSODY_SHS: rc = alloc_f0_frame_scratch(plan, b.get()); break;   // (no Viterbi, no jitter pass: their vectors stay empty)
     case SMILEHIP_CHAIN_COMPARE: rc = alloc_compare_scratch(plan, b.get(), L); break;
     case SMILEHIP_CHAIN_EGEMAPS: rc = alloc_egemaps_scratch(plan, b.get(), L); break;
     case SMILEHIP_CHAIN_MFCC:
@@ -507,6 +514,22 @@ static void set_jitter_items(const smilehip_batch *fb, F0Params &Q) {
   Q.jit_cap = jitter_wave_capacity(Q.jit_Tw, Q.N, Q.min_pitch, Q.jit_search_range);
 }
 
+// The chunk pipeline of the frame kernels, where the batch holds a second set of rows (SMILEHIP_F0_PIPE=1)
+static int f0_pipe_of(smilehip_plan *plan, smilehip_batch *b, const F0Pipe **pipe) {
+  *pipe = nullptr;
+  if (!b->d_f0_ab2.p || serial_forced()) return SMILEHIP_OK;
+  F0Pipe &fp = plan->f0_pipe;
+  if (!fp.spec) {
+    HIP_TRY(hipStreamCreateWithFlags(&fp.spec, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&fp.sweep, hipStreamNonBlocking));
+    for (hipEvent_t *ev_ : {&fp.start, &fp.spec_done[0], &fp.spec_done[1], &fp.sweep_done[0], &fp.sweep_done[1], &fp.cand_done[0], &fp.cand_done[1]})
+      HIP_TRY(hipEventCreateWithFlags(ev_, hipEventDisableTiming));
+  }
+  fp.ab2 = b->d_f0_ab2.p;
+  *pipe = &fp;
+  return SMILEHIP_OK;
+}
+
 // log_out: rows [F0final, F0finalLog, voicingFinalUnclipped] (the eGeMAPS sub-chain, ld_out >= 3) instead of [F0final, voicing]
 static int f0_run(smilehip_plan *plan, smilehip_batch *b, const int16_t *d_pcm, float *d_out, int64_t ld_out, void *stream,
                   bool log_out = false, hipEvent_t frames_done = nullptr) {
@@ -531,21 +554,62 @@ static int f0_run(smilehip_plan *plan, smilehip_batch *b, const int16_t *d_pcm, 
   int trc;
   if ((trc = timing_mark(plan, 0, (hipStream_t)stream))) return trc;       // (a sub-chain's plan never has timing switched on)
   const F0Pipe *pipe = nullptr;
-  if (b->d_f0_ab2.p && !serial_forced()) {
-    F0Pipe &fp = plan->f0_pipe;
-    if (!fp.spec) {
-      HIP_TRY(hipStreamCreateWithFlags(&fp.spec, hipStreamNonBlocking));
-      HIP_TRY(hipStreamCreateWithFlags(&fp.sweep, hipStreamNonBlocking));
-      for (hipEvent_t *ev_ : {&fp.start, &fp.spec_done[0], &fp.spec_done[1], &fp.sweep_done[0], &fp.sweep_done[1], &fp.cand_done[0], &fp.cand_done[1]})
-        HIP_TRY(hipEventCreateWithFlags(ev_, hipEventDisableTiming));
-    }
-    fp.ab2 = b->d_f0_ab2.p;
-    pipe = &fp;
-  }
+  if ((trc = f0_pipe_of(plan, b, &pipe))) return trc;
   hipError_t e = launch_f0(P, Q, plan->ctx->prop.multiProcessorCount, d_out, ld_out, (hipStream_t)stream, frames_done, pipe);
   if (e != hipSuccess) return fail(SMILEHIP_ERR_HIP, "F0 kernel launch failed: %s", hipGetErrorString(e));
   if ((trc = timing_mark(plan, 1, (hipStream_t)stream))) return trc;
   return timing_mark(plan, 2, (hipStream_t)stream);
+}
+
+// SMILEHIP_CHAIN_PROSODY_SHS: the F0 front end's frame kernels (cPitchShs rows into the batch's scratch), then ONE kernel over the
+// output rows: cPitchSmoother, cIntensity and cContourSmoother (lld_prosody.hip)
+static int prosody_shs_run(smilehip_plan *plan, smilehip_batch *b, const int16_t *d_pcm, float *d_out, int64_t ld_out, void *stream) {
+  if (ld_out < 3) return fail(SMILEHIP_ERR_INVALID, "ld_out %lld < n_out 3", (long long)ld_out);
+  if (plan->cfg.specscale_off & 7)
+    return fail(SMILEHIP_ERR_INVALID, "the fused prosodyShs chain runs cSpecScale with enhancement, smoothing and weighting on (specscale_off is for smilehip_specscale_frames)");
+  if (b->total_frames == 0) return SMILEHIP_OK;
+  if (!d_pcm || !d_out) return fail(SMILEHIP_ERR_INVALID, "smilehip_lld_run: null device pointer");
+  hipStream_t s = (hipStream_t)stream;
+  LldParams P;
+  fill_params(plan, b, d_pcm, d_out, ld_out, P);
+  F0Params Q;
+  fill_f0_params(plan, Q);
+  Q.shs = b->d_shs.p;
+  Q.e60 = b->d_e60.p;
+  Q.ab = b->d_f0_ab.p;
+  Q.ab_rows = f0_scratch_rows(b->n_tiles);
+  Q.hps_tap = b->d_hps_tap;
+  int trc;
+  if ((trc = timing_mark(plan, 0, s))) return trc;
+  const F0Pipe *pipe = nullptr;
+  if ((trc = f0_pipe_of(plan, b, &pipe))) return trc;
+  hipError_t e = launch_f0_frames(P, Q, s, pipe);
+  if (e != hipSuccess) return fail(SMILEHIP_ERR_HIP, "F0 kernel launch failed: %s", hipGetErrorString(e));
+  if ((trc = timing_mark(plan, 1, s))) return trc;
+  ProsodyParams R;
+  std::memset(&R, 0, sizeof(R));
+  R.pcm = d_pcm;
+  R.pcm_f32 = b->run_pcm_f32;
+  R.samp_off = b->d_samp_off.p; R.frame_off = b->d_frame_off.p; R.row_off = b->d_row_off.p;
+  R.tile_utt = b->d_dtile_utt.p; R.tile_t0 = b->d_dtile_t0.p; R.n_tiles = b->n_dtiles;
+  R.H = (int32_t)plan->geo.H;
+  R.shs = b->d_shs.p;
+  R.voicing_cutoff = (float)plan->cfg.voicing_cutoff;
+  R.W = plan->cfg.sma_win / 2;
+  // cIntensity::setupNamesForField (intensity.cpp:91-112): the Hamming window as doubles (smileUtil.c:1291-1303), summed in index order
+  {
+    const double NN = (double)plan->geo.N;
+    double sum = 0.0;
+    for (double i = 0.0; i < NN; i += 1.0) sum += 0.54 - 0.46 * std::cos((2.0 * M_PI * i) / (NN - 1.0));
+    if (sum <= 0.0) sum = 1.0;
+    R.win0 = 0.54 - 0.46 * std::cos((2.0 * M_PI * 0.0) / (NN - 1.0));
+    R.win_sum = sum;
+  }
+  R.out = d_out;
+  R.ld_out = ld_out;
+  e = launch_prosody_tail(R, s);
+  if (e != hipSuccess) return fail(SMILEHIP_ERR_HIP, "prosodyShs tail kernel launch failed: %s", hipGetErrorString(e));
+  return timing_mark(plan, 2, s);
 }
 
 // SMILEHIP_CHAIN_COMPARE: groups A+B into columns 6..64 / 71..129, the 60 ms sub-chain (F0 contour into scratch), then
@@ -714,8 +778,8 @@ extern "C" int smilehip_batch_egemaps_taps(smilehip_batch *b, const float **d_ra
 // (candidates: total_frames x 21, level is13_pitchShsG60; energy: total_frames, level is13_e60) and an optional
 // destination for the octave-scaled spectra (total_frames x K, level is13_hpsG60; pass NULL to switch it off).
 extern "C" int smilehip_batch_f0_taps(smilehip_batch *b, float *d_hps_dst, const float **d_shs, const float **d_e60) {
-  if (!b || b->plan->cfg.chain_kind != SMILEHIP_CHAIN_COMPARE_F0)
-    return fail(SMILEHIP_ERR_INVALID, "smilehip_batch_f0_taps: not an F0 chain batch");
+  if (!b || !f0_front_chain(b->plan->cfg.chain_kind))
+    return fail(SMILEHIP_ERR_INVALID, "smilehip_batch_f0_taps: not an F0 / prosodyShs chain batch");
   b->d_hps_tap = d_hps_dst;
   if (d_shs) *d_shs = b->d_shs.p;
   if (d_e60) *d_e60 = b->d_e60.p;
@@ -787,6 +851,7 @@ extern "C" int smilehip_lld_run(smilehip_plan *plan, smilehip_batch *b, const in
     return smilehip_mfcc_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE_AB) return compare_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE_F0) return f0_run(plan, b, d_pcm, d_out, ld_out, stream);
+  if (plan->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_SHS) return prosody_shs_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE) return compare_full_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_EGEMAPS) return egemaps_run(plan, b, d_pcm, d_out, ld_out, stream);
   return is09_run(plan, b, d_pcm, d_out, ld_out, stream);

@@ -260,6 +260,8 @@ struct smilehip_batch {
 int plan_n_static(const smilehip_plan *p);
 int plan_n_out(const smilehip_plan *p);
 int plan_row_extra(const smilehip_plan *p);
+// chains whose frame kernels are the F0 front end of lld_f0.hip (window .. cPitchShs) on the plan's own framing
+inline bool f0_front_chain(int chain_kind) { return chain_kind == SMILEHIP_CHAIN_COMPARE_F0 || chain_kind == SMILEHIP_CHAIN_PROSODY_SHS; }
 void fill_f0_params(const smilehip_plan *plan, smilehip::F0Params &Q);   // smilehip_batch.cpp
 void gemaps_plan_consts(const smilehip_plan *plan, smilehip::GemapsParams &G);   // smilehip_batch.cpp: constants of an eGeMAPS plan
 

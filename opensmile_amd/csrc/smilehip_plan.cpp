@@ -151,6 +151,18 @@ extern "C" void smilehip_config_egemapsv01a(smilehip_lld_config *c) {
   c->formant_max_freq = 5500.0;      // [gemapsv01a_formantLpc]
 }
 
+// config/prosody/prosodyShs.conf: the F0 front end on 50 ms frames, cPitchSmoother without state, cIntensity loudness, SMA(3)
+extern "C" void smilehip_config_prosody_shs(smilehip_lld_config *c) {
+  smilehip_config_compare16_f0(c);   // [win] gauss 0.4, [scale] minF 25 (specscale_min_f 0), [shs] 52 .. 620 Hz, 15 harmonics, 0.85, cutoff 0.7
+  c->chain_kind = SMILEHIP_CHAIN_PROSODY_SHS;
+  c->frame_size_sec = 0.050;         // [frame:cFramer] frameSize = 0.050, frameStep = 0.010
+  c->zero_pad_symmetric = 0;         // [fft:cTransformFFT]
+  c->shs_n_candidates = 4;           // [shs:cPitchShs] nCandidates = 4
+  c->shs_old_peak_algo = 1;          // ... greedyPeakAlgo not set: 0 (pitchShs.cpp:286-302)
+  c->f0_min_energy = 0.0f;           // (no cValbasedSelector in this file)
+  c->sma_win = 3;                    // [smo:cContourSmoother] smaWin = 3
+}
+
 static inline bool is_compare_ab_like(const smilehip_lld_config &c) {
   return c.chain_kind == SMILEHIP_CHAIN_COMPARE_AB || c.chain_kind == SMILEHIP_CHAIN_COMPARE;
 }
@@ -197,7 +209,9 @@ static int build_tables(smilehip_plan *p, bool upload = true) {
     if (p->cfg.first_mfcc != 0 && p->cfg.first_mfcc != 1) return fail(SMILEHIP_ERR_INVALID, "PLP chain: firstCC must be 0 or 1");
     p->dct.n_mfcc = p->cfg.plp_lp_order + (p->cfg.first_mfcc == 0 ? 1 : 0);   // c1..c_lpOrder [, c0]: outputs of cPlp
     p->dct.melfloor = 1.0f;                              // htkcompatible forces melfloor = 1.0 (plp.cpp:150-160)
-  } else if (p->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE_F0) {
+  } else if (f0_front_chain(p->cfg.chain_kind)) {
+    if (p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_SHS && (p->cfg.sma_win < 3 || !(p->cfg.sma_win & 1) || p->cfg.sma_win > 9))
+      return fail(SMILEHIP_ERR_INVALID, "prosodyShs chain: cContourSmoother smaWin must be odd, 3 .. 9");
     if (mask != SMILEHIP_STAGE_ALL || p->cfg.preemph || p->cfg.n_delta != 0 || p->cfg.win_offset != 0.0)
       return fail(SMILEHIP_ERR_INVALID, "F0 chain: no pre-emphasis / deltas / window offset");
     if (p->geo.Nfft != 512 && p->geo.Nfft != 1024 && p->geo.Nfft != 2048 && p->geo.Nfft != 4096)
@@ -269,7 +283,7 @@ static int build_tables(smilehip_plan *p, bool upload = true) {
   if (p->geo.Nfft >= 64 && (rc = p->oo.build((int)p->geo.Nfft, true))) return rc;
   if (is_plp && ((rc = p->d_plp_eql.upload(plp_eql)) || (rc = p->d_plp_cos.upload(p->h_plp_cos)) || (rc = p->d_plp_sin.upload(plp_sin))))
     return rc;
-  if (p->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE_F0 &&
+  if (f0_front_chain(p->cfg.chain_kind) &&
       ((rc = p->d_f0_rec.upload(p->f0.sp_rec)) || (rc = p->d_f0_d1.upload(p->f0.sp_d1)) || (rc = p->d_f0_d2.upload(p->f0.sp_d2)) ||
        (rc = p->d_f0_co.upload(p->f0.ip_co)) || (rc = p->d_f0_audw.upload(p->f0.audw)) || (rc = p->d_f0_k.upload(p->f0.ip_k)) ||
        (rc = p->d_f0_iprec.upload(p->f0.ip_rec)) || (rc = p->d_f0_swrec.upload(p->f0.sw_rec)) || (rc = p->d_f0_ipcnt.upload(p->f0.ip_cnt))))
@@ -545,13 +559,16 @@ extern "C" void smilehip_plan_destroy(smilehip_plan *plan) { delete plan; }
 
 int plan_n_static(const smilehip_plan *p) {
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE_F0) return 2;
+  if (p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_SHS) return 3;
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE) return 65;
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_EGEMAPS) return 25;
   return p->cfg.chain_kind == SMILEHIP_CHAIN_IS09 ? 16
          : (p->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE_AB ? 59 : p->dct.n_mfcc + (p->cfg.append_log_energy ? 1 : 0));
 }
 int plan_n_out(const smilehip_plan *p) { return plan_n_static(p) * (1 + p->cfg.n_delta); }
-int plan_row_extra(const smilehip_plan *p) { return p->cfg.chain_kind == SMILEHIP_CHAIN_IS09 ? p->cfg.sma_win / 2 : 0; }
+int plan_row_extra(const smilehip_plan *p) {
+  return (p->cfg.chain_kind == SMILEHIP_CHAIN_IS09 || p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_SHS) ? p->cfg.sma_win / 2 : 0;
+}
 
 extern "C" int smilehip_plan_geometry(const smilehip_plan *p, smilehip_geometry *g) {
   if (!p || !g) return fail(SMILEHIP_ERR_INVALID, "smilehip_plan_geometry: null argument");
@@ -580,6 +597,9 @@ extern "C" double smilehip_frame_time(const smilehip_plan *p, int64_t t) {
 
 extern "C" double smilehip_row_time(const smilehip_plan *plan, int64_t n_frames, int64_t row) {
   if (!plan || row < 0) return 0.0;
+  // prosodyShs: the rows carry the time stamps of cPitchSmoother's level, whose frame j has that of input frame j + 1
+  if (plan->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_SHS)
+    return smilehip_frame_time(plan, n_frames >= 2 ? (row < n_frames - 2 ? row : n_frames - 2) + 1 : 0);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_MFCC || plan->cfg.chain_kind == SMILEHIP_CHAIN_PLP ||
       plan->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE_F0 || plan->cfg.chain_kind == SMILEHIP_CHAIN_EGEMAPS || n_frames <= 1)
     return smilehip_frame_time(plan, row);

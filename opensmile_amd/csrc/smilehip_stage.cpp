@@ -549,7 +549,7 @@ static int f0_rows(smilehip_plan *p, int mode, const float *d_src, int64_t ld_sr
                    void *stream, const char *fn) {
   if (!p) return fail(SMILEHIP_ERR_INVALID, "%s: null plan", fn);
   if (!p->ctx) return fail(SMILEHIP_ERR_NO_DEVICE, "host-only plan: no device attached");
-  if (p->cfg.chain_kind != SMILEHIP_CHAIN_COMPARE_F0) return fail(SMILEHIP_ERR_INVALID, "%s: plan is not an F0 chain plan", fn);
+  if (!f0_front_chain(p->cfg.chain_kind)) return fail(SMILEHIP_ERR_INVALID, "%s: plan is not an F0 chain plan", fn);
   int rc = check_frames(d_src, d_dst, ld_src, ld_dst, n_frames, p->geo.K, mode == 1 ? p->geo.K : 21, fn);
   if (rc || n_frames == 0) return rc;
   F0Params Q;

@@ -387,6 +387,9 @@ void conf_apply_f0_params(const ConfPlan &p, smilehip_lld_config &c) {
     else if (kv.first == "jitter_search_range") c.jitter_search_range = kv.second;
     else if (kv.first == "jitter_broken_thresh") c.jitter_broken_thresh = (int32_t)kv.second;
     else if (kv.first == "f0_min_energy") c.f0_min_energy = (float)kv.second;
+    else if (kv.first == "shs_n_candidates") c.shs_n_candidates = (int32_t)kv.second;
+    else if (kv.first == "specscale_min_f") c.specscale_min_f = kv.second;
+    else if (kv.first == "sma_win") c.sma_win = (int32_t)kv.second;
   }
 }
 
@@ -500,6 +503,151 @@ bool conf_check_io(const ConfFile &f, const std::set<std::string> &produced, std
     const std::string *delim = i.find("delimChar");
     if (delim && *delim != ";") { err = "[" + i.name + ":cCsvSink] delimChar = " + *delim + " is not implemented (only ';')"; return false; }
   }
+  return true;
+}
+
+// ---- smilextract_hip --set prosody_shs -C file: config/prosody/prosodyShs.conf, possibly with other values of the options the chain takes as
+// parameters. (Plain -C does not map the file: conf_to_plan is unchanged.) The graph is walked component by
+// component, every option either has the one value SMILEHIP_CHAIN_PROSODY_SHS implements or is one of its parameters (cPitchShs
+// minPitch, maxPitch, voicingCutoff, nHarmonics, compressionFactor, nCandidates; cSpecScale minF; cContourSmoother smaWin)
+// fingerprint of the reference's own file with its includes and every command-line option at its default (--fingerprint prints it)
+static const uint64_t kProsodyShsFingerprint = 0xbb9ed3ae4574db3cull;
+static const std::set<std::string> kProsodyTypes = {"cFramer", "cIntensity", "cWindower", "cTransformFFT", "cFFTmagphase", "cSpecScale",
+                                                    "cPitchShs", "cPitchSmoother", "cContourSmoother"};
+bool conf_to_prosody_shs(const ConfFile &f, ConfPlan &p, std::string &err) {
+  p = ConfPlan();
+  std::map<std::string, const ConfInstance *> one;
+  for (const ConfInstance &i : f.inst) {
+    if (is_io_type(i.type)) continue;
+    if (!kProsodyTypes.count(i.type)) { err = "component [" + i.name + ":" + i.type + "] is not part of the graph of prosodyShs.conf"; return false; }
+    if (one.count(i.type)) { err = "more than one " + i.type + " ([" + i.name + "]): not the graph of prosodyShs.conf"; return false; }
+    one[i.type] = &i;
+  }
+  for (const std::string &t : kProsodyTypes)
+    if (!one.count(t)) { err = "the graph has no " + t + ": not the graph of prosodyShs.conf"; return false; }
+  auto lvl = [](const ConfInstance *i, const char *k) { const std::string *v = i->find(k); return v ? *v : std::string(); };
+  auto wired = [&](const ConfInstance *i, const std::string &want) {
+    if (lvl(i, "reader.dmLevel") == want) return true;
+    err = "[" + i->name + ":" + i->type + "] reader.dmLevel = '" + lvl(i, "reader.dmLevel") + "', expected '" + want + "' (not the wiring of prosodyShs.conf)";
+    return false;
+  };
+  auto must_be = [](OptReader &o, const char *key, const char *want, const char *dflt) {
+    const std::string v = o.str(key, dflt);
+    if (lower(v) != lower(want) && o.err.empty())
+      o.err = "[" + o.ci.name + ":" + o.ci.type + "] " + key + " = " + v + " is not expressible on the fused path (needs " + want + ")";
+  };
+  const ConfInstance *fr = one["cFramer"], *in = one["cIntensity"], *win = one["cWindower"], *fft = one["cTransformFFT"],
+                     *mag = one["cFFTmagphase"], *sc = one["cSpecScale"], *shs = one["cPitchShs"], *sm = one["cPitchSmoother"],
+                     *smo = one["cContourSmoother"];
+  {                                                       // src/core/winToVecProcessor.cpp:51-83
+    OptReader o(*fr);
+    if (!wired(fr, "wave")) return false;
+    o.require("frameSize", 0.05, 0.025); o.require("frameStep", 0.01, 0.0);
+    must_be(o, "frameMode", "fixed", "fixed"); must_be(o, "frameCenterSpecial", "left", "left");
+    o.require("noPostEOIprocessing", 1, 1); o.require("frameSizeFrames", 0, 0); o.require("frameStepFrames", 0, 0);
+    o.require("frameCenter", 0, 0); o.require("frameCenterFrames", 0, 0); o.require("allowLastFrameIncomplete", 0, 0);
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  const std::string frames = lvl(fr, "writer.dmLevel");
+  {                                                       // src/lldcore/intensity.cpp:36-38
+    OptReader o(*in);
+    if (!wired(in, frames)) return false;
+    o.require("intensity", 0, 1); o.require("loudness", 1, 0); o.require("processArrayFields", 1, 1);
+    if (o.has("nameAppend") && !o.str("nameAppend", "").empty()) o.err = "[" + in->name + ":cIntensity] nameAppend is not expressible on the fused path (needs none)";
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  {                                                       // src/dspcore/windower.cpp:36-49
+    OptReader o(*win);
+    if (!wired(win, frames)) return false;
+    const std::string wf = o.str("winFunc", "Han");
+    if (win_func_of(wf) != SMILEHIP_WIN_GAUSS) o.err = "[" + win->name + ":cWindower] winFunc = " + wf + " is not expressible on the fused path (needs gauss)";
+    o.require("gain", 1, 1); o.require("sigma", 0.4, 0.4); o.require("offset", 0, 0);
+    o.require("fade", 0, 0); o.require("squareRoot", 0, 0); o.require("xshift", 0, 0); o.require("processArrayFields", 1, 1);
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  {                                                       // src/dspcore/transformFft.cpp:34-35
+    OptReader o(*fft);
+    if (!wired(fft, lvl(win, "writer.dmLevel"))) return false;
+    o.require("inverse", 0, 0); o.require("zeroPadSymmetric", 0, 1); o.require("processArrayFields", 1, 1);
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  {                                                       // src/dspcore/fftmagphase.cpp:39-49
+    OptReader o(*mag);
+    if (!wired(mag, lvl(fft, "writer.dmLevel"))) return false;
+    o.require("inverse", 0, 0); o.require("magnitude", 1, 1); o.require("phase", 0, 0); o.require("joinMagphase", 0, 0);
+    o.require("normalise", 0, 0); o.require("power", 0, 0); o.require("dBpsd", 0, 0); o.require("processArrayFields", 1, 1);
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  {                                                       // src/dsp/specScale.cpp:44-73
+    OptReader o(*sc);
+    if (!wired(sc, lvl(mag, "writer.dmLevel"))) return false;
+    must_be(o, "scale", "octave", "log"); must_be(o, "sourceScale", "lin", "lin"); must_be(o, "interpMethod", "spline", "spline");
+    const double min_f = o.num("minF", 25.0);
+    if (!(min_f > 0.0) && o.err.empty()) o.err = "[" + sc->name + ":cSpecScale] minF = " + canonical_value(std::to_string(min_f)) + " is not expressible on the fused path (needs > 0)";
+    p.f0_params["specscale_min_f"] = min_f;
+    o.require("maxF", -1, -1); o.require("nPointsTarget", 0, 0); o.require("specSmooth", 1, 0); o.require("specEnhance", 1, 0);
+    o.require("auditoryWeighting", 1, 0); o.require("processArrayFields", 0, 0);
+    o.num("logScaleBase", 2.0); o.num("logSourceScaleBase", 2.0); o.num("firstNote", 55.0);   // (not read with scale = octave, sourceScale = lin)
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  {                                                       // src/lldcore/pitchBase.cpp:41-60, src/lld/pitchShs.cpp:55-62
+    OptReader o(*shs);
+    if (!wired(shs, lvl(sc, "writer.dmLevel"))) return false;
+    p.f0_params["pitch_max"] = o.num("maxPitch", 620.0);
+    p.f0_params["pitch_min"] = o.num("minPitch", 52.0);
+    p.f0_params["voicing_cutoff"] = o.num("voicingCutoff", 0.70);
+    p.f0_params["shs_n_harmonics"] = o.num("nHarmonics", 15);
+    p.f0_params["shs_compression"] = o.num("compressionFactor", 0.85);
+    const double nc = o.num("nCandidates", 3);
+    if ((nc < 1 || nc > 6 || nc != std::floor(nc)) && o.err.empty())
+      o.err = "[" + shs->name + ":cPitchShs] nCandidates = " + canonical_value(std::to_string(nc)) + " is not expressible on the fused path (needs 1 .. 6)";
+    p.f0_params["shs_n_candidates"] = nc;
+    o.require("scores", 1, 1); o.require("voicing", 1, 1); o.require("F0C1", 0, 0); o.require("voicingC1", 0, 0); o.require("F0raw", 1, 0);
+    o.require("voicingClip", 1, 0); o.require("octaveCorrection", 0, 0); o.require("greedyPeakAlgo", 0, 0); o.require("shsSpectrumOutput", 0, 0);
+    o.require("lfCut", 0, 0); o.require("processArrayFields", 0, 0);
+    must_be(o, "inputFieldSearch", "Mag_logScale", "Mag_logScale");
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  {                                                       // src/lldcore/pitchSmoother.cpp:39-57
+    OptReader o(*sm);
+    if (!wired(sm, lvl(shs, "writer.dmLevel"))) return false;
+    o.require("medianFilter0", 0, 0); o.require("postSmoothing", 0, 0); must_be(o, "postSmoothingMethod", "simple", "simple");
+    o.require("octaveCorrection", 0, 1); o.require("F0final", 1, 1); o.require("F0finalEnv", 0, 0); o.require("no0f0", 0, 0);
+    o.require("voicingFinalClipped", 0, 0); o.require("voicingFinalUnclipped", 1, 0); o.require("F0raw", 0, 0); o.require("voicingC1", 0, 0);
+    o.require("voicingClip", 0, 0); o.require("processArrayFields", 0, 0);
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  {                                                       // src/dspcore/contourSmoother.cpp:33-36, src/core/windowProcessor.cpp:39
+    OptReader o(*smo);
+    if (!wired(smo, lvl(sm, "writer.dmLevel") + ";" + lvl(in, "writer.dmLevel"))) return false;
+    const double w = o.num("smaWin", 3);
+    if ((w < 3 || w > 9 || w != std::floor(w) || !((int)w & 1)) && o.err.empty())
+      o.err = "[" + smo->name + ":cContourSmoother] smaWin = " + canonical_value(std::to_string(w)) + " is not expressible on the fused path (needs an odd number, 3 .. 9)";
+    p.f0_params["sma_win"] = w;
+    o.require("noZeroSma", 0, 0); o.require("noPostEOIprocessing", 0, 0);
+    must_be(o, "nameAppend", "sma", "sma");
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  if (lvl(smo, "writer.dmLevel") != "lld") {
+    err = "[" + smo->name + ":cContourSmoother] writer.dmLevel = '" + lvl(smo, "writer.dmLevel") + "', expected 'lld' (the level the shared output file's sinks read)";
+    return false;
+  }
+  if (!conf_check_io(f, {"lld"}, err)) return false;
+  p.preset = "prosody_shs";
+  for (const ConfInstance &i : f.inst)
+    if (i.type == "cWaveSource") { const std::string *fn = i.find("filename"); if (fn) p.wave_file = *fn; }
+  if (conf_fingerprint(f) == kProsodyShsFingerprint) {     // the shipped file: the preset as it is
+    p.f0_params.clear();
+    p.describe = "the graph of prosodyShs.conf (every processing component and option identical)";
+    return true;
+  }
+  std::string what;
+  for (const auto &kv : p.f0_params) {
+    char buf[64];
+    snprintf(buf, sizeof(buf), "%s%s = %.9g", what.empty() ? "" : ", ", kv.first.c_str(), kv.second);
+    what += buf;
+  }
+  p.describe = "the graph of prosodyShs.conf with the file's own parameter values (" + what + ")";
   return true;
 }
 

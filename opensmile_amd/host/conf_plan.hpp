@@ -65,7 +65,7 @@ struct ConfPlan {
   std::string wave_file;                 // the wave source's filename option, command-line options applied
   // big sets recognised through the masked fingerprint: the values of the parameter options the file sets, keyed by the
   // smilehip_lld_config field they map to (pitch_min, pitch_max, voicing_cutoff, shs_n_harmonics, shs_compression,
-  // vit_buffer_len, jitter_search_range, jitter_broken_thresh, f0_min_energy)
+  // vit_buffer_len, jitter_search_range, jitter_broken_thresh, f0_min_energy; conf_to_prosody_shs: see there)
   std::map<std::string, double> f0_params;
   // ComParE graphs recognised through the second masked fingerprint: lastMfcc (0 = as shipped: 14) and, per cFunctionals
   // instance ("A", "B", "F0", "Nz", "LLD", "Delta"), the family names the file enables (absent = as shipped)
@@ -76,6 +76,12 @@ void conf_apply_f0_params(const ConfPlan &p, smilehip_lld_config &cfg);
 
 // false + err: the graph (component, option) the fused path cannot express
 bool conf_to_plan(const ConfFile &f, ConfPlan &p, std::string &err);
+// smilextract_hip --set prosody_shs -C file: the file must be the graph of config/prosody/prosodyShs.conf; preset = "prosody_shs", and
+// unless it is the shipped file itself f0_params holds its values of the options the chain takes as parameters (cPitchShs minPitch,
+// maxPitch, voicingCutoff, nHarmonics, compressionFactor, nCandidates; cSpecScale minF; cContourSmoother smaWin: pitch_min, pitch_max,
+// voicing_cutoff, shs_n_harmonics, shs_compression, shs_n_candidates, specscale_min_f, sma_win). Any other component, wiring or option
+// value is refused with its name in err. conf_to_plan itself does not map that file.
+bool conf_to_prosody_shs(const ConfFile &f, ConfPlan &p, std::string &err);
 
 // Sources and sinks are outside the fingerprint and the plan: this checks them. Every cWaveSource must read the whole file
 // (start 0, end -1, no sample-based range, a RIFF header), every ACTIVE sink (filename other than "?") must be one

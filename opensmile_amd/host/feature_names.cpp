@@ -33,6 +33,10 @@ std::vector<std::string> lld_names_htk_variant(bool plp, bool energy) {
   return n;
 }
 
+// config/prosody/prosodyShs.conf, level lld: cPitchSmoother's two outputs and cIntensity's "<input>_loudness" (copyInputName = 1 on
+// the framer's "pcm" field), each with cContourSmoother's nameAppend = sma
+std::vector<std::string> lld_names_prosody_shs() { return {"F0final_sma", "voicingFinalUnclipped_sma", "pcm_loudness_sma"}; }
+
 std::vector<std::string> lld_names_is09() {
   std::vector<std::string> n;
   for (const char *suffix : {"_sma", "_sma_de"}) {
