@@ -168,6 +168,12 @@ typedef struct smilehip_lld_config {
    * shipped F0 chains set): 1 = specEnhance 0, 2 = specSmooth 0, 4 = auditoryWeighting 0 (src/dsp/specScale.cpp:326-353; without the
    * weighting the spline's values pass as they are, negative ones too) -- emobase2010, IS10_paraling_compat */
   int32_t  specscale_off;
+  /* SMILEHIP_CHAIN_PROSODY_ACF: usePower of the cepstrum's cAcf instance (src/dspcore/acf.cpp:91-102, :252-305): 0 = the cepstrum
+   * is the inverse transform of log(mag + 1), what [cep:cAcf] of prosodyAcf.conf gets by not setting the option; 1 = of
+   * log(mag^2 + 1) (IS09_emotion.conf sets it; SMILEHIP_CHAIN_IS09 always runs that form and does not read this field).
+   * Appended last, in what was the struct's tail padding: struct_size is what it was, and a caller built before this field
+   * existed, whose struct the presets zero first, passes 0. Only SMILEHIP_CHAIN_PROSODY_ACF reads it. */
+  int32_t  acf_cep_use_power;
 } smilehip_lld_config;
 
 #define SMILEHIP_CHAIN_MFCC 0
@@ -202,6 +208,20 @@ typedef struct smilehip_lld_config {
  * No Viterbi pass, no jitter pass: every kernel of this chain is parallel over frames or rows. smilehip_batch_f0_taps serves it
  * as well (the energies it returns are those of the 50 ms frame). */
 #define SMILEHIP_CHAIN_PROSODY_SHS 7
+/* SMILEHIP_CHAIN_PROSODY_ACF: the lld level of config/prosody/prosodyAcf.conf ([smo:cContourSmoother] reader.dmLevel = pitch;intens),
+ * 3 columns in the binary's order (cPitchACF::setupNewNames, src/lldcore/pitchACF.cpp:111-132, then intens):
+ *   voiceProb_sma | F0_sma | pcm_loudness_sma
+ * on 50 ms frames every 10 ms: gauss window, cTransformFFT, cFFTmagphase, cAcf twice (ACF of the power spectrum; cepstrum of
+ * log(mag + 1), acf_cep_use_power = 0: src/dspcore/acf.cpp:252-345), cPitchACF (voicing probability and first cepstral peak,
+ * pitchACF.cpp:137-192 with Tsamp = (float)frameSizeSec / Nfft, :113-116, :151-153; the causal contour, :197-237, state per
+ * utterance), cIntensity loudness on the UNWINDOWED frame (src/lldcore/intensity.cpp:125-145, which sums MIN(N, number of
+ * outputs) = 1 term) and cContourSmoother (src/dspcore/contourSmoother.cpp:104-111) with noPostEOIprocessing = 0.
+ * Rows per utterance, as measured against the binary: T + smaWin / 2 for T >= 1 frames, none for T = 0 (SMILEHIP_CHAIN_IS09's
+ * rule: both levels the smoother reads hold T frames). Row n carries the time of frame min(n, T - 1); the second row of a
+ * one-frame utterance that of frame 1. One frame kernel (lld_acf_pitch_frame: a wave per frame for transforms of 512 / 1024
+ * points, a workgroup per frame otherwise), one thread per utterance for the contour, the window-chain kernel for the smoother.
+ * smilehip_batch_prosody_acf_taps returns the levels in front of the smoother. */
+#define SMILEHIP_CHAIN_PROSODY_ACF 8
 
 #define SMILEHIP_STAGE_WINDOW 1u
 #define SMILEHIP_STAGE_FFT    2u
@@ -273,6 +293,13 @@ void smilehip_config_egemapsv01a(smilehip_lld_config *c);
  *   smoothing, pitchSmoother.cpp:91-99), F0final + voicingFinalUnclipped (:103-122);
  *   [int:cIntensity] loudness 1, intensity 0 on level outp (:37-44); [smo:cContourSmoother] smaWin 3, noPostEOIprocessing 0 (:124-130) */
 void smilehip_config_prosody_shs(smilehip_lld_config *c);
+/* fills c with config/prosody/prosodyAcf.conf (chain_kind = PROSODY_ACF, 3 columns):
+ *   [frame:cFramer] 0.050 / 0.010 s, frameCenterSpecial = left (:31-36); [int:cIntensity] loudness 1, intensity 0 on level outp
+ *   (:38-45); [win:cWindower] gauss, sigma 0.4, gain 1 (:47-52); [fft:cTransformFFT] zeroPadSymmetric = 0 (:54-58);
+ *   [fftmp:cFFTmagphase] magnitudes (:60-62); [acf:cAcf] the defaults: usePower 1 (:64-66); [cep:cAcf] cepstrum = 1 and usePower at
+ *   its default 0 = acf_cep_use_power 0 (:68-71, acf.cpp:91-102); [pitch:cPitchACF] maxPitch 500, voicingCutoff 0.55, voiceProb +
+ *   F0 (:73-86); [smo:cContourSmoother] smaWin 3, noPostEOIprocessing 0 (:88-94) */
+void smilehip_config_prosody_acf(smilehip_lld_config *c);
 
 /* F0 group, per component, on an F0 chain plan (smilehip_config_compare16_f0; the plan's spectrum geometry -- n_bins and
  * the level's frameSizeSec, force_fft_frame_size_sec -- must be the input level's):
@@ -292,6 +319,10 @@ int smilehip_pitchshs_frames(smilehip_plan *plan, const float *d_hps, int64_t ld
  * candScores[6] | F0raw | voicingClip), energies [total_frames] = level is13_e60 -- and an optional caller-owned
  * destination [total_frames x n_bins] for level is13_hpsG60 (NULL switches the tap off). */
 int smilehip_batch_f0_taps(smilehip_batch *b, float *d_hps_dst, const float **d_shs, const float **d_e60);
+/* prosodyAcf chain tap (tests / diagnostics; SMILEHIP_CHAIN_PROSODY_ACF batches): device pointer to the per-frame scratch the last
+ * smilehip_lld_run of this batch filled, [total_frames x 3] = voiceProb | F0 (the contour) | pcm_loudness: the levels `pitch` and
+ * `intens` in front of the smoother. n_frames (optional) receives total_frames. */
+int smilehip_batch_prosody_acf_taps(smilehip_batch *batch, float **d_raw3, int64_t *n_frames);
 /* Frames per utterance that cPitchSmootherViterbi had not decided when the input ended (they are flushed at the end of input:
  * src/lld/pitchSmootherViterbi.cpp:451-570), [n_utt] device ints filled by the last smilehip_lld_run of an F0 / ComParE / eGeMAPS
  * chain batch. Every end-of-input rule of the smoothed levels and the row counts the F0-group functionals see follow from it. */

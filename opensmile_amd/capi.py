@@ -44,6 +44,7 @@ class LldConfig(C.Structure):
         ("f0_min_energy", C.c_float), ("append_log_energy", C.c_int32), ("cms", C.c_int32), ("jitter_broken_thresh", C.c_int32),
         ("vit_buffer_len", C.c_int32), ("jitter_search_range", C.c_double), ("formant_max_freq", C.c_double), ("specscale_min_f", C.c_double), ("shs_n_candidates", C.c_int32), ("shs_old_peak_algo", C.c_int32),
         ("spectral_band_lo", C.c_int32 * 2), ("spectral_band_hi", C.c_int32 * 2), ("specscale_off", C.c_int32),
+        ("acf_cep_use_power", C.c_int32),
     ]
 
 
@@ -172,6 +173,8 @@ SYMBOLS = {
     "smilehip_config_compare16_ab": (None, [C.POINTER(LldConfig)]),
     "smilehip_config_compare16_f0": (None, [C.POINTER(LldConfig)]),
     "smilehip_config_prosody_shs": (None, [C.POINTER(LldConfig)]),
+    "smilehip_config_prosody_acf": (None, [C.POINTER(LldConfig)]),
+    "smilehip_batch_prosody_acf_taps": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
     "smilehip_config_htk_variant": (C.c_int, [C.POINTER(LldConfig), C.c_char_p]),
     "smilehip_config_compare16": (None, [C.POINTER(LldConfig)]),
     "smilehip_specscale_frames": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp]),
@@ -542,6 +545,16 @@ def prosody_shs_config():
     return c
 
 
+CHAIN_PROSODY_ACF = 8
+
+
+def prosody_acf_config():
+    """config/prosody/prosodyAcf.conf (chain_kind = PROSODY_ACF): voiceProb_sma | F0_sma | pcm_loudness_sma"""
+    c = LldConfig()
+    load().smilehip_config_prosody_acf(C.byref(c))
+    return c
+
+
 def funcspec_compare16(instance):
     """One of ComParE_2016's six cFunctionals instances: "A", "B", "F0", "Nz", "LLD", "Delta"."""
     s = FuncSpec()
@@ -862,6 +875,39 @@ class Batch:
         frame ({shs: total_frames x 21, hps, e60}, through smilehip_batch_f0_taps)."""
         assert self.plan.geometry.n_out == 3, "not a prosodyShs chain plan"
         return self.f0_run_host_taps(pcm) if taps else self.run_host(pcm)
+
+    def prosody_acf_run_host(self, pcm, ld_out=3, fill=0.0, runs=1):
+        """prosodyAcf chain plans: run on host data (int16 samples through smilehip_lld_run, a float32 array through
+        smilehip_lld_run_f32) into a matrix [total_rows x ld_out] that held `fill` everywhere before, `runs` times over.
+        Returns it and the tap [total_frames x 3] = voiceProb | F0 | pcm_loudness (smilehip_batch_prosody_acf_taps)."""
+        L = load()
+        ctx = self.plan.ctx._h
+        f32 = np.asarray(pcm).dtype == np.float32
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32 if f32 else np.int16)
+        out = np.full((self.total_rows, ld_out), fill, np.float32)
+        tap = np.zeros((self.total_frames, 3), np.float32)
+        d_pcm, d_out = _vp(), _vp()
+        _check(L.smilehip_alloc(ctx, max(pcm.nbytes, 4), C.byref(d_pcm)))
+        _check(L.smilehip_alloc(ctx, max(out.nbytes, 4), C.byref(d_out)))
+        try:
+            if pcm.nbytes:
+                _check(L.smilehip_copy_to_device(ctx, d_pcm, pcm.ctypes.data, pcm.nbytes, None))
+            if out.nbytes:
+                _check(L.smilehip_copy_to_device(ctx, d_out, out.ctypes.data, out.nbytes, None))
+            for _ in range(runs):
+                _check((L.smilehip_lld_run_f32 if f32 else L.smilehip_lld_run)(self.plan._h, self._h, d_pcm, d_out, ld_out, None))
+            _check(L.smilehip_stream_synchronize(ctx, None))
+            d_raw3, nf = _vp(), _i64(0)
+            _check(L.smilehip_batch_prosody_acf_taps(self._h, C.byref(d_raw3), C.byref(nf)))
+            assert nf.value == self.total_frames
+            if out.nbytes:
+                _check(L.smilehip_copy_to_host(ctx, out.ctypes.data, d_out, out.nbytes, None))
+            if tap.nbytes:
+                _check(L.smilehip_copy_to_host(ctx, tap.ctypes.data, d_raw3, tap.nbytes, None))
+        finally:
+            L.smilehip_free(ctx, d_pcm)
+            L.smilehip_free(ctx, d_out)
+        return out, tap
 
     def func_rows(self):
         """LLD rows each utterance's functionals summarise (IS09 chain plans)."""

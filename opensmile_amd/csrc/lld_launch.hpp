@@ -68,6 +68,10 @@ hipError_t launch_f0(const LldParams &P, const F0Params &Q, int max_blocks, floa
 hipError_t launch_f0_frames(const LldParams &P, const F0Params &Q, hipStream_t s, const F0Pipe *pipe = nullptr);
 // prosodyShs.conf behind cPitchShs: cPitchSmoother, cIntensity, cContourSmoother over the output rows (lld_prosody.hip)
 hipError_t launch_prosody_tail(const ProsodyParams &R, hipStream_t s);
+// prosodyAcf.conf: lld_acf_pitch_frame (wave per frame for Nfft 512 / 1024, workgroup per frame otherwise) into Q.raw3, then
+// cPitchACF's contour in place on its pitch column (lld_prosody_acf.hip). P.frame_utt is required.
+hipError_t launch_prosody_acf(const LldParams &P, const ProsodyAcfParams &Q, hipStream_t s);
+int prosody_acf_wave_frames();      // frames per workgroup of the wave form
 int f0_chunk_tiles();
 int f0_tile_frames();
 // cPitchSmootherViterbi as a stream: one frame (or the flush) per launch, state in global memory

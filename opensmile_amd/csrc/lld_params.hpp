@@ -187,6 +187,17 @@ struct ProsodyParams {
   int64_t ld_out;
 };
 
+// prosodyAcf.conf (lld_prosody_acf.hip, lld_prosody_acf_ops.hpp): extra parameters of lld_acf_pitch_frame next to LldParams
+// (batch, geometry, window, transform tables; nothing of the mel / DCT part is read)
+struct ProsodyAcfParams {
+  float *raw3;                      // [total_frames x 3] voiceProb | cut-off pitch candidate (the contour's input, smoothed in place) | loudness
+  float fsSec;                      // (float) frameSizeSec of the ACF level (pitchACF.cpp:113-116)
+  int32_t cep_use_power;            // [cep:cAcf] usePower: log(mag^2 + 1) if set, log(mag + 1) otherwise (acf.cpp:252-305)
+  double maxPitch;
+  double voicingCutoff;             // clamped to [0, 1] (pitchACF.cpp:96-98)
+  double win0, win_sum;             // cIntensity: the Hamming window's first value and its sum in index order (intensity.cpp:99-104)
+};
+
 // eGeMAPSv02 / GeMAPSv01b LLD level (lld_gemaps.hip): per-frame scratch and constants
 struct GemapsParams {
   // ---- 20 ms chain ----

@@ -11,8 +11,9 @@
 //   * the emitted F0 is the mean of the two previous tracked values (the previous one alone while either is zero), i.e.
 //     the contour runs one to two frames behind.
 // All arithmetic in float, in the reference's order: the outputs are the binary's bits.
+// __host__ __device__ (GLF_HD): tests/test_prosody_acf_host.py compiles it with g++ and holds it to the binary's contour.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "glibc_float.hpp"
 
 namespace smilehip {
 
@@ -24,7 +25,7 @@ struct PitchContour {
 static_assert(sizeof(PitchContour) == 32, "smilehip_pitchacf_contour_step's d_state is 8 words");
 
 // returns the contour value the reference emits for this frame; S.env follows it (F0env, :236-240)
-__device__ __forceinline__ float pitch_contour_step(PitchContour &S, float p) {
+GLF_HD float pitch_contour_step(PitchContour &S, float p) {
   const bool was = S.last > 0.0f, now = p > 0.0f;
   if (was == now) S.edge = 0;
   else if (now) S.edge = 1;

@@ -45,6 +45,14 @@ static int alloc_is09_scratch(smilehip_batch *b, const BatchLayout &L) {
   return SMILEHIP_OK;
 }
 
+// prosodyAcf: the utterance of every frame, and three floats per frame (voiceProb | pitch candidate, then contour | loudness)
+static int alloc_prosody_acf_scratch(smilehip_batch *b, const BatchLayout &L) {
+  int rc;
+  if (b->total_frames > 0 && (rc = b->d_frame_utt.upload(L.frame_utt))) return rc;
+  if (b->d_raw3.alloc(at_least_one(b->total_frames) * 3)) return fail(SMILEHIP_ERR_HIP, "hipMalloc of the prosodyAcf scratch matrix failed");
+  return SMILEHIP_OK;
+}
+
 static int alloc_compare_ab_scratch(smilehip_batch *b, const BatchLayout &L) {
   int rc;
   b->n_runs = (int32_t)L.run_utt.size();
@@ -162,6 +170,7 @@ extern "C" int smilehip_batch_create(smilehip_plan *plan, const int64_t *h_off, 
     case SMILEHIP_CHAIN_COMPARE_AB: rc = alloc_compare_ab_scratch(b.get(), L); break;
     case SMILEHIP_CHAIN_COMPARE_F0: rc = alloc_f0_scratch(plan, b.get(), L); break;
     case SMILEHIP_CHAIN_PROSODY_SHS: rc = alloc_f0_frame_scratch(plan, b.get()); break;   // (no Viterbi, no jitter pass: their vectors stay empty)
+    case SMILEHIP_CHAIN_PROSODY_ACF: rc = alloc_prosody_acf_scratch(b.get(), L); break;
     case SMILEHIP_CHAIN_COMPARE: rc = alloc_compare_scratch(plan, b.get(), L); break;
     case SMILEHIP_CHAIN_EGEMAPS: rc = alloc_egemaps_scratch(plan, b.get(), L); break;
     case SMILEHIP_CHAIN_MFCC:
@@ -413,6 +422,49 @@ static int is09_run(smilehip_plan *plan, smilehip_batch *b, const int16_t *d_pcm
   Q.kind[1] = 0; Q.W[1] = plan->cfg.delta_win;            // cDeltaRegression
   Q.out_col[0] = 0;
   Q.out_col[1] = 16;
+  e = launch_chain(Q, s);
+  if (e != hipSuccess) return fail(SMILEHIP_ERR_HIP, "window-chain kernel launch failed: %s", hipGetErrorString(e));
+  return timing_mark(plan, 2, s);
+}
+
+// SMILEHIP_CHAIN_PROSODY_ACF: lld_acf_pitch_frame (voicing, pitch candidate, loudness per frame) -> cPitchACF's contour per
+// utterance -> cContourSmoother as one SMA stage of the window chain over the scratch's three columns
+static int prosody_acf_run(smilehip_plan *plan, smilehip_batch *b, const int16_t *d_pcm, float *d_out, int64_t ld_out, void *stream) {
+  if (ld_out < 3) return fail(SMILEHIP_ERR_INVALID, "ld_out %lld < n_out 3", (long long)ld_out);
+  if (b->total_frames == 0) return SMILEHIP_OK;
+  if (!d_pcm || !d_out) return fail(SMILEHIP_ERR_INVALID, "smilehip_lld_run: null device pointer");
+  hipStream_t s = (hipStream_t)stream;
+  LldParams P;
+  fill_params(plan, b, d_pcm, d_out, ld_out, P);
+  ProsodyAcfParams A;
+  std::memset(&A, 0, sizeof(A));
+  A.raw3 = b->d_raw3.p;
+  A.fsSec = (float)plan->geo.fft_frame_size_sec;          // the level's frameSizeSec: Tsamp = fsSec / Nfft (pitchACF.cpp:113-116, :151-153)
+  A.cep_use_power = plan->cfg.acf_cep_use_power;
+  A.maxPitch = plan->cfg.pitch_max;
+  A.voicingCutoff = plan->cfg.voicing_cutoff;
+  if (A.voicingCutoff > 1.0) A.voicingCutoff = 1.0;       // pitchACF.cpp:96-98
+  if (A.voicingCutoff < 0.0) A.voicingCutoff = 0.0;
+  if (A.maxPitch < 0.0) A.maxPitch = 0.0;
+  // cIntensity::setupNamesForField (intensity.cpp:91-112): the Hamming window as doubles (smileUtil.c:1291-1303), summed in index order
+  {
+    const double NN = (double)plan->geo.N;
+    double sum = 0.0;
+    for (double i = 0.0; i < NN; i += 1.0) sum += 0.54 - 0.46 * std::cos((2.0 * M_PI * i) / (NN - 1.0));
+    if (sum <= 0.0) sum = 1.0;
+    A.win0 = 0.54 - 0.46 * std::cos((2.0 * M_PI * 0.0) / (NN - 1.0));
+    A.win_sum = sum;
+  }
+  int trc;
+  if ((trc = timing_mark(plan, 0, s))) return trc;
+  hipError_t e = launch_prosody_acf(P, A, s);
+  if (e != hipSuccess) return fail(SMILEHIP_ERR_HIP, "prosodyAcf kernel launch failed: %s", hipGetErrorString(e));
+  if ((trc = timing_mark(plan, 1, s))) return trc;
+  ChainParams Q = chain_params(b, b->d_raw3.p, 3, 3, d_out, ld_out);
+  Q.copy_col = -1;
+  Q.n_stages = 1;
+  Q.kind[0] = 1; Q.W[0] = plan->cfg.sma_win / 2;          // cContourSmoother
+  Q.out_col[0] = 0;
   e = launch_chain(Q, s);
   if (e != hipSuccess) return fail(SMILEHIP_ERR_HIP, "window-chain kernel launch failed: %s", hipGetErrorString(e));
   return timing_mark(plan, 2, s);
@@ -774,6 +826,15 @@ extern "C" int smilehip_batch_egemaps_taps(smilehip_batch *b, const float **d_ra
   return SMILEHIP_OK;
 }
 
+// prosodyAcf chain tap: the per-frame scratch of the last run, [total_frames x 3] = voiceProb | F0 (contour) | pcm_loudness
+extern "C" int smilehip_batch_prosody_acf_taps(smilehip_batch *b, float **d_raw3, int64_t *n_frames) {
+  if (!b || b->plan->cfg.chain_kind != SMILEHIP_CHAIN_PROSODY_ACF)
+    return fail(SMILEHIP_ERR_INVALID, "smilehip_batch_prosody_acf_taps: not a prosodyAcf chain batch");
+  if (d_raw3) *d_raw3 = b->d_raw3.p;
+  if (n_frames) *n_frames = b->total_frames;
+  return SMILEHIP_OK;
+}
+
 // Test/diagnostic taps of the F0 chain: device pointers to the per-frame scratch of the LAST run
 // (candidates: total_frames x 21, level is13_pitchShsG60; energy: total_frames, level is13_e60) and an optional
 // destination for the octave-scaled spectra (total_frames x K, level is13_hpsG60; pass NULL to switch it off).
@@ -852,6 +913,7 @@ extern "C" int smilehip_lld_run(smilehip_plan *plan, smilehip_batch *b, const in
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE_AB) return compare_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE_F0) return f0_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_SHS) return prosody_shs_run(plan, b, d_pcm, d_out, ld_out, stream);
+  if (plan->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_ACF) return prosody_acf_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE) return compare_full_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_EGEMAPS) return egemaps_run(plan, b, d_pcm, d_out, ld_out, stream);
   return is09_run(plan, b, d_pcm, d_out, ld_out, stream);

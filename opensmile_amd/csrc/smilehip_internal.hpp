@@ -244,7 +244,8 @@ struct smilehip_batch {
   int32_t run_frames = 8;               // frames per run (compare_run_frames)
   std::vector<int32_t> h_short;
   DevBuf<int64_t> d_samp_off, d_frame_off;
-  DevBuf<int32_t> d_frame_utt;     // IS09 chain: utterance of every frame (the frame kernel has one frame per wave and would search frame_off for it)
+  DevBuf<float> d_raw3;            // prosodyAcf chain: [total_frames x 3] voiceProb | pitch candidate -> contour | loudness
+  DevBuf<int32_t> d_frame_utt;     // IS09 / prosodyAcf chain: utterance of every frame (the frame kernel has one frame per wave and would search frame_off for it)
   DevBuf<int32_t> d_tile_utt, d_tile_t0, d_short, d_dtile_utt, d_dtile_t0;
   DevBuf<TileRec> d_tile_rec;
   DevBuf<FTileRec> d_ftile_rec;  // tiles of the delta-fused fast kernel (MFCC / PLP chain with two regression stages of window 2)

@@ -163,6 +163,22 @@ extern "C" void smilehip_config_prosody_shs(smilehip_lld_config *c) {
   c->sma_win = 3;                    // [smo:cContourSmoother] smaWin = 3
 }
 
+// config/prosody/prosodyAcf.conf: ACF / cepstrum pitch on 50 ms gauss-windowed frames, cIntensity loudness, SMA(3)
+extern "C" void smilehip_config_prosody_acf(smilehip_lld_config *c) {
+  smilehip_config_mfcc12_0_d_a(c);   // (the mel / DCT fields are not read by this chain)
+  c->chain_kind = SMILEHIP_CHAIN_PROSODY_ACF;
+  c->frame_size_sec = 0.050;         // [frame:cFramer] frameSize = 0.050, frameStep = 0.010
+  c->preemph = 0;
+  c->win_func = SMILEHIP_WIN_GAUSS;  // [win:cWindower] winFunc = gauss, sigma = 0.4, gain = 1
+  c->win_sigma = 0.4;
+  c->zero_pad_symmetric = 0;         // [fft:cTransformFFT]
+  c->n_delta = 0;
+  c->pitch_max = 500.0;              // [pitch:cPitchACF] maxPitch = 500, voicingCutoff = 0.55
+  c->voicing_cutoff = 0.55;
+  c->acf_cep_use_power = 0;          // [cep:cAcf] sets cepstrum = 1 only: usePower stays 0 (acf.cpp:91-102)
+  c->sma_win = 3;                    // [smo:cContourSmoother] smaWin = 3
+}
+
 static inline bool is_compare_ab_like(const smilehip_lld_config &c) {
   return c.chain_kind == SMILEHIP_CHAIN_COMPARE_AB || c.chain_kind == SMILEHIP_CHAIN_COMPARE;
 }
@@ -173,16 +189,18 @@ static int build_tables(smilehip_plan *p, bool upload = true) {
   if ((rc = make_geometry(p->cfg, p->geo)) != SMILEHIP_OK) return fail(rc, "invalid framing parameters");
   if (p->geo.Nfft > 8192) return fail(SMILEHIP_ERR_INVALID, "FFT length %lld > 8192 unsupported", (long long)p->geo.Nfft);
   const uint32_t mask = p->cfg.stage_mask ? p->cfg.stage_mask : SMILEHIP_STAGE_ALL;
+  // the tables built: the prosodyAcf chain has no mel bank and no DCT (its frames may be shorter than a bank has bands)
+  const uint32_t tmask = p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_ACF ? (mask & ~(SMILEHIP_STAGE_MEL | SMILEHIP_STAGE_MFCC)) : mask;
   p->h_window.assign(size_t(p->geo.N), 1.0f);
   if ((mask & SMILEHIP_STAGE_WINDOW) && (rc = make_window(p->cfg, p->geo.N, p->h_window)) != SMILEHIP_OK)
     return fail(rc, "unknown window function %d", p->cfg.win_func);
-  if (mask & SMILEHIP_STAGE_MEL) {
+  if (tmask & SMILEHIP_STAGE_MEL) {
     if ((rc = make_mel(p->cfg, p->geo, p->mel)) != SMILEHIP_OK) return fail(rc, "invalid mel bank parameters");
   } else {
     p->mel = MelBank();
     p->mel.n_bands = p->cfg.n_bands;
   }
-  if (mask & SMILEHIP_STAGE_MFCC) {
+  if (tmask & SMILEHIP_STAGE_MFCC) {
     if ((rc = make_dct(p->cfg, p->dct)) != SMILEHIP_OK) return fail(rc, "invalid MFCC range");
   } else {
     p->dct = DctTables();
@@ -225,14 +243,28 @@ static int build_tables(smilehip_plan *p, bool upload = true) {
     if ((rc = make_f0_tables(p->geo.K, p->geo.fft_frame_size_sec, p->cfg.shs_n_harmonics, p->cfg.shs_compression,
                              p->cfg.specscale_min_f > 0.0 ? p->cfg.specscale_min_f : 25.0, p->f0)))
       return fail(rc, "F0 chain: spectrum geometry / nHarmonics not usable by cSpecScale / cPitchShs");
+  } else if (p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_ACF) {
+    // everything the chain cannot express is refused with the option named
+    if (mask != SMILEHIP_STAGE_ALL) return fail(SMILEHIP_ERR_INVALID, "prosodyAcf chain: stage_mask must be all stages");
+    if (p->cfg.sma_win < 3 || !(p->cfg.sma_win & 1) || p->cfg.sma_win > 9)
+      return fail(SMILEHIP_ERR_INVALID, "prosodyAcf chain: sma_win (cContourSmoother smaWin) must be odd, 3 .. 9; got %d", p->cfg.sma_win);
+    if (p->cfg.n_delta != 0) return fail(SMILEHIP_ERR_INVALID, "prosodyAcf chain: n_delta must be 0 (the file has no cDeltaRegression); got %d", p->cfg.n_delta);
+    if (p->cfg.preemph) return fail(SMILEHIP_ERR_INVALID, "prosodyAcf chain: preemph must be 0 (the file has no cVectorPreemphasis)");
+    if (p->cfg.win_offset != 0.0) return fail(SMILEHIP_ERR_INVALID, "prosodyAcf chain: win_offset must be 0");
+    if (p->cfg.zero_pad_symmetric) return fail(SMILEHIP_ERR_INVALID, "prosodyAcf chain: zero_pad_symmetric must be 0 ([fft:cTransformFFT] zeroPadSymmetric = 0)");
+    if (p->cfg.acf_cep_use_power != 0 && p->cfg.acf_cep_use_power != 1)
+      return fail(SMILEHIP_ERR_INVALID, "prosodyAcf chain: acf_cep_use_power must be 0 or 1; got %d", p->cfg.acf_cep_use_power);
+    if (p->geo.Nfft < 64 || p->geo.Nfft > 8192)
+      return fail(SMILEHIP_ERR_INVALID, "prosodyAcf chain: the transform length must be 64 .. 8192 points; frame_size_sec at this sample_rate gives %lld",
+                  (long long)p->geo.Nfft);
   } else if (p->cfg.chain_kind != SMILEHIP_CHAIN_MFCC) {
     return fail(SMILEHIP_ERR_INVALID, "unknown chain_kind %d", p->cfg.chain_kind);
   }
   if (p->cfg.n_delta > 0 && (p->cfg.delta_win < 1 || p->cfg.delta_win > 4))
     return fail(SMILEHIP_ERR_INVALID, "delta_win must be 1..4");
 
-  std::vector<int32_t> rng((mask & SMILEHIP_STAGE_MEL) ? size_t(4) * p->mel.n_bands : 0);
-  for (int b = 0; b < p->mel.n_bands && (mask & SMILEHIP_STAGE_MEL); ++b) {
+  std::vector<int32_t> rng((tmask & SMILEHIP_STAGE_MEL) ? size_t(4) * p->mel.n_bands : 0);
+  for (int b = 0; b < p->mel.n_bands && (tmask & SMILEHIP_STAGE_MEL); ++b) {
     rng[4 * b + 0] = p->mel.rise_lo[b];
     rng[4 * b + 1] = p->mel.rise_hi[b];
     rng[4 * b + 2] = p->mel.fall_lo[b];
@@ -559,7 +591,7 @@ extern "C" void smilehip_plan_destroy(smilehip_plan *plan) { delete plan; }
 
 int plan_n_static(const smilehip_plan *p) {
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE_F0) return 2;
-  if (p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_SHS) return 3;
+  if (p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_SHS || p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_ACF) return 3;
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE) return 65;
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_EGEMAPS) return 25;
   return p->cfg.chain_kind == SMILEHIP_CHAIN_IS09 ? 16
@@ -567,7 +599,8 @@ int plan_n_static(const smilehip_plan *p) {
 }
 int plan_n_out(const smilehip_plan *p) { return plan_n_static(p) * (1 + p->cfg.n_delta); }
 int plan_row_extra(const smilehip_plan *p) {
-  return (p->cfg.chain_kind == SMILEHIP_CHAIN_IS09 || p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_SHS) ? p->cfg.sma_win / 2 : 0;
+  return (p->cfg.chain_kind == SMILEHIP_CHAIN_IS09 || p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_SHS ||
+          p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_ACF) ? p->cfg.sma_win / 2 : 0;
 }
 
 extern "C" int smilehip_plan_geometry(const smilehip_plan *p, smilehip_geometry *g) {
@@ -603,6 +636,7 @@ extern "C" double smilehip_row_time(const smilehip_plan *plan, int64_t n_frames,
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_MFCC || plan->cfg.chain_kind == SMILEHIP_CHAIN_PLP ||
       plan->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE_F0 || plan->cfg.chain_kind == SMILEHIP_CHAIN_EGEMAPS || n_frames <= 1)
     return smilehip_frame_time(plan, row);
+  // IS09 and prosodyAcf (lld_prosody_acf_ops.hpp: row_time_frame): the smoother's end-of-input rows repeat the last frame's time
   return smilehip_frame_time(plan, row < n_frames - 1 ? row : n_frames - 1);
 }
 

@@ -651,6 +651,156 @@ bool conf_to_prosody_shs(const ConfFile &f, ConfPlan &p, std::string &err) {
   return true;
 }
 
+// ---- smilextract_hip --set prosody_acf -C file: config/prosody/prosodyAcf.conf, possibly with other values of the options the chain
+// takes as parameters (cPitchACF maxPitch, voicingCutoff; cContourSmoother smaWin). Walked like prosodyShs.conf above: every other
+// option has the one value SMILEHIP_CHAIN_PROSODY_ACF implements or is refused by name. (Plain -C does not map the file.)
+// fingerprint of the reference's own file with its includes and every command-line option at its default (--fingerprint prints it)
+static const uint64_t kProsodyAcfFingerprint = 0xe34c269f6b709ce4ull;
+bool conf_to_prosody_acf(const ConfFile &f, ConfPlan &p, std::string &err) {
+  p = ConfPlan();
+  static const std::set<std::string> types = {"cFramer", "cIntensity", "cWindower", "cTransformFFT", "cFFTmagphase", "cAcf", "cPitchACF",
+                                              "cContourSmoother"};
+  std::map<std::string, const ConfInstance *> one;
+  std::vector<const ConfInstance *> acfs;
+  for (const ConfInstance &i : f.inst) {
+    if (is_io_type(i.type)) continue;
+    if (!types.count(i.type)) { err = "component [" + i.name + ":" + i.type + "] is not part of the graph of prosodyAcf.conf"; return false; }
+    if (i.type == "cAcf") { acfs.push_back(&i); continue; }
+    if (one.count(i.type)) { err = "more than one " + i.type + " ([" + i.name + "]): not the graph of prosodyAcf.conf"; return false; }
+    one[i.type] = &i;
+  }
+  for (const std::string &t : types)
+    if (t != "cAcf" && !one.count(t)) { err = "the graph has no " + t + ": not the graph of prosodyAcf.conf"; return false; }
+  if (acfs.size() != 2) { err = "the graph has " + std::to_string(acfs.size()) + " cAcf instances, prosodyAcf.conf has two (ACF and cepstrum)"; return false; }
+  auto lvl = [](const ConfInstance *i, const char *k) { const std::string *v = i->find(k); return v ? *v : std::string(); };
+  auto wired = [&](const ConfInstance *i, const std::string &want) {
+    if (lvl(i, "reader.dmLevel") == want) return true;
+    err = "[" + i->name + ":" + i->type + "] reader.dmLevel = '" + lvl(i, "reader.dmLevel") + "', expected '" + want + "' (not the wiring of prosodyAcf.conf)";
+    return false;
+  };
+  auto must_be = [](OptReader &o, const char *key, const char *want, const char *dflt) {
+    const std::string v = o.str(key, dflt);
+    if (lower(v) != lower(want) && o.err.empty())
+      o.err = "[" + o.ci.name + ":" + o.ci.type + "] " + key + " = " + v + " is not expressible on the fused path (needs " + want + ")";
+  };
+  const ConfInstance *fr = one["cFramer"], *in = one["cIntensity"], *win = one["cWindower"], *fft = one["cTransformFFT"],
+                     *mag = one["cFFTmagphase"], *pit = one["cPitchACF"], *smo = one["cContourSmoother"];
+  // which cAcf is which: cPitchACF reads "<acf level>;<cepstrum level>" (pitchACF.cpp:148-164: the ACF first)
+  const std::vector<std::string> pin = split_levels(lvl(pit, "reader.dmLevel"));
+  const ConfInstance *acf = nullptr, *cep = nullptr;
+  if (pin.size() == 2)
+    for (const ConfInstance *a : acfs) {
+      if (lvl(a, "writer.dmLevel") == pin[0] && !acf) acf = a;
+      else if (lvl(a, "writer.dmLevel") == pin[1] && !cep) cep = a;
+    }
+  if (!acf || !cep) {
+    err = "[" + pit->name + ":cPitchACF] reader.dmLevel = '" + lvl(pit, "reader.dmLevel") + "', expected the levels of the two cAcf instances, ACF first (not the wiring of prosodyAcf.conf)";
+    return false;
+  }
+  {                                                       // the cepstrum instance where the ACF belongs (and the other way round): the reader's order
+    const std::string *ca = acf->find("cepstrum"), *cc = cep->find("cepstrum");
+    if (ca && atof(ca->c_str()) != 0.0 && !(cc && atof(cc->c_str()) != 0.0)) {
+      err = "[" + pit->name + ":cPitchACF] reader.dmLevel = '" + lvl(pit, "reader.dmLevel") + "' names the cepstrum's level first; cPitchACF takes the ACF first (not the wiring of prosodyAcf.conf)";
+      return false;
+    }
+  }
+  {                                                       // src/core/winToVecProcessor.cpp:51-83
+    OptReader o(*fr);
+    if (!wired(fr, "wave")) return false;
+    o.require("frameSize", 0.05, 0.025); o.require("frameStep", 0.01, 0.0);
+    must_be(o, "frameMode", "fixed", "fixed"); must_be(o, "frameCenterSpecial", "left", "left");
+    o.require("noPostEOIprocessing", 1, 1); o.require("frameSizeFrames", 0, 0); o.require("frameStepFrames", 0, 0);
+    o.require("frameCenter", 0, 0); o.require("frameCenterFrames", 0, 0); o.require("allowLastFrameIncomplete", 0, 0);
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  const std::string frames = lvl(fr, "writer.dmLevel");
+  {                                                       // src/lldcore/intensity.cpp:36-38
+    OptReader o(*in);
+    if (!wired(in, frames)) return false;
+    o.require("intensity", 0, 1); o.require("loudness", 1, 0); o.require("processArrayFields", 1, 1);
+    if (o.has("nameAppend") && !o.str("nameAppend", "").empty()) o.err = "[" + in->name + ":cIntensity] nameAppend is not expressible on the fused path (needs none)";
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  {                                                       // src/dspcore/windower.cpp:36-49
+    OptReader o(*win);
+    if (!wired(win, frames)) return false;
+    const std::string wf = o.str("winFunc", "Han");
+    if (win_func_of(wf) != SMILEHIP_WIN_GAUSS) o.err = "[" + win->name + ":cWindower] winFunc = " + wf + " is not expressible on the fused path (needs gauss)";
+    o.require("gain", 1, 1); o.require("sigma", 0.4, 0.4); o.require("offset", 0, 0);
+    o.require("fade", 0, 0); o.require("squareRoot", 0, 0); o.require("xshift", 0, 0); o.require("processArrayFields", 1, 1);
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  {                                                       // src/dspcore/transformFft.cpp:34-35
+    OptReader o(*fft);
+    if (!wired(fft, lvl(win, "writer.dmLevel"))) return false;
+    o.require("inverse", 0, 0); o.require("zeroPadSymmetric", 0, 1); o.require("processArrayFields", 1, 1);
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  {                                                       // src/dspcore/fftmagphase.cpp:39-49
+    OptReader o(*mag);
+    if (!wired(mag, lvl(fft, "writer.dmLevel"))) return false;
+    o.require("inverse", 0, 0); o.require("magnitude", 1, 1); o.require("phase", 0, 0); o.require("joinMagphase", 0, 0);
+    o.require("normalise", 0, 0); o.require("power", 0, 0); o.require("dBpsd", 0, 0); o.require("processArrayFields", 1, 1);
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  for (const ConfInstance *a : {acf, cep}) {              // src/dspcore/acf.cpp:46-55; usePower defaults to 0 with cepstrum = 1 (:91-102)
+    const bool c = a == cep;
+    OptReader o(*a);
+    if (!wired(a, lvl(mag, "writer.dmLevel"))) return false;
+    o.require("cepstrum", c ? 1 : 0, 0); o.require("usePower", c ? 0 : 1, c ? 0 : 1); o.require("inverse", 0, 0);
+    o.require("cosLifterCepstrum", 0, 0); o.require("expBeforeAbs", 1, 1); o.require("symmetricData", 1, 1);
+    o.require("acfCepsNormOutput", 1, 1); o.require("oldCompatCepstrum", 0, 0); o.require("absCepstrum", 0, 0);
+    o.require("processArrayFields", 1, 1);
+    o.str("nameAppend", "acf");                           // (cPitchACF names its outputs itself)
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  {                                                       // src/lldcore/pitchACF.cpp:38-49, :96-103
+    OptReader o(*pit);
+    double mp = o.num("maxPitch", 500.0), vc = o.num("voicingCutoff", 0.55);
+    if (vc > 1.0) vc = 1.0;
+    if (vc < 0.0) vc = 0.0;
+    if (mp < 0.0) mp = 0.0;
+    p.f0_params["pitch_max"] = mp;
+    p.f0_params["voicing_cutoff"] = vc;
+    o.require("voiceProb", 1, 1); o.require("F0", 1, 0); o.require("F0raw", 0, 0); o.require("F0env", 0, 0); o.require("voiceQual", 0, 0);
+    o.require("HNR", 0, 0); o.require("HNRdB", 0, 0); o.require("linHNR", 0, 0); o.require("processArrayFields", 0, 0);
+    if (o.has("nameAppend") && !o.str("nameAppend", "").empty()) o.err = "[" + pit->name + ":cPitchACF] nameAppend is not expressible on the fused path (needs none)";
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  {                                                       // src/dspcore/contourSmoother.cpp:33-36, src/core/windowProcessor.cpp:39
+    OptReader o(*smo);
+    if (!wired(smo, lvl(pit, "writer.dmLevel") + ";" + lvl(in, "writer.dmLevel"))) return false;
+    const double w = o.num("smaWin", 3);
+    if ((w < 3 || w > 9 || w != std::floor(w) || !((int)w & 1)) && o.err.empty())
+      o.err = "[" + smo->name + ":cContourSmoother] smaWin = " + canonical_value(std::to_string(w)) + " is not expressible on the fused path (needs an odd number, 3 .. 9)";
+    p.f0_params["sma_win"] = w;
+    o.require("noZeroSma", 0, 0); o.require("noPostEOIprocessing", 0, 0);
+    must_be(o, "nameAppend", "sma", "sma");
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  if (lvl(smo, "writer.dmLevel") != "lld") {
+    err = "[" + smo->name + ":cContourSmoother] writer.dmLevel = '" + lvl(smo, "writer.dmLevel") + "', expected 'lld' (the level the shared output file's sinks read)";
+    return false;
+  }
+  if (!conf_check_io(f, {"lld"}, err)) return false;
+  p.preset = "prosody_acf";
+  for (const ConfInstance &i : f.inst)
+    if (i.type == "cWaveSource") { const std::string *fn = i.find("filename"); if (fn) p.wave_file = *fn; }
+  if (conf_fingerprint(f) == kProsodyAcfFingerprint) {     // the shipped file: the preset as it is
+    p.f0_params.clear();
+    p.describe = "the graph of prosodyAcf.conf (every processing component and option identical)";
+    return true;
+  }
+  std::string what;
+  for (const auto &kv : p.f0_params) {
+    char buf[64];
+    snprintf(buf, sizeof(buf), "%s%s = %.9g", what.empty() ? "" : ", ", kv.first.c_str(), kv.second);
+    what += buf;
+  }
+  p.describe = "the graph of prosodyAcf.conf with the file's own parameter values (" + what + ")";
+  return true;
+}
+
 static bool conf_to_plan_inner(const ConfFile &f, ConfPlan &p, std::string &err);
 bool conf_to_plan(const ConfFile &f, ConfPlan &p, std::string &err) {
   const bool ok = conf_to_plan_inner(f, p, err);

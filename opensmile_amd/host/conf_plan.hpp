@@ -82,6 +82,9 @@ bool conf_to_plan(const ConfFile &f, ConfPlan &p, std::string &err);
 // voicing_cutoff, shs_n_harmonics, shs_compression, shs_n_candidates, specscale_min_f, sma_win). Any other component, wiring or option
 // value is refused with its name in err. conf_to_plan itself does not map that file.
 bool conf_to_prosody_shs(const ConfFile &f, ConfPlan &p, std::string &err);
+// smilextract_hip --set prosody_acf -C file: the same for config/prosody/prosodyAcf.conf; preset = "prosody_acf", f0_params holds
+// cPitchACF maxPitch and voicingCutoff (clamped as pitchACF.cpp:96-103 does) and cContourSmoother smaWin: pitch_max, voicing_cutoff, sma_win
+bool conf_to_prosody_acf(const ConfFile &f, ConfPlan &p, std::string &err);
 
 // Sources and sinks are outside the fingerprint and the plan: this checks them. Every cWaveSource must read the whole file
 // (start 0, end -1, no sample-based range, a RIFF header), every ACTIVE sink (filename other than "?") must be one

@@ -35,6 +35,8 @@ std::vector<std::string> lld_names_htk_variant(bool plp, bool energy) {
 
 // config/prosody/prosodyShs.conf, level lld: cPitchSmoother's two outputs and cIntensity's "<input>_loudness" (copyInputName = 1 on
 // the framer's "pcm" field), each with cContourSmoother's nameAppend = sma
+// config/prosody/prosodyAcf.conf, level lld: cPitchACF's outputs in the order of setupNewNames (pitchACF.cpp:111-132), then cIntensity's
+std::vector<std::string> lld_names_prosody_acf() { return {"voiceProb_sma", "F0_sma", "pcm_loudness_sma"}; }
 std::vector<std::string> lld_names_prosody_shs() { return {"F0final_sma", "voicingFinalUnclipped_sma", "pcm_loudness_sma"}; }
 
 std::vector<std::string> lld_names_is09() {

@@ -42,6 +42,7 @@ std::vector<std::string> lld_names_plp_0_d_a();
 std::vector<std::string> lld_names_htk_variant(bool plp, bool energy);   // MFCC12_{0,E}_D_A[_Z], PLP_{0,E}_D_A[_Z]
 std::vector<std::string> lld_names_is09();
 std::vector<std::string> lld_names_prosody_shs();   // prosodyShs.conf: F0final_sma, voicingFinalUnclipped_sma, pcm_loudness_sma
+std::vector<std::string> lld_names_prosody_acf();   // prosodyAcf.conf: voiceProb_sma, F0_sma, pcm_loudness_sma
 std::vector<std::string> lld_names_compare16();
 std::vector<std::string> func_names_is09();     // 384: <lld>_<functional>
 std::vector<std::string> func_names_compare16();   // 6373, the functionals level of ComParE_2016.conf

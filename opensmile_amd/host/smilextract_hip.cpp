@@ -23,6 +23,8 @@
 //   smilextract_hip --set prosody_shs   config/prosody/prosodyShs.conf: F0final, voicing and loudness contours (-O out.htk -csvoutput out.csv)
 //                   [-C prosodyShs.conf]  with that file's (edited) parameter values and command-line options; what the chain does not
 //                   take as a parameter is refused by name (plain -C does not map this file)
+//   smilextract_hip --set prosody_acf   config/prosody/prosodyAcf.conf: voicing probability, ACF / cepstrum F0 and loudness contours
+//                   [-C prosodyAcf.conf]  with that file's (edited) maxPitch, voicingCutoff and smaWin; anything else is refused by name
 //   smilextract_hip --set gemapsv01a | egemapsv01a   the v01a files: the same columns, zeroPadSymmetric = 0, useBrokenJitterThresh = 1, maxF = 5500
 //   smilextract_hip --set gemapsv01b | egemapsv01b   config/gemaps/v01b/GeMAPSv01b.conf (18 LLDs, 62 functionals) / config/egemaps/v01b/
 //                                       eGeMAPSv01b.conf (23, 88): sub-graphs of eGeMAPSv02.conf, written as column subsets of its levels
@@ -156,9 +158,11 @@ static int run_main(int argc, char **argv, Persist *ps) {
   // ---- -C file.conf: the plan comes from the configuration file (conf_plan.cpp)
   ConfPlan conf_plan;
   if (with_conf) {
-    // --set prosody_shs -C file: the set with the file's own parameter values (conf_to_prosody_shs); otherwise one or the other
-    const bool set_with_conf = opt.count("--set") && opt["--set"] == "prosody_shs";
-    if (opt.count("--set") && !set_with_conf) die("-C and --set exclude each other (except --set prosody_shs -C prosodyShs.conf)");
+    // --set prosody_shs | prosody_acf -C file: the set with the file's own parameter values (conf_to_prosody_shs / _acf); otherwise one or the other
+    const bool set_acf = opt.count("--set") && opt["--set"] == "prosody_acf";
+    const bool set_with_conf = opt.count("--set") && (opt["--set"] == "prosody_shs" || set_acf);
+    if (opt.count("--set") && !set_with_conf)
+      die("-C and --set exclude each other (except --set prosody_shs -C prosodyShs.conf and --set prosody_acf -C prosodyAcf.conf)");
     ConfFile cf;
     std::string cerr_;
     if (!conf_parse(opt["-C"], conf_cmdline, cf, cerr_)) die("-C " + opt["-C"] + ": " + cerr_);
@@ -200,11 +204,14 @@ static int run_main(int argc, char **argv, Persist *ps) {
           opt[o.second] = dflt->second;
       }
     }
-    if (!(set_with_conf ? conf_to_prosody_shs(cf, conf_plan, cerr_) : conf_to_plan(cf, conf_plan, cerr_))) {
+    if (!(set_acf ? conf_to_prosody_acf(cf, conf_plan, cerr_)
+                  : (set_with_conf ? conf_to_prosody_shs(cf, conf_plan, cerr_) : conf_to_plan(cf, conf_plan, cerr_)))) {
       ConfPlan as_set;
       std::string e2;
       const bool hint = !set_with_conf && conf_to_prosody_shs(cf, as_set, e2);
-      die("-C " + opt["-C"] + " cannot run on the fused path: " + cerr_ + (hint ? " -- this file runs as --set prosody_shs -C <file>" : ""));
+      const bool hint_acf = !set_with_conf && !hint && conf_to_prosody_acf(cf, as_set, e2);
+      die("-C " + opt["-C"] + " cannot run on the fused path: " + cerr_ +
+          (hint ? " -- this file runs as --set prosody_shs -C <file>" : (hint_acf ? " -- this file runs as --set prosody_acf -C <file>" : "")));
     }
     fprintf(stderr, "smilextract_hip: %s -> %s\n", opt["-C"].c_str(), conf_plan.describe.c_str());
     if (!conf_plan.preset.empty()) opt["--set"] = conf_plan.preset;
@@ -280,12 +287,14 @@ static int run_main(int argc, char **argv, Persist *ps) {
   smilehip_lld_config vcfg;
   if (free_chain) vcfg = conf_plan.cfg;
   // config/prosody/prosodyShs.conf: an LLD-only set like the cepstral files (-O = HTK, -csvoutput = CSV of the lld level)
-  const bool prosody = set == "prosody_shs";
-  if (prosody) smilehip_config_prosody_shs(&vcfg);
+  const bool prosody_acf = set == "prosody_acf";         // config/prosody/prosodyAcf.conf: the same kind of set
+  const bool prosody = set == "prosody_shs" || prosody_acf;
+  if (prosody_acf) smilehip_config_prosody_acf(&vcfg);
+  else if (prosody) smilehip_config_prosody_shs(&vcfg);
   const bool htk_variant = free_chain || prosody || (!is09 && !cmp16 && !egm && smilehip_config_htk_variant(&vcfg, variant.c_str()) == SMILEHIP_OK);
   const bool plp = htk_variant && vcfg.chain_kind == SMILEHIP_CHAIN_PLP;
   if (!is09 && !cmp16 && !egm && !htk_variant)
-    die("--set must be mfcc12_{0,e}_d_a[_z], plp_{0,e}_d_a[_z], is09_emotion, compare16, compare16_lld, is13_compare, egemapsv02, gemapsv01b, egemapsv01b, gemapsv01a, egemapsv01a or prosody_shs (or use -C file.conf)");
+    die("--set must be mfcc12_{0,e}_d_a[_z], plp_{0,e}_d_a[_z], is09_emotion, compare16, compare16_lld, is13_compare, egemapsv02, gemapsv01b, egemapsv01b, gemapsv01a, egemapsv01a, prosody_shs or prosody_acf (or use -C file.conf)");
   // parmKind of the files' own cHtkSink sections (the _Z files); the others write through standard_data_output_lldonly (9)
   int parm_kind = 9;
   if (variant == "MFCC12_0_D_A_Z") parm_kind = 11014;
@@ -458,6 +467,7 @@ static int run_main(int argc, char **argv, Persist *ps) {
   };
   const std::vector<std::string> lld_names =
       free_chain ? conf_plan.lld_names
+                 : prosody_acf ? lld_names_prosody_acf()
                  : prosody ? lld_names_prosody_shs()
                  : (is09 ? lld_names_is09() : (cmp16 ? (cmp_subset ? select_names(lld_names_compare16(), sel_lld) : lld_names_compare16())
                     : (egm ? (egm_subset ? select_names(lld_names_egemaps(), sel_lld) : lld_names_egemaps())
