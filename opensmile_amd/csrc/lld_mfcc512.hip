@@ -23,8 +23,8 @@
 //           plus an untangle pass
 //   FFT     256 = 16 x 16: radix-16 DFT over m in registers (two radix-4
 //           layers, constants only), twiddle by w256^(j*k1) (LDS table), ONE
-//           16x16 transpose of (re,im) pairs through LDS (b64 stores and loads,
-//           conflict-free interleaved layout), radix-16 DFT over j
+//           16x16 transpose through LDS (a plane of re and a plane of im: address-free
+//           b32 stores, b128 loads, conflict-free by a table of row bases: kTSWaveFloats), radix-16 DFT over j
 //           Order of the transposition traffic (round 8): the first DFT's last layer finishes its outputs in groups of four --
 //           k1 = 0, 4, 8, 12, then 1, 5, 9, 13, .. -- and each is twiddled and stored at once, so the sixteen stores are spread
 //           over that layer and the twiddles instead of standing in one block in front of the sixteen loads (which are issued
@@ -90,6 +90,34 @@ constexpr int kPbFloats = 448;        // power buffer of one frame group (33 oct
 constexpr int kWaveFloats = 2080;     // per-wave LDS: max(transpose buffer, 4 x (kLmelFloats + kPbFloats) = 2064), 16-byte multiple
 
 static_assert(kWaveFloats >= kTB2Floats && kWaveFloats >= 4 * (kLmelFloats + kPbFloats) && kWaveFloats % 4 == 0, "per-wave LDS region");
+
+// The SPLIT-COMPLEX transposition buffer (the instances of split_transpose() below): a plane of real and a plane of imaginary parts,
+// a row = the 64 floats that the 64 lanes hold for one index k1 of the first DFT16, at `row base + lane`. The writer is lane-linear
+// (lane 16 g + j writes column j of group g), so a row is stored by ds_write_addtid_b32 -- address = M0 + immediate + 4 x lane, no
+// address register, 2 cycles of the LDS pipe where a ds_write_b64 of the pair takes 6 (its address and two data registers at 2
+// cycles each) -- and the reader, lane (g, kc), takes the sixteen columns of row kc of its group with four ds_read_b128 per plane.
+// Row bases are a TABLE: a ds_read_b128 lane group holds lanes j = 0 .. 3, 12 .. 15 of one frame group (rows A, through the lane -> column
+// map) and j = 4 .. 11 of the next (rows B), whose columns start four bank quads further on. With q(r) = (base(r) / 4) mod 16 the
+// loads are conflict-free iff q is one-to-one on A and on B and q(A) u (q(B) + 4) = q(B) u (q(A) + 4) = all sixteen quads, i.e.
+// q(A) = q(A) + 8 and q(B) = complement of q(A), minus 4. q(A) = q(B) = {0, 1, 2, 3, 8, 9, 10, 11} is the one family in which a row
+// of A and a row of B share a quad; both planes share it too, so FOUR rows (64 quads, a multiple of 16) stand on each quad one behind
+// the other -- re A | re B | im A | im B, slot s = 0 .. 7 -- and the padding is what the quad's steps 0 -> 1 -> 2 -> 3 -> 8 -> .. -> 11 take:
+// 11 quads in all, 2048 + 44 floats. The imaginary plane lies 128 floats behind the real one in every slot (one address register,
+// immediate offsets). tools/lds_bank_sim.py holds the same table and is the judge (tests/test_lds_ledger_split_transpose.py).
+// M0 holds 16 bits of LDS byte address, so the per-wave regions of these instances come FIRST in the block's LDS, the shared
+// tables behind them.
+constexpr int kTSWaveFloats = 2092;   // per-wave LDS of the split-complex instances: 32 rows of 64 floats + 11 bank quads
+// ONE table serves both lane -> column maps: rows 0 .. 3 and 12 .. 15 stand first in slots 0 .. 3 and 4 .. 7, rows 4 .. 11 second in
+// slots 0 .. 7. Lanes j = 0 .. 3, 12 .. 15 read rows 0 .. 3, 12 .. 15 (kc = j) or 0 .. 3, 13, 14, 15, 8 (the one-hop map), lanes 4 .. 11
+// the other eight: in both maps each set meets every slot once, and only the slot decides the quad.
+constexpr int tsplit_base(int r, bool imag) {   // float offset of row r (index k1 = column kc) in the wave's region
+  const int s = r < 4 ? r : (r < 12 ? r - 4 : r - 8);        // slot
+  const bool b = r >= 4 && r < 12;                            // second of the slot's two rows
+  return 256 * s + 4 * (s < 4 ? s : s + 4) + (b ? 64 : 0) + (imag ? 128 : 0);
+}
+static_assert(tsplit_base(11, true) + 64 == kTSWaveFloats, "last row");
+static_assert(kTSWaveFloats >= 4 * (kLmelFloats + kPbFloats) && kTSWaveFloats % 4 == 0, "per-wave LDS region, split-complex");
+static_assert(4 * (kWavesPerBlock - 1) * kTSWaveFloats < 65536, "a wave's LDS byte address has to fit M0's 16 bits");
 static_assert(kPbFloats % 64 == 0 && kPbFloats >= 33 * kOctetFloats, "power buffer");
 static_assert(kLmelFloats >= 64 && kLmelFloats % 4 == 0 && (kLmelFloats / 4) % 2 == 1,
               "band vectors: room for the PLP vectors at +32 and +48, 16-byte aligned, neighbouring groups on different bank quads");
@@ -121,6 +149,20 @@ __device__ __forceinline__ void dft4(float &r0, float &i0, float &r1, float &i1,
   r3 = t1r - t3i; i3 = t1i + t3r;     // t1 + i*t3
 }
 
+// the same with a3 = 0 as a literal: the compiler folds x - 0 but not x + 0 (the sign of a zero), so the general form carries two
+// additions of zero. Without them only the sign of an exact zero inside the transform can differ, and every output of the
+// transform is squared before it is used (pk, pm, p128)
+__device__ __forceinline__ void dft4_z3(float &r0, float &i0, float &r1, float &i1, float &r2, float &i2,
+                                        float &r3, float &i3) {
+  const float t0r = r0 + r2, t0i = i0 + i2;
+  const float t1r = r0 - r2, t1i = i0 - i2;
+  const float t2r = r1, t2i = i1;
+  r0 = t0r + t2r; i0 = t0i + t2i;
+  r2 = t0r - t2r; i2 = t0i - t2i;
+  r1 = t1r + t2i; i1 = t1i - t2r;
+  r3 = t1r - t2i; i3 = t1i + t2r;
+}
+
 __device__ __forceinline__ void cmul(float &r, float &i, float c, float s) {   // (r+ii)*(c+is)
   const float nr = fmaf(r, c, -i * s);
   const float ni = fmaf(r, s, i * c);
@@ -150,8 +192,11 @@ struct Dft16K {
 // In three parts, so that the caller can put LDS traffic between them (round 8): dft16_first + dft16_last(q = 0 .. 3) + dft16_rename
 // is dft16 -- one implementation of the arithmetic.
 // first layer, group m0: needs the inputs m0, m0 + 4, m0 + 8, m0 + 12 only
+// Z3: the input m0 + 12 is a literal zero (the sample pairs m >= MP of a frame that has fewer than sixteen per lane)
+template <bool Z3 = false>
 __device__ __forceinline__ void dft16_first(float (&re)[16], float (&im)[16], int m0) {
-  dft4(re[m0], im[m0], re[m0 + 4], im[m0 + 4], re[m0 + 8], im[m0 + 8], re[m0 + 12], im[m0 + 12]);
+  if constexpr (Z3) dft4_z3(re[m0], im[m0], re[m0 + 4], im[m0 + 4], re[m0 + 8], im[m0 + 8], re[m0 + 12], im[m0 + 12]);
+  else dft4(re[m0], im[m0], re[m0 + 4], im[m0 + 4], re[m0 + 8], im[m0 + 8], re[m0 + 12], im[m0 + 12]);
 }
 // y[m0][q] sits at index m0 + 4q. Twiddles w16^(m0*q), w16 = e^{-2 pi i/16}:
 // (1,1)->e1 (1,2)->e2 (1,3)->e3 (2,1)->e2 (2,2)->e4 (2,3)->e6 (3,1)->e3 (3,2)->e6 (3,3)->e9
@@ -290,6 +335,39 @@ template <int MP, bool PLP, bool DELTA>
 constexpr bool one_hop_exchange() {
   return !PLP && !(MP == 16 && DELTA);
 }
+// The transposition through the split-complex buffer (tsplit_base above) with address-free stores, or through the interleaved
+// buffer of (re, im) pairs with ds_write_b64 / ds_read_b64. Per instance: the split form is taken by the instances of the bench's
+// class -- the column map of one_hop_exchange(), the same rule -- which is the class it was timed in (DESIGN 4.1,
+// profiles/split_transpose_ab.txt). The PLP chain and the delta-fused MP = 16 instances keep the interleaved buffer: nobody has
+// timed them. Statically the split form would suit them as well (the row table serves kc = j too; compiled for all 108 instances
+// no instance had more scratch -- 1524 -> 992 bytes per lane summed over the 32 that have any --, all had <= 128 VGPRs, occupancy
+// >= 4 and two blocks per CU: tools/dev/kernel_resources.sh lld_mfcc512.hip) and their bits were the parent's.
+template <int MP, bool PLP, bool DELTA>
+constexpr bool split_transpose() {
+  return !PLP && !(MP == 16 && DELTA);
+}
+// One index k1 of the first DFT16 into its two rows: the wave's region is M0 (set at the head of the pass), the row an immediate.
+// (The compiler does not count these stores in its s_waitcnt lgkmcnt bookkeeping: a wait of its own then stands for MORE
+// outstanding operations than it counted and returns later, never earlier; LDS operations of a wave complete in order.)
+template <int K1>
+__device__ __forceinline__ void tsplit_store(float x, float y) {
+  asm volatile("ds_write_addtid_b32 %0 offset:%2\n\tds_write_addtid_b32 %1 offset:%3"
+               :
+               : "v"(x), "v"(y), "i"(4 * tsplit_base(K1, false)), "i"(4 * tsplit_base(K1, true))
+               : "memory");
+}
+__device__ __forceinline__ void tsplit_store_k1(int k1, float x, float y) {   // k1 is a constant after unrolling
+  switch (k1) {
+#define SMILEHIP_TSPLIT_CASE(K) case K: tsplit_store<K>(x, y); break;
+    SMILEHIP_TSPLIT_CASE(0) SMILEHIP_TSPLIT_CASE(1) SMILEHIP_TSPLIT_CASE(2) SMILEHIP_TSPLIT_CASE(3)
+    SMILEHIP_TSPLIT_CASE(4) SMILEHIP_TSPLIT_CASE(5) SMILEHIP_TSPLIT_CASE(6) SMILEHIP_TSPLIT_CASE(7)
+    SMILEHIP_TSPLIT_CASE(8) SMILEHIP_TSPLIT_CASE(9) SMILEHIP_TSPLIT_CASE(10) SMILEHIP_TSPLIT_CASE(11)
+    SMILEHIP_TSPLIT_CASE(12) SMILEHIP_TSPLIT_CASE(13) SMILEHIP_TSPLIT_CASE(14) SMILEHIP_TSPLIT_CASE(15)
+#undef SMILEHIP_TSPLIT_CASE
+    default: break;
+  }
+}
+typedef float float4v __attribute__((ext_vector_type(4)));
 typedef float float2v __attribute__((ext_vector_type(2)));
 __device__ float2v tbuffer_load_xy(__amdgpu_buffer_rsrc_t rsrc, int voffset, int soffset, int format, int aux)
     __asm("llvm.amdgcn.raw.ptr.tbuffer.load.v2f32");
@@ -373,7 +451,8 @@ __device__ __forceinline__ void wave_set_prio(int level) {
 //   shared tables : tw512 [256 f2] | win [MP*16 f2] | tw256 [256 f2, index k1*16+j] |
 //                   melw0 [UC*16 f4] | melw1 [UC*16 f4] | dct [16 x 28] | plp [48]
 //   per wave      : 4 x (log-mel [32] | acf [16] | cepstra [16]) | 4 x power buffer [448];
-//                   the (re,im) transpose buffer [2078] overlays all of it between the two DFT16
+//                   the transpose buffer (split-complex [2092]; interleaved (re,im) pairs [2078]) overlays all of it between the
+//                   two DFT16. With the split-complex buffer the eight per-wave regions stand in FRONT of the shared tables
 // DELTA: the two regression stages behind the static coefficients (cDeltaRegression, deltaRegression.cpp:144-152, deltawin = 2,
 // twice) computed by the same waves -- a lane keeps its coefficient of the previous pass's frame and the two passes' first-order
 // values in registers, takes its neighbours' through the LDS crossbar (ds_bpermute: no storage), and writes static | delta |
@@ -394,8 +473,21 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
   const int g = lane >> 4;
   const int j = lane & 15;
 
-  // ---- carve shared memory
-  float2 *s_tw512 = reinterpret_cast<float2 *>(smem);
+  // ---- carve shared memory (split-complex transposition: the per-wave regions first, see kTSWaveFloats)
+  constexpr bool kOneHop = one_hop_exchange<MP, PLP, DELTA>();
+  constexpr bool kSplit = split_transpose<MP, PLP, DELTA>();
+  constexpr int kWaveRegion = kSplit ? kTSWaveFloats : kWaveFloats;
+  typedef __attribute__((address_space(3))) float *LdsFloatPtr;
+  float *tables = smem;
+  if constexpr (kSplit) {
+    // behind 65 KB of wave regions no table offset fits an LDS instruction's 16-bit immediate: the tables' base is an opaque
+    // scalar, so that the compiler adds it to the per-lane part of an address once and keeps the small immediates it always had
+    // (with the constant in sight it built one address register per offset and spilled them)
+    uint32_t tb = (uint32_t)(uintptr_t)(LdsFloatPtr)smem + 4u * kWavesPerBlock * kWaveRegion;
+    asm volatile("" : "+s"(tb));
+    tables = (float *)(LdsFloatPtr)(uintptr_t)tb;
+  }
+  float2 *s_tw512 = reinterpret_cast<float2 *>(tables);
   float2 *s_win = s_tw512 + 256;
   float2 *s_tw256 = s_win + MP * 16;
   float4 *s_melw0 = reinterpret_cast<float4 *>(s_tw256 + 256);
@@ -403,7 +495,7 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
   float *s_dct = reinterpret_cast<float *>(s_melw1 + UC * 16);
   float *s_plp = s_dct + 16 * 28;                                    // PLP chain: eql[32] | sintable[16]
   constexpr int shared_floats = 256 * 2 + MP * 16 * 2 + 256 * 2 + UC * 16 * 8 + 16 * 28 + 48;
-  float *wbase = smem + shared_floats + wave * kWaveFloats;
+  float *wbase = smem + (kSplit ? 0 : shared_floats) + wave * kWaveRegion;
   float *s_lmel = wbase + g * kLmelFloats;                        // log-mel of my frame (28 read by the DCT)
   float *s_cep = s_lmel + 48;                                     // PLP: 16 cepstra behind the band vector and its 16 acf lags
   float *s_pb = wbase + 4 * kLmelFloats + g * kPbFloats;          // power spectrum of my frame
@@ -442,8 +534,15 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
   // The column of the second DFT16 that lane j transforms: 0 .. 7, 9 .. 15, 8 (one_hop_exchange()) -- the lane's bins, their
   // twiddles and their places in the power buffer go by kc; everything in front of the transposition's loads and behind the power
   // buffer goes by j. kc(0) = 0: lane 0 stays the lane of DC / Nyquist and of bin 128.
-  constexpr bool kOneHop = one_hop_exchange<MP, PLP, DELTA>();
   const int kc = !kOneHop ? j : (j < 8 ? j : (j == 15 ? 8 : j + 1));
+  // split-complex transposition: the wave's region as the stores' M0 (an LDS byte address) and the reader's one address -- columns
+  // 0 .. 15 of row kc of my group in the real plane, the imaginary plane 128 floats behind it
+  const uint32_t wbase_lds = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(LdsFloatPtr)wbase);
+  int ts_row = 0;
+#pragma unroll
+  for (int r = 0; r < 16; ++r)
+    if (kc == r) ts_row = tsplit_base(r, false);
+  const float *ts_rd = wbase + ts_row + 16 * g;
   float *pb_k = s_pb + pb_pos(kc);             // my bins k = kc + 16 q sit 24 q floats further on
   float *pb_m = s_pb + pb_pos(256 - kc);       // their mirror images 256 - k sit 24 q floats back
 
@@ -545,6 +644,10 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
   for (;;) {
     wave_set_prio(passes_done + slot);
     passes_done += 1;
+    // M0 for the pass's address-free stores: written here and nowhere else in the kernel (the compiler has no use for M0 in this
+    // kernel: tests/test_mfcc512_split_transpose_static.py reads the assembly); one wait state between a scalar write of M0 and an
+    // LDS instruction that adds the lane number to it
+    if constexpr (kSplit) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0" : : "s"(wbase_lds));
     const bool live = tp + g < (DELTA ? cur_live : cur_n);
     PH(0);                                   // loop overhead
     // ------------------------------------------------------------ frame from registers: R0 (scale folded), R2, R3
@@ -647,7 +750,10 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
       for (int p = 1; p < 4; ++p) w[p] = s_tw256[(4 * p) * 16 + j];
       w[0] = make_float2(1.0f, 0.0f);              // k1 = 0: no product
 #pragma unroll
-      for (int m0 = 0; m0 < 4; ++m0) dft16_first(re, im, m0);
+      for (int m0 = 0; m0 < 4; ++m0) {
+        if (m0 + 12 >= MP) dft16_first<true>(re, im, m0);      // MP = 13: m = 13, 14, 15 are literal zeros
+        else dft16_first(re, im, m0);
+      }
       dft16_twiddles(re, im, dk);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -660,7 +766,8 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
         for (int p = 0; p < 4; ++p) {
           const int k1 = q + 4 * p;
           if (k1 > 0) cmul(re[4 * q + p], im[4 * q + p], w[p].x, w[p].y);
-          tbw[k1 * kTB2Row] = make_float2(re[4 * q + p], im[4 * q + p]);
+          if constexpr (kSplit) tsplit_store_k1(k1, re[4 * q + p], im[4 * q + p]);
+          else tbw[k1 * kTB2Row] = make_float2(re[4 * q + p], im[4 * q + p]);
         }
 #pragma unroll
         for (int p = 0; p < 4; ++p) w[p] = wn[p];
@@ -669,11 +776,25 @@ __device__ __forceinline__ void lld_mfcc512_body(const LldParams &P, const Fast5
     PH(3);                                   // dft16 + twiddles (+ transposition writes)
     {
       wave_lds_fence();
+      if constexpr (kSplit) {                    // four ds_read_b128 per plane: columns 4 i .. 4 i + 3 (4 LDS cycles each)
+        typedef const volatile __attribute__((address_space(3))) float4v *LdsF4;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float4v v = ((LdsF4)ts_rd)[i];
+          re[4 * i] = v.x; re[4 * i + 1] = v.y; re[4 * i + 2] = v.z; re[4 * i + 3] = v.w;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float4v v = ((LdsF4)ts_rd)[32 + i];
+          im[4 * i] = v.x; im[4 * i + 1] = v.y; im[4 * i + 2] = v.z; im[4 * i + 3] = v.w;
+        }
+      } else {
 #pragma unroll
       for (int jj = 0; jj < 16; ++jj) {          // one ds_read_b64 each (2 LDS cycles); paired into ds_read2_b64 they would take 8 per pair
         typedef const volatile __attribute__((address_space(3))) unsigned long long *LdsU64;
         const unsigned long long v = ((LdsU64)tbr)[jj];
         re[jj] = __int_as_float((int)(uint32_t)v); im[jj] = __int_as_float((int)(uint32_t)(v >> 32));
+      }
       }
       wave_lds_fence();
     }
@@ -1046,7 +1167,11 @@ int fast512_build_host(const smilehip_lld_config &cfg, const Geometry &geo, cons
 }
 
 template <int MP, bool PREEMPH, bool USE_POWER, bool ALIGNED, bool PLP, int UC, bool DELTA = false>
-static hipError_t launch_mfcc512_one(bool padded, unsigned grid, size_t lds, hipStream_t s, const LldParams &P, const Fast512Tables &F) {
+static hipError_t launch_mfcc512_one(bool padded, unsigned grid, hipStream_t s, const LldParams &P, const Fast512Tables &F) {
+  constexpr int shared_floats = 256 * 2 + MP * 16 * 2 + 256 * 2 + UC * 16 * 8 + 16 * 28 + 48;          // (the kernel's own figure)
+  constexpr int wave_floats = split_transpose<MP, PLP, DELTA>() ? kTSWaveFloats : kWaveFloats;
+  constexpr size_t lds = sizeof(float) * (size_t(shared_floats) + size_t(kWavesPerBlock) * wave_floats);
+  static_assert(2 * lds <= 160 * 1024, "two blocks per CU");
   if constexpr (PREEMPH) {
     if (padded) {
       hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&lld_mfcc512_padded<MP, PREEMPH, USE_POWER, ALIGNED, PLP, UC, DELTA>),
@@ -1064,8 +1189,6 @@ static hipError_t launch_mfcc512_one(bool padded, unsigned grid, size_t lds, hip
 }
 
 hipError_t launch_mfcc512(const LldParams &P, const Fast512Tables &F, const Fast512Host &h, bool aligned, bool fused_delta, hipStream_t s) {
-  const int shared_floats = 256 * 2 + h.mp * 16 * 2 + 256 * 2 + h.mel_units * 16 * 8 + 16 * 28 + 48;
-  const size_t lds = sizeof(float) * (size_t(shared_floats) + size_t(kWavesPerBlock) * kWaveFloats);
   if (fused_delta && (!aligned || !P.ftile_rec || P.n_ftiles <= 0)) return hipErrorInvalidValue;   // (the caller decides; see smilehip_mfcc_run)
   unsigned grid = (unsigned)(((fused_delta ? P.n_ftiles : P.n_tiles) + kWavesPerBlock - 1) / kWavesPerBlock);
   if (grid > (unsigned)h.max_blocks) grid = (unsigned)h.max_blocks;   // persistent: 2 blocks of 8 waves per CU
@@ -1078,7 +1201,7 @@ hipError_t launch_mfcc512(const LldParams &P, const Fast512Tables &F, const Fast
   const bool padded = P.pad_left != 0 || h.force_padded;
 #define SMILEHIP_LAUNCH(...)                                                                                    \
   {                                                                                                             \
-    hipError_t e = launch_mfcc512_one<__VA_ARGS__>(padded, grid, lds, s, P, F);                                 \
+    hipError_t e = launch_mfcc512_one<__VA_ARGS__>(padded, grid, s, P, F);                                      \
     if (e != hipSuccess) return e;                                                                              \
     launched = true;                                                                                            \
   }

@@ -35,7 +35,19 @@ The transposition is modelled per instruction and in issue order (`transposition
 on its own row / column index only, so the ORDER in which the sixteen stores and the sixteen loads are issued cannot change the
 conflict count -- the function checks that and returns the count for any order (since round 8 the stores are issued in the order of
 the first DFT's last layer, TRANSPOSE_ORDER_R8; the loads in that order too were measured and are no gain; before
-round 8 both were issued in index order)."""
+round 8 both were issued in index order).
+
+`split_layout`: the kernel's SPLIT-COMPLEX transposition buffer (its split_transpose() instances: all but the PLP chain and MP = 16
+with the regression stages fused, the rule of one_hop_exchange(); those keep the interleaved buffer of `tree_layout`, which is also
+what the split form was measured against). A plane of real and a plane of
+imaginary parts, a row = the 64 floats the 64 lanes hold for one index k1, at TSPLIT row base + lane:
+  ds_write_addtid_b32          address = M0 + immediate + 4 x lane, no address register: banked as a ds_write_b32 (2 groups of 32
+                               consecutive dwords: never a conflict), array 2, store transfer 2 (one data dword)
+Two of them per index (32 per pass), and the reader -- lane (g, kc) takes columns 0 .. 15 of row kc of its group -- four ds_read_b128
+per plane. A b128 lane group mixes lanes j = 0 .. 3, 12 .. 15 of one frame group with j = 4 .. 11 of the next, so the row bases are a
+table (`tsplit_base`, the kernel's function of the same name): four rows (re A | re B | im A | im B) on each of the bank quads 0, 1,
+2, 3, 8, 9, 10, 11, 2048 + 44 floats per wave. The per-wave regions of these instances come first in the block's LDS (M0 holds 16 bits
+of byte address), the shared tables behind them."""
 import os
 import re
 import subprocess
@@ -49,6 +61,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MP, UC = 13, 6                       # the bench's instance
 K_TB2_ROW = 65                       # float2 per 4-group row of the transpose buffer
 K_LMEL, K_OCTET, K_PB, K_WAVE = 68, 12, 448, 2080
+K_TS_WAVE = 2092                     # per-wave LDS of the split-complex instances (kTSWaveFloats)
 
 TRANSPOSE_ORDER_PARENT = list(range(16))
 TRANSPOSE_ORDER_R8 = [q + 4 * p for q in range(4) for p in range(4)]       # 0, 4, 8, 12 | 1, 5, 9, 13 | ...
@@ -70,6 +83,8 @@ class Layout:
     lane_major: bool = False         # the tables of pairs: one row per lane (tw512 | window | tw256), read 16 bytes at a time
     column_map: bool = False         # lane j transforms column KC[j] of the second DFT16 (the one-hop untangle exchange)
     tab_row: int = None              # floats per lane-major row; None: the smallest odd number of bank quads that holds a row
+    split: bool = False              # the split-complex transposition buffer; the per-wave regions in front of the shared tables
+    plp: bool = False                # (only the column map of the split form depends on it)
 
     # ---- the shared tables in front of the per-wave regions (float offsets)
     @property
@@ -117,6 +132,26 @@ def tree_layout(mp=MP, uc=UC, delta=True):
     return Layout(mp=mp, uc=uc, column_map=one_hop_exchange(mp, delta=delta))
 
 
+def split_transpose(mp, plp=False, delta=True):
+    """the kernel's rule of the same name: which instances move the transposition through the split-complex buffer"""
+    return not plp and not (mp == 16 and delta)
+
+
+def split_layout(mp=MP, uc=UC, delta=True, plp=False):
+    """(for any instance: the row table serves both lane -> column maps)"""
+    return Layout(mp=mp, uc=uc, k_wave=K_TS_WAVE, column_map=one_hop_exchange(mp, plp, delta), split=True, plp=plp)
+
+
+def tsplit_base(r, imag=False):
+    """float offset of row r (index k1 of the stores, column kc of the loads) in the wave's region: the kernel's tsplit_base. Slot
+    s = 0 .. 7 stands on bank quad 0, 1, 2, 3, 8, 9, 10, 11 and holds four rows of 64 floats: re, im of one of the rows 0 .. 3,
+    12 .. 15 and re, im of one of the rows 4 .. 11. One table for both lane -> column maps: lanes j = 0 .. 3, 12 .. 15 read rows 0 .. 3,
+    12 .. 15 (kc = j) or 0 .. 3, 13, 14, 15, 8 (KC), and either set meets every slot once."""
+    s = r if r < 4 else (r - 4 if r < 12 else r - 8)
+    b = 4 <= r < 12
+    return 256 * s + 4 * (s if s < 4 else s + 4) + (64 if b else 0) + (128 if imag else 0)
+
+
 def parent_layout(mp=MP, uc=UC):
     return Layout(mp=mp, uc=uc, k_lmel=64)
 
@@ -126,7 +161,7 @@ def lane_major_layout(mp=MP, uc=UC, **kw):
 
 
 def groups(kind):
-    if kind in ("r32", "w32", "r64"):
+    if kind in ("r32", "w32", "r64", "wtid"):
         return [list(range(0, 32)), list(range(32, 64))]
     if kind in ("w64", "r2_64"):
         return [list(range(16 * i, 16 * i + 16)) for i in range(4)]
@@ -138,14 +173,14 @@ def groups(kind):
     raise ValueError(kind)
 
 
-ARRAY_CYCLES = {"r32": 2, "w32": 2, "r64": 2, "w64": 4, "r128": 4, "bperm": 2}
-TRANSFER_CYCLES = {"w32": 4, "w64": 6}
+ARRAY_CYCLES = {"r32": 2, "w32": 2, "r64": 2, "w64": 4, "r128": 4, "bperm": 2, "wtid": 2}
+TRANSFER_CYCLES = {"w32": 4, "w64": 6, "wtid": 2}
 
 
 def cost(kind, addr_bytes, active=None):
     """extra cycles beyond the conflict-free cost for one wave instruction"""
-    nb = {"r32": 32, "w32": 32, "w64": 32, "r2_64": 32, "r64": 64, "r128": 64}[kind]
-    width = {"r32": 1, "w32": 1, "w64": 2, "r2_64": 2, "r64": 2, "r128": 4}[kind]
+    nb = {"r32": 32, "w32": 32, "wtid": 32, "w64": 32, "r2_64": 32, "r64": 64, "r128": 64}[kind]
+    width = {"r32": 1, "w32": 1, "wtid": 1, "w64": 2, "r2_64": 2, "r64": 2, "r128": 4}[kind]
     extra = 0
     for g in groups(kind):
         per_bank = {}
@@ -177,7 +212,24 @@ def column(layout):
 
 def wave_base(wave=0, layout=None):
     layout = layout or tree_layout()
-    return layout.shared + wave * layout.k_wave
+    return wave * layout.k_wave if layout.split else layout.shared + wave * layout.k_wave
+
+
+def table_base(layout):
+    """float offset of the shared tables"""
+    return 8 * layout.k_wave if layout.split else 0
+
+
+def transposition_split(wave=0, layout=None, base=tsplit_base):
+    """The split-complex buffer: per index k1 two ds_write_addtid_b32 (row k1 of the real and of the imaginary plane, address = wave
+    region + row base + lane) and per plane four ds_read_b128 (lane (g, kc): row base of kc + 16 g + 4 i) -> (extra cycles of the 32
+    stores, of the 8 loads). `base`: the row-base table (another one shows that the model sees it)."""
+    layout = layout or split_layout()
+    wb, kc = wave_base(wave, layout), column(layout)
+    st = sum(cost("wtid", 4 * (wb + base(k1, im) + lane)) for k1 in range(16) for im in (False, True))
+    rd = np.array([base(int(c)) for c in kc])
+    ld = sum(cost("r128", 4 * (wb + rd + 16 * g + 4 * i + (128 if im else 0))) for im in (False, True) for i in range(4))
+    return st, ld
 
 
 def transposition(store_order=TRANSPOSE_ORDER_R8, load_order=TRANSPOSE_ORDER_R8, wave=0, layout=None):
@@ -243,6 +295,7 @@ class Ledger:
 
 
 WINDOW, TW256, TR_WRITE, TR_READ, TW512 = "window read", "tw256 read", "transpose write b64", "transpose read b64", "tw512 read"
+TR_WRITE_SPLIT, TR_READ_SPLIT = "transpose write addtid b32", "transpose read b128"
 POWER_WRITE, MEL_POWER, MEL_WEIGHT = "power write b32", "mel power read b128", "mel weight read b128"
 BAND_WRITE, LMEL_READ, DCT_READ, BPERMUTE = "band vector write b32", "log-mel read b128", "dct read b128", "regression ds_bpermute"
 
@@ -254,6 +307,7 @@ def ledger(layout=None, wave=0, octets=None, n_mfcc=13, n_bands=26, delta=True):
     led = Ledger()
     wb = wave_base(wave, L)
     kc = column(L)                              # the lane's bins kc + 16 q: their twiddles and their places in the power buffer
+    tb = table_base(L)
     lmel = wb + g * L.k_lmel
     pb = wb + 4 * L.k_lmel + g * L.k_pb
     if octets is None:
@@ -262,7 +316,7 @@ def ledger(layout=None, wave=0, octets=None, n_mfcc=13, n_bands=26, delta=True):
     if delta:                                   # delta_fast: s1, s3, d1, d3, drow -- the crossbar, no bank
         led.add(BPERMUTE, "bperm", 0, 5)
     if L.lane_major:
-        tab = L.row * j                         # float offset of lane j's row: tw512 [16] | window | tw256 [32]
+        tab = tb + L.row * j                    # float offset of lane j's row: tw512 [16] | window | tw256 [32]
         # (a read whose second pair is never used -- the window's last at an odd MP, group 0's second of tw256, which ends in the
         # pair k1 = 0 -- is narrowed by the compiler to a ds_read_b64 of its first pair)
         for i in range((L.mp + 1) // 2):
@@ -272,20 +326,25 @@ def ledger(layout=None, wave=0, octets=None, n_mfcc=13, n_bands=26, delta=True):
             kind = "r64" if i == 1 else "r128"
             led.add(TW256, kind, cost(kind, 4 * (tab + 16 + L.win_floats + 4 * i)))
     else:
-        off_win, off_tw256 = 512, 512 + L.mp * 32
+        off_win, off_tw256 = tb + 512, tb + 512 + L.mp * 32
         for m in range(L.mp):
             led.add(WINDOW, "r64", cost("r64", 4 * (off_win + 2 * (m * 16 + j))))
         for k1 in range(1, 16):
             led.add(TW256, "r64", cost("r64", 4 * (off_tw256 + 2 * (k1 * 16 + j))))
-    s, l, _ = transposition(wave=wave, layout=L)
-    led.add(TR_WRITE, "w64", s, 16)
-    led.add(TR_READ, "r64", l, 16)
+    if L.split:
+        s, l = transposition_split(wave=wave, layout=L)
+        led.add(TR_WRITE_SPLIT, "wtid", s, 32)
+        led.add(TR_READ_SPLIT, "r128", l, 8)
+    else:
+        s, l, _ = transposition(wave=wave, layout=L)
+        led.add(TR_WRITE, "w64", s, 16)
+        led.add(TR_READ, "r64", l, 16)
     if L.lane_major:
         for i in range(4):
-            led.add(TW512, "r128", cost("r128", 4 * (L.row * j + 4 * i)))
+            led.add(TW512, "r128", cost("r128", 4 * (tb + L.row * j + 4 * i)))
     else:
         for q in range(8):
-            led.add(TW512, "r64", cost("r64", 4 * (2 * (kc + 16 * q))))
+            led.add(TW512, "r64", cost("r64", 4 * (tb + 2 * (kc + 16 * q))))
     for q in range(8):
         led.add(POWER_WRITE, "w32", cost("w32", 4 * (pb + pb_pos(kc, L.k_octet) + 2 * L.k_octet * q)))
         led.add(POWER_WRITE, "w32", cost("w32", 4 * (pb + pb_pos(256 - kc, L.k_octet) - 2 * L.k_octet * q)))
@@ -294,7 +353,7 @@ def ledger(layout=None, wave=0, octets=None, n_mfcc=13, n_bands=26, delta=True):
     for i in range(L.uc):
         a = pb + L.k_octet * octets[i][j]
         led.add(MEL_POWER, "r128", cost("r128", 4 * a) + cost("r128", 4 * (a + 4)), 2)
-        led.add(MEL_WEIGHT, "r128", cost("r128", 4 * (L.off_melw0 + 4 * (i * 16 + j))) + cost("r128", 4 * (L.off_melw1 + 4 * (i * 16 + j))), 2)
+        led.add(MEL_WEIGHT, "r128", cost("r128", 4 * (tb + L.off_melw0 + 4 * (i * 16 + j))) + cost("r128", 4 * (tb + L.off_melw1 + 4 * (i * 16 + j))), 2)
     # the lane's two bands (each lane owns other bands: 16 different dwords of 32 per frame group) and the pads up to 32
     led.add(BAND_WRITE, "w32", cost("w32", 4 * (lmel + j)))
     led.add(BAND_WRITE, "w32", cost("w32", 4 * (lmel + 16 + j), j + 16 < n_bands))
@@ -303,7 +362,7 @@ def ledger(layout=None, wave=0, octets=None, n_mfcc=13, n_bands=26, delta=True):
     act = j < n_mfcc
     for q in range(7):
         led.add(LMEL_READ, "r128", cost("r128", 4 * (lmel + 4 * q), act))
-        led.add(DCT_READ, "r128", cost("r128", 4 * (L.off_dct + j * 28 + 4 * q), act))
+        led.add(DCT_READ, "r128", cost("r128", 4 * (tb + L.off_dct + j * 28 + 4 * q), act))
     return led
 
 
@@ -365,7 +424,8 @@ def main():
     print("columns: instructions | conflict-free LDS-array cycles | conflict cycles | store transfer cycles | busy = max(transfer, array + conflicts)")
     cand = lane_major_layout()
     for title, L in (("parent layout (kLmelFloats 64, tables of pairs [index][lane], ds_read_b64)", parent_layout()),
-                     ("tree layout (kLmelFloats %d, tables of pairs [index][lane], ds_read_b64)" % K_LMEL, tree_layout()),
+                     ("interleaved transposition buffer (kLmelFloats %d, tables of pairs [index][lane], ds_read_b64)" % K_LMEL, tree_layout()),
+                     ("tree layout: split-complex transposition buffer, address-free stores, ds_read_b128", split_layout()),
                      ("candidate, measured and not taken (kLmelFloats %d, tables of pairs lane-major in rows of %d floats, ds_read_b128)"
                       % (K_LMEL, cand.row), cand)):
         per = [ledger(L, w).totals()["conflicts"] for w in range(8)]
@@ -373,6 +433,8 @@ def main():
         led = ledger(L, worst)
         print_ledger(f"{title}; wave {worst} of the block (the worst of the 8)", led)
         print("  conflict cycles per pass of the 8 waves of a block:", per)
+        if L.split:
+            print("  bytes of LDS per block:", {(mp, uc): 4 * (split_layout(mp, uc).shared + 8 * K_TS_WAVE) for mp in (13, 16) for uc in (6, 8)})
         print(f"  log-mel read b128 extra cycles {led.conflicts(LMEL_READ)}; mel power reads: the ledger's "
               f"{led.conflicts(MEL_POWER)} = 4 lane groups x 2 reads x the builder's own {BENCH_BUILDER_EXTRA} "
               "(SMILEHIP_DEBUG_TABLES: 'bank model: 2 extra cycles over 6 steps')")

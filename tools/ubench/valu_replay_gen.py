@@ -35,7 +35,7 @@ SRC = os.path.join(ROOT, "opensmile_amd", "csrc", "lld_mfcc512.hip")
 KERNEL = "_ZN8smilehip11lld_mfcc512ILi13ELb1ELb1ELb1ELb0ELi6ELb1EEEvNS_9LldParamsENS_13Fast512TablesE"
 FLAGS = ("--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-slp-vectorize -Xclang -target-feature "
          "-Xclang -load-store-opt --cuda-device-only -gline-tables-only -S").split()
-DFT_LINES = set(range(112, 123)) | set(range(131, 136)) | set(range(153, 173))   # dft4, cmul_ns, dft16_first / _twiddles / _last of lld_mfcc512.hip (innermost inlined location); cmul (124-128) is left
+DFT_LINES = set(range(140, 151)) | set(range(155, 165)) | set(range(173, 178)) | set(range(196, 218))   # dft4, dft4_z3, cmul_ns, dft16_first / _twiddles / _last of lld_mfcc512.hip (innermost inlined location); cmul (166-170) is left
 # in: the line tables cannot tell the 4 cmul inside a dft16 from the 15 twiddle products between the stages, which stay on the vector ALU
 
 
@@ -107,7 +107,7 @@ def main():
                 cur_file, cur_line = files.get(m.group(1), ""), int(m.group(2))
                 continue
             t = l.strip()
-            if t.startswith("ds_write_b64"):
+            if t.startswith(("ds_write_b64", "ds_write_addtid_b32")):       # the transposition's stores (interleaved / split-complex buffer)
                 seen_transpose_write = True
             if not t or t.startswith(";") or t.startswith("."):
                 continue
