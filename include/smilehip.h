@@ -62,7 +62,7 @@ typedef enum smilehip_winfunc {
 /* Parameters of the MFCC chain. Each group carries exactly the options the
  * corresponding reference component reads in myFetchConfig(). */
 typedef struct smilehip_lld_config {
-  uint32_t struct_size;        /* = sizeof(smilehip_lld_config) */
+  uint32_t struct_size;        /* = sizeof(smilehip_lld_config), or SMILEHIP_LLD_CONFIG_SIZE_V1 (see behind the struct) */
   /* cWaveSource (src/iocore/waveSource.cpp:190) + cFramer
    * (src/core/winToVecProcessor.cpp:435-456): frameMode=fixed,
    * frameCenterSpecial=left, noPostEOIprocessing=1 */
@@ -174,7 +174,28 @@ typedef struct smilehip_lld_config {
    * Appended last, in what was the struct's tail padding: struct_size is what it was, and a caller built before this field
    * existed, whose struct the presets zero first, passes 0. Only SMILEHIP_CHAIN_PROSODY_ACF reads it. */
   int32_t  acf_cep_use_power;
+  /* ---- everything below lies behind SMILEHIP_LLD_CONFIG_SIZE_V1 and is read only where struct_size covers it ----
+   * SMILEHIP_CHAIN_CHROMA_FFT: [tonespec:cTonespec] (src/lld/tonespec.cpp:89-117) and [chroma:cChroma] (src/lld/chroma.cpp:67-75).
+   * firstNote and silThresh are floats because the components keep them as FLOAT_DMEM (tonespec.cpp:96, chroma.cpp:71). */
+  int32_t  tonespec_n_octaves;          /* nOctaves: nNotes = 12 nOctaves outputs (1 .. 10) */
+  float    tonespec_first_note;         /* firstNote in Hz */
+  int32_t  tonespec_filter_type;        /* SMILEHIP_TONESPEC_GAUSS / _TRI / _TRI_POWERED / _RECT */
+  int32_t  tonespec_use_power;          /* usePower */
+  int32_t  tonespec_dba;                /* dbA */
+  int32_t  chroma_octave_size;          /* octaveSize: the chain's outputs; 12 nOctaves must be a multiple of it (1 .. 64) */
+  float    chroma_sil_thresh;           /* silThresh */
+  int32_t  reserved_chroma;             /* 0 */
 } smilehip_lld_config;
+/* struct_size rules. The struct only ever grows at its end. SMILEHIP_LLD_CONFIG_SIZE_V1 is its size up to and including
+ * acf_cep_use_power, i.e. sizeof(smilehip_lld_config) of every header before the chroma fields. The presets that existed then
+ * (everything but smilehip_config_chroma_fft) still zero and fill exactly that many bytes and set struct_size to it, so a caller
+ * compiled against such a header, whose struct ends there, is never written past its end. smilehip_plan_create accepts either
+ * size; fields a struct_size does not cover read as zero, and SMILEHIP_CHAIN_CHROMA_FFT requires the full size. */
+#define SMILEHIP_LLD_CONFIG_SIZE_V1 280u
+#define SMILEHIP_TONESPEC_GAUSS 0
+#define SMILEHIP_TONESPEC_TRI 1
+#define SMILEHIP_TONESPEC_TRI_POWERED 2
+#define SMILEHIP_TONESPEC_RECT 3
 
 #define SMILEHIP_CHAIN_MFCC 0
 #define SMILEHIP_CHAIN_IS09 1
@@ -222,6 +243,16 @@ typedef struct smilehip_lld_config {
  * points, a workgroup per frame otherwise), one thread per utterance for the contour, the window-chain kernel for the smoother.
  * smilehip_batch_prosody_acf_taps returns the levels in front of the smoother. */
 #define SMILEHIP_CHAIN_PROSODY_ACF 8
+/* SMILEHIP_CHAIN_CHROMA_FFT: the level `chroma` of config/chroma/chroma_fft.conf, what its one cCsvSink writes: chroma_octave_size
+ * (12) columns chroma[0] .. chroma[11] on 64 ms frames every 10 ms (frameCenterSpecial = left, noPostEOIprocessing = 1): gauss
+ * window (sigma 0.4), cTransformFFT zero-padded to a power of two, cFFTmagphase magnitudes, cTonespec (6 octaves from 55 Hz, gauss
+ * filters, usePower, dbA: src/lld/tonespec.cpp:171-441 with computeDBA, src/dsp/dbA.cpp:110-126; the bin width is
+ * (float)(1 / frameSizeSec) of the magnitude level, whose frameSizeSec cTransformFFT has scaled by Nfft / N,
+ * src/dspcore/transformFft.cpp:68-94) and cChroma (src/lld/chroma.cpp:86-118). Rows per utterance, as measured against the binary:
+ * (n - N) / H + 1 for n >= N samples, none below (chroma::rows_of, lld_chroma_ops.hpp). One frame kernel (lld_chroma_frame: a wave
+ * per frame for transforms of 512 / 1024 points, a workgroup per frame otherwise). smilehip_batch_chroma_taps returns the tonespec
+ * level. */
+#define SMILEHIP_CHAIN_CHROMA_FFT 9
 
 #define SMILEHIP_STAGE_WINDOW 1u
 #define SMILEHIP_STAGE_FFT    2u
@@ -300,6 +331,13 @@ void smilehip_config_prosody_shs(smilehip_lld_config *c);
  *   its default 0 = acf_cep_use_power 0 (:68-71, acf.cpp:91-102); [pitch:cPitchACF] maxPitch 500, voicingCutoff 0.55, voiceProb +
  *   F0 (:73-86); [smo:cContourSmoother] smaWin 3, noPostEOIprocessing 0 (:88-94) */
 void smilehip_config_prosody_acf(smilehip_lld_config *c);
+/* fills c -- the FULL struct, struct_size = sizeof(smilehip_lld_config) -- with config/chroma/chroma_fft.conf at this sample rate
+ * (chain_kind = CHROMA_FFT, 12 columns):
+ *   [framer:cFramer] 0.064 / 0.010 s, frameCenterSpecial = left, noPostEOIprocessing = 1 (:43-53); [windower:cWindower] Gau, sigma 0.4,
+ *   gain 1, offset 0 (:55-64); [transformFFT:cTransformFFT] (:66-72); [fFTmagphase:cFFTmagphase] magnitudes (:74-82);
+ *   [tonespec:cTonespec] nOctaves 6, firstNote 55, filterType gau, usePower 1, dbA 1 (:84-94); [chroma:cChroma] octaveSize 12 and
+ *   silThresh at its default 0.001 (:96-102, chroma.cpp:49) */
+void smilehip_config_chroma_fft(smilehip_lld_config *c, double sample_rate);
 
 /* F0 group, per component, on an F0 chain plan (smilehip_config_compare16_f0; the plan's spectrum geometry -- n_bins and
  * the level's frameSizeSec, force_fft_frame_size_sec -- must be the input level's):
@@ -323,6 +361,9 @@ int smilehip_batch_f0_taps(smilehip_batch *b, float *d_hps_dst, const float **d_
  * smilehip_lld_run of this batch filled, [total_frames x 3] = voiceProb | F0 (the contour) | pcm_loudness: the levels `pitch` and
  * `intens` in front of the smoother. n_frames (optional) receives total_frames. */
 int smilehip_batch_prosody_acf_taps(smilehip_batch *batch, float **d_raw3, int64_t *n_frames);
+/* chroma_fft chain tap (tests / diagnostics; SMILEHIP_CHAIN_CHROMA_FFT batches): device pointer to the level `tonespec` the last
+ * smilehip_lld_run of this batch filled, [total_frames x 12 tonespec_n_octaves], packed. n_frames (optional) receives total_frames. */
+int smilehip_batch_chroma_taps(smilehip_batch *batch, float **d_tonespec, int64_t *n_frames);
 /* Frames per utterance that cPitchSmootherViterbi had not decided when the input ended (they are flushed at the end of input:
  * src/lld/pitchSmootherViterbi.cpp:451-570), [n_utt] device ints filled by the last smilehip_lld_run of an F0 / ComParE / eGeMAPS
  * chain batch. Every end-of-input rule of the smoothed levels and the row counts the F0-group functionals see follow from it. */
@@ -1223,6 +1264,43 @@ int smilehip_specscale_op_destroy(smilehip_specscale_op *op);
  * and rec [n_tgt x 4] = a, c, d of smileMath_csplint_init and the auditory weight (1 where the weighting is off). */
 int smilehip_specscale_tables(const smilehip_specscale_opts *opts, int64_t n_src, double frame_size_sec, double *f_t, double *spline,
                               int32_t *k, double *rec);
+
+/* ---- cTonespec and cChroma per component (src/lld/tonespec.cpp, src/lld/chroma.cpp): the row functions of the fused chroma_fft chain
+ * (lld_chroma_ops.hpp) on n_frames independent rows, frame-major with leading dimensions. */
+typedef struct smilehip_tonespec_opts {
+  int32_t n_octaves;        /* nOctaves, 1 .. 10 */
+  float   first_note;       /* firstNote in Hz (a FLOAT_DMEM in the component) */
+  int32_t filter_type;      /* SMILEHIP_TONESPEC_* */
+  int32_t use_power, dba;
+} smilehip_tonespec_opts;
+typedef struct smilehip_tonespec_op smilehip_tonespec_op;
+/* cTonespec::setupNamesForField (tonespec.cpp:370-377: setPitchclassFreq, computeFilters) for n_src (2 .. 8192) magnitudes of a level
+ * whose frameSizeSec is frame_size_sec */
+int smilehip_tonespec_op_create(smilehip_context *ctx, const smilehip_tonespec_opts *opts, int64_t n_src, double frame_size_sec,
+                                smilehip_tonespec_op **out);
+int smilehip_tonespec_op_n_out(const smilehip_tonespec_op *op);       /* nNotes = 12 nOctaves */
+/* cTonespec::processVector (tonespec.cpp:390-441): rows of n_src magnitudes -> rows of n_out notes; one thread per note */
+int smilehip_tonespec_op_frames(smilehip_tonespec_op *op, const float *d_src, int64_t ld_src, float *d_dst, int64_t ld_dst,
+                                int64_t n_frames, void *stream);
+int smilehip_tonespec_op_destroy(smilehip_tonespec_op *op);
+/* The operator's host tables without a device: returns nNotes, or a negative value where smilehip_tonespec_op_create refuses. Every
+ * output is optional: pitch_class_freq [nNotes + 2]; bin_key [n_src]; nbins [nNotes + 2] (pitchClassNbins); filter_map [n_src]
+ * (with the first/last-bin cut and the dbA weights); note_rec [nNotes x 4] = first bin, bins, pitchClassNbins, 0 of output note k;
+ * first_last [2] = firstBin, lastBin */
+int smilehip_tonespec_op_tables(const smilehip_tonespec_opts *opts, int64_t n_src, double frame_size_sec, float *pitch_class_freq,
+                                int32_t *bin_key, int32_t *nbins, float *filter_map, int32_t *note_rec, int32_t *first_last);
+typedef struct smilehip_chroma_opts {
+  int32_t octave_size;      /* octaveSize, 1 .. 64 */
+  float   sil_thresh;       /* silThresh (a FLOAT_DMEM in the component) */
+} smilehip_chroma_opts;
+typedef struct smilehip_chroma_op smilehip_chroma_op;
+/* n_src values per row; an n_src that is no multiple of octaveSize is refused with SMILEHIP_ERR_INVALID (the component writes an
+ * error per frame and no values, chroma.cpp:113-115) */
+int smilehip_chroma_op_create(smilehip_context *ctx, const smilehip_chroma_opts *opts, int64_t n_src, smilehip_chroma_op **out);
+/* cChroma::processVector (chroma.cpp:86-118): rows of n_src tonespec values -> rows of octaveSize values; one thread per row */
+int smilehip_chroma_op_frames(smilehip_chroma_op *op, const float *d_src, int64_t ld_src, float *d_dst, int64_t ld_dst,
+                              int64_t n_frames, void *stream);
+int smilehip_chroma_op_destroy(smilehip_chroma_op *op);
 
 #ifdef __cplusplus
 }

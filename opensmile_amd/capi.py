@@ -136,6 +136,42 @@ def spectral_axis_opts(bands=(), rolloff=(), slopes=(), square_input=1, use_log_
     return o
 
 
+class LldConfigChroma(LldConfig):
+    """the full smilehip_lld_config: LldConfig (SMILEHIP_LLD_CONFIG_SIZE_V1 bytes, what every older preset fills and reports in
+    struct_size) and behind it the fields SMILEHIP_CHAIN_CHROMA_FFT reads. Every entry point that takes a LldConfig takes this."""
+    _fields_ = [("tonespec_n_octaves", C.c_int32), ("tonespec_first_note", C.c_float), ("tonespec_filter_type", C.c_int32),
+                ("tonespec_use_power", C.c_int32), ("tonespec_dba", C.c_int32), ("chroma_octave_size", C.c_int32),
+                ("chroma_sil_thresh", C.c_float), ("reserved_chroma", C.c_int32)]
+
+
+LLD_CONFIG_SIZE_V1 = 280
+TONESPEC_FILTER = {"gau": 0, "tri": 1, "trp": 2, "rec": 3}          # SMILEHIP_TONESPEC_*
+
+
+class TonespecOpts(C.Structure):
+    """smilehip_tonespec_opts"""
+    _fields_ = [("n_octaves", C.c_int32), ("first_note", C.c_float), ("filter_type", C.c_int32), ("use_power", C.c_int32), ("dba", C.c_int32)]
+
+
+class ChromaOpts(C.Structure):
+    """smilehip_chroma_opts"""
+    _fields_ = [("octave_size", C.c_int32), ("sil_thresh", C.c_float)]
+
+
+def tonespec_opts(n_octaves=6, first_note=55.0, filter_type="gau", use_power=1, dba=1):
+    o = TonespecOpts()
+    o.n_octaves, o.first_note = int(n_octaves), float(first_note)
+    o.filter_type = TONESPEC_FILTER[filter_type] if isinstance(filter_type, str) else int(filter_type)
+    o.use_power, o.dba = int(use_power), int(dba)
+    return o
+
+
+def chroma_opts(octave_size=12, sil_thresh=0.001):
+    o = ChromaOpts()
+    o.octave_size, o.sil_thresh = int(octave_size), float(sil_thresh)
+    return o
+
+
 class SpecScaleOpts(C.Structure):
     """smilehip_specscale_opts (include/smilehip.h): cSpecScale on any target scale"""
     _fields_ = [("scale", C.c_int32), ("param", C.c_double), ("min_f", C.c_double), ("max_f", C.c_double), ("n_points_target", C.c_int32),
@@ -175,6 +211,16 @@ SYMBOLS = {
     "smilehip_config_prosody_shs": (None, [C.POINTER(LldConfig)]),
     "smilehip_config_prosody_acf": (None, [C.POINTER(LldConfig)]),
     "smilehip_batch_prosody_acf_taps": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "smilehip_config_chroma_fft": (None, [C.POINTER(LldConfigChroma), _dbl]),
+    "smilehip_batch_chroma_taps": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "smilehip_tonespec_op_create": (C.c_int, [_vp, _vp, _i64, _dbl, _vp]),
+    "smilehip_tonespec_op_n_out": (C.c_int, [_vp]),
+    "smilehip_tonespec_op_frames": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp]),
+    "smilehip_tonespec_op_destroy": (C.c_int, [_vp]),
+    "smilehip_tonespec_op_tables": (C.c_int, [_vp, _i64, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "smilehip_chroma_op_create": (C.c_int, [_vp, _vp, _i64, _vp]),
+    "smilehip_chroma_op_frames": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp]),
+    "smilehip_chroma_op_destroy": (C.c_int, [_vp]),
     "smilehip_config_htk_variant": (C.c_int, [C.POINTER(LldConfig), C.c_char_p]),
     "smilehip_config_compare16": (None, [C.POINTER(LldConfig)]),
     "smilehip_specscale_frames": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp]),
@@ -555,6 +601,29 @@ def prosody_acf_config():
     return c
 
 
+CHAIN_CHROMA_FFT = 9
+
+
+def chroma_fft_config(sample_rate=16000.0):
+    """config/chroma/chroma_fft.conf (chain_kind = CHROMA_FFT): chroma[0] .. chroma[11]; the full struct (LldConfigChroma)"""
+    c = LldConfigChroma()
+    load().smilehip_config_chroma_fft(C.byref(c), float(sample_rate))
+    return c
+
+
+def tonespec_tables(opts, n_src, frame_size_sec):
+    """smilehip_tonespec_op_tables: dict of pitch_class_freq, bin_key, nbins, filter_map, note_rec [n_notes x 4], first_last"""
+    L = load()
+    n = L.smilehip_tonespec_op_tables(C.byref(opts), n_src, frame_size_sec, None, None, None, None, None, None)
+    if n < 0:
+        raise RuntimeError(L.smilehip_last_error().decode())
+    t = dict(pitch_class_freq=np.zeros(n + 2, np.float32), bin_key=np.zeros(n_src, np.int32), nbins=np.zeros(n + 2, np.int32),
+             filter_map=np.zeros(n_src, np.float32), note_rec=np.zeros((n, 4), np.int32), first_last=np.zeros(2, np.int32))
+    assert L.smilehip_tonespec_op_tables(C.byref(opts), n_src, frame_size_sec, *(t[k].ctypes.data for k in (
+        "pitch_class_freq", "bin_key", "nbins", "filter_map", "note_rec", "first_last"))) == n
+    return t
+
+
 def funcspec_compare16(instance):
     """One of ComParE_2016's six cFunctionals instances: "A", "B", "F0", "Nz", "LLD", "Delta"."""
     s = FuncSpec()
@@ -904,6 +973,41 @@ class Batch:
                 _check(L.smilehip_copy_to_host(ctx, out.ctypes.data, d_out, out.nbytes, None))
             if tap.nbytes:
                 _check(L.smilehip_copy_to_host(ctx, tap.ctypes.data, d_raw3, tap.nbytes, None))
+        finally:
+            L.smilehip_free(ctx, d_pcm)
+            L.smilehip_free(ctx, d_out)
+        return out, tap
+
+    def chroma_run_host(self, pcm, ld_out=None, fill=0.0, runs=1):
+        """chroma_fft chain plans: run on host data (int16 samples through smilehip_lld_run, a float32 array through
+        smilehip_lld_run_f32) into a matrix [total_rows x ld_out] that held `fill` everywhere before, `runs` times over.
+        Returns it and the tap [total_frames x n_notes], the level tonespec (smilehip_batch_chroma_taps)."""
+        L = load()
+        ctx = self.plan.ctx._h
+        n_notes = 12 * self.plan.cfg.tonespec_n_octaves
+        ld_out = self.plan.geometry.n_out if ld_out is None else ld_out
+        f32 = np.asarray(pcm).dtype == np.float32
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32 if f32 else np.int16)
+        out = np.full((self.total_rows, ld_out), fill, np.float32)
+        tap = np.zeros((self.total_frames, n_notes), np.float32)
+        d_pcm, d_out = _vp(), _vp()
+        _check(L.smilehip_alloc(ctx, max(pcm.nbytes, 4), C.byref(d_pcm)))
+        _check(L.smilehip_alloc(ctx, max(out.nbytes, 4), C.byref(d_out)))
+        try:
+            if pcm.nbytes:
+                _check(L.smilehip_copy_to_device(ctx, d_pcm, pcm.ctypes.data, pcm.nbytes, None))
+            if out.nbytes:
+                _check(L.smilehip_copy_to_device(ctx, d_out, out.ctypes.data, out.nbytes, None))
+            for _ in range(runs):
+                _check((L.smilehip_lld_run_f32 if f32 else L.smilehip_lld_run)(self.plan._h, self._h, d_pcm, d_out, ld_out, None))
+            _check(L.smilehip_stream_synchronize(ctx, None))
+            d_ts, nf = _vp(), _i64(0)
+            _check(L.smilehip_batch_chroma_taps(self._h, C.byref(d_ts), C.byref(nf)))
+            assert nf.value == self.total_frames
+            if out.nbytes:
+                _check(L.smilehip_copy_to_host(ctx, out.ctypes.data, d_out, out.nbytes, None))
+            if tap.nbytes:
+                _check(L.smilehip_copy_to_host(ctx, tap.ctypes.data, d_ts, tap.nbytes, None))
         finally:
             L.smilehip_free(ctx, d_pcm)
             L.smilehip_free(ctx, d_out)

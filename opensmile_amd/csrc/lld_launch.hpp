@@ -72,6 +72,15 @@ hipError_t launch_prosody_tail(const ProsodyParams &R, hipStream_t s);
 // cPitchACF's contour in place on its pitch column (lld_prosody_acf.hip). P.frame_utt is required.
 hipError_t launch_prosody_acf(const LldParams &P, const ProsodyAcfParams &Q, hipStream_t s);
 int prosody_acf_wave_frames();      // frames per workgroup of the wave form
+// chroma_fft.conf: lld_chroma_frame (wave per frame for Nfft 512 / 1024, workgroup per frame otherwise) writes Q.tonespec and the
+// chain's rows P.out (lld_chroma.hip). P.frame_utt is required.
+hipError_t launch_chroma(const LldParams &P, const ChromaParams &Q, hipStream_t s);
+int64_t chroma_wave_grid_cap(int n_cu, int64_t lds_bytes);   // workgroups of the wave form a device of n_cu CUs gets at most
+// cTonespec / cChroma per component (smilehip_tonespec_op_frames / smilehip_chroma_op_frames): strided rows
+hipError_t stage_tonespec(const float *fmap, const chroma::NoteRec *rec, int n_src, int n_notes, int use_power, const float *src, int64_t ld_src,
+                          float *dst, int64_t ld_dst, int64_t n_frames, hipStream_t s);
+hipError_t stage_chroma(int n_src, int octave_size, float sil_thresh, const float *src, int64_t ld_src, float *dst, int64_t ld_dst,
+                        int64_t n_frames, hipStream_t s);
 int f0_chunk_tiles();
 int f0_tile_frames();
 // cPitchSmootherViterbi as a stream: one frame (or the flush) per launch, state in global memory

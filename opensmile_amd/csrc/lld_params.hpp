@@ -1,6 +1,7 @@
 // Kernel parameter block shared by the host API (smilehip_*.cpp) and the device
 // code (lld_kernels.hip). Plain data, passed by value at launch.
 #pragma once
+#include "lld_chroma_ops.hpp"
 #include "lld_device.hpp"
 #include "lld_ooura.hpp"
 #include "lld_ooura_wave.hpp"
@@ -196,6 +197,17 @@ struct ProsodyAcfParams {
   double maxPitch;
   double voicingCutoff;             // clamped to [0, 1] (pitchACF.cpp:96-98)
   double win0, win_sum;             // cIntensity: the Hamming window's first value and its sum in index order (intensity.cpp:99-104)
+};
+
+// chroma_fft.conf (lld_chroma.hip, lld_chroma_ops.hpp): extra parameters of lld_chroma_frame next to LldParams (batch, geometry, window,
+// transform tables; nothing of the mel / DCT part is read)
+struct ChromaParams {
+  float *tonespec;                  // [total_frames x n_notes] the level tonespec (smilehip_batch_chroma_taps), packed
+  const float *fmap;                // [K] cTonespec's filterMap
+  const chroma::NoteRec *rec;       // [n_notes] the run of bins of each note
+  int32_t n_notes, use_power;
+  int32_t octave_size;              // the chain's outputs per frame
+  float sil_thresh;
 };
 
 // eGeMAPSv02 / GeMAPSv01b LLD level (lld_gemaps.hip): per-frame scratch and constants

@@ -53,6 +53,15 @@ static int alloc_prosody_acf_scratch(smilehip_batch *b, const BatchLayout &L) {
   return SMILEHIP_OK;
 }
 
+// chroma_fft: the utterance of every frame, and the level tonespec
+static int alloc_chroma_scratch(smilehip_plan *plan, smilehip_batch *b, const BatchLayout &L) {
+  int rc;
+  if (b->total_frames > 0 && (rc = b->d_frame_utt.upload(L.frame_utt))) return rc;
+  if (b->d_tonespec.alloc(at_least_one(b->total_frames) * (size_t)plan->tonespec.n_notes))
+    return fail(SMILEHIP_ERR_HIP, "hipMalloc of the chroma_fft scratch matrix failed");
+  return SMILEHIP_OK;
+}
+
 static int alloc_compare_ab_scratch(smilehip_batch *b, const BatchLayout &L) {
   int rc;
   b->n_runs = (int32_t)L.run_utt.size();
@@ -171,6 +180,7 @@ extern "C" int smilehip_batch_create(smilehip_plan *plan, const int64_t *h_off, 
     case SMILEHIP_CHAIN_COMPARE_F0: rc = alloc_f0_scratch(plan, b.get(), L); break;
     case SMILEHIP_CHAIN_PROSODY_SHS: rc = alloc_f0_frame_scratch(plan, b.get()); break;   // (no Viterbi, no jitter pass: their vectors stay empty)
     case SMILEHIP_CHAIN_PROSODY_ACF: rc = alloc_prosody_acf_scratch(b.get(), L); break;
+    case SMILEHIP_CHAIN_CHROMA_FFT: rc = alloc_chroma_scratch(plan, b.get(), L); break;
     case SMILEHIP_CHAIN_COMPARE: rc = alloc_compare_scratch(plan, b.get(), L); break;
     case SMILEHIP_CHAIN_EGEMAPS: rc = alloc_egemaps_scratch(plan, b.get(), L); break;
     case SMILEHIP_CHAIN_MFCC:
@@ -467,6 +477,32 @@ static int prosody_acf_run(smilehip_plan *plan, smilehip_batch *b, const int16_t
   Q.out_col[0] = 0;
   e = launch_chain(Q, s);
   if (e != hipSuccess) return fail(SMILEHIP_ERR_HIP, "window-chain kernel launch failed: %s", hipGetErrorString(e));
+  return timing_mark(plan, 2, s);
+}
+
+// SMILEHIP_CHAIN_CHROMA_FFT: one launch of lld_chroma_frame writes the tonespec level into the scratch and the chroma rows into d_out
+static int chroma_run(smilehip_plan *plan, smilehip_batch *b, const int16_t *d_pcm, float *d_out, int64_t ld_out, void *stream) {
+  const int n_out = plan->cfg.chroma_octave_size;
+  if (ld_out < n_out) return fail(SMILEHIP_ERR_INVALID, "ld_out %lld < n_out %d", (long long)ld_out, n_out);
+  if (b->total_frames == 0) return SMILEHIP_OK;
+  if (!d_pcm || !d_out) return fail(SMILEHIP_ERR_INVALID, "smilehip_lld_run: null device pointer");
+  hipStream_t s = (hipStream_t)stream;
+  LldParams P;
+  fill_params(plan, b, d_pcm, d_out, ld_out, P);
+  ChromaParams Q;
+  std::memset(&Q, 0, sizeof(Q));
+  Q.tonespec = b->d_tonespec.p;
+  Q.fmap = plan->d_ts_fmap.p;
+  Q.rec = plan->d_ts_rec.p;
+  Q.n_notes = plan->tonespec.n_notes;
+  Q.use_power = plan->cfg.tonespec_use_power != 0;
+  Q.octave_size = n_out;
+  Q.sil_thresh = plan->cfg.chroma_sil_thresh;
+  int trc;
+  if ((trc = timing_mark(plan, 0, s))) return trc;
+  hipError_t e = launch_chroma(P, Q, s);
+  if (e != hipSuccess) return fail(SMILEHIP_ERR_HIP, "chroma_fft kernel launch failed: %s", hipGetErrorString(e));
+  if ((trc = timing_mark(plan, 1, s))) return trc;
   return timing_mark(plan, 2, s);
 }
 
@@ -835,6 +871,15 @@ extern "C" int smilehip_batch_prosody_acf_taps(smilehip_batch *b, float **d_raw3
   return SMILEHIP_OK;
 }
 
+// chroma_fft chain tap: the level tonespec of the last run, [total_frames x n_notes]
+extern "C" int smilehip_batch_chroma_taps(smilehip_batch *b, float **d_tonespec, int64_t *n_frames) {
+  if (!b || b->plan->cfg.chain_kind != SMILEHIP_CHAIN_CHROMA_FFT)
+    return fail(SMILEHIP_ERR_INVALID, "smilehip_batch_chroma_taps: not a chroma_fft chain batch");
+  if (d_tonespec) *d_tonespec = b->d_tonespec.p;
+  if (n_frames) *n_frames = b->total_frames;
+  return SMILEHIP_OK;
+}
+
 // Test/diagnostic taps of the F0 chain: device pointers to the per-frame scratch of the LAST run
 // (candidates: total_frames x 21, level is13_pitchShsG60; energy: total_frames, level is13_e60) and an optional
 // destination for the octave-scaled spectra (total_frames x K, level is13_hpsG60; pass NULL to switch it off).
@@ -914,6 +959,7 @@ extern "C" int smilehip_lld_run(smilehip_plan *plan, smilehip_batch *b, const in
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE_F0) return f0_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_SHS) return prosody_shs_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_ACF) return prosody_acf_run(plan, b, d_pcm, d_out, ld_out, stream);
+  if (plan->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT) return chroma_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE) return compare_full_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_EGEMAPS) return egemaps_run(plan, b, d_pcm, d_out, ld_out, stream);
   return is09_run(plan, b, d_pcm, d_out, ld_out, stream);

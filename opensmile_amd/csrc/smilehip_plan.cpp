@@ -1,9 +1,15 @@
 // libsmilehip, C ABI part 2: configuration presets, plan creation (host tables -> device), plan getters.
 #include "smilehip_internal.hpp"
 
+static_assert(offsetof(smilehip_lld_config, acf_cep_use_power) + sizeof(int32_t) == SMILEHIP_LLD_CONFIG_SIZE_V1,
+              "SMILEHIP_LLD_CONFIG_SIZE_V1 is the struct's size up to and including acf_cep_use_power");
+static_assert(offsetof(smilehip_lld_config, tonespec_n_octaves) == SMILEHIP_LLD_CONFIG_SIZE_V1, "the chroma fields start where the older struct ends");
+
+// the base of every preset that existed before the struct grew: it fills SMILEHIP_LLD_CONFIG_SIZE_V1 bytes and says so in struct_size (the
+// header's struct_size rules: a caller whose struct ends there is not written past its end)
 extern "C" void smilehip_config_mfcc12_0_d_a(smilehip_lld_config *c) {
-  std::memset(c, 0, sizeof(*c));
-  c->struct_size = sizeof(*c);
+  std::memset(c, 0, SMILEHIP_LLD_CONFIG_SIZE_V1);
+  c->struct_size = SMILEHIP_LLD_CONFIG_SIZE_V1;
   c->sample_rate = 16000.0;
   c->frame_size_sec = 0.0250;
   c->frame_step_sec = 0.010;
@@ -179,18 +185,48 @@ extern "C" void smilehip_config_prosody_acf(smilehip_lld_config *c) {
   c->sma_win = 3;                    // [smo:cContourSmoother] smaWin = 3
 }
 
+// config/chroma/chroma_fft.conf: the full struct
+extern "C" void smilehip_config_chroma_fft(smilehip_lld_config *c, double sample_rate) {
+  std::memset(c, 0, sizeof(*c));
+  smilehip_config_mfcc12_0_d_a(c);   // (the mel / DCT fields are not read by this chain)
+  c->struct_size = sizeof(*c);
+  c->chain_kind = SMILEHIP_CHAIN_CHROMA_FFT;
+  c->sample_rate = sample_rate;
+  c->frame_size_sec = 0.064;         // [framer:cFramer] frameSize = 0.064, frameStep = 0.010
+  c->frame_step_sec = 0.010;
+  c->preemph = 0;
+  c->win_func = SMILEHIP_WIN_GAUSS;  // [windower:cWindower] winFunc = Gau, sigma = 0.4, gain = 1, offset = 0
+  c->win_sigma = 0.4;
+  c->zero_pad_symmetric = 1;         // [transformFFT:cTransformFFT] sets nothing: the component's default
+  c->n_delta = 0;
+  c->tonespec_n_octaves = 6;         // [tonespec:cTonespec]
+  c->tonespec_first_note = 55.0f;
+  c->tonespec_filter_type = SMILEHIP_TONESPEC_GAUSS;
+  c->tonespec_use_power = 1;
+  c->tonespec_dba = 1;
+  c->chroma_octave_size = 12;        // [chroma:cChroma]
+  c->chroma_sil_thresh = (float)0.001;   // the default (chroma.cpp:49), kept as FLOAT_DMEM (:71)
+}
+
 static inline bool is_compare_ab_like(const smilehip_lld_config &c) {
   return c.chain_kind == SMILEHIP_CHAIN_COMPARE_AB || c.chain_kind == SMILEHIP_CHAIN_COMPARE;
 }
 
 // ------------------------------------------------------------------- plan
+// the caller's struct as far as its struct_size reaches (the header's struct_size rules), zeros behind it
+static void copy_config(smilehip_lld_config &dst, const smilehip_lld_config *src) {
+  std::memset(&dst, 0, sizeof(dst));
+  std::memcpy(&dst, src, std::min<size_t>(src->struct_size, sizeof(dst)));
+}
+
 static int build_tables(smilehip_plan *p, bool upload = true) {
   int rc;
   if ((rc = make_geometry(p->cfg, p->geo)) != SMILEHIP_OK) return fail(rc, "invalid framing parameters");
   if (p->geo.Nfft > 8192) return fail(SMILEHIP_ERR_INVALID, "FFT length %lld > 8192 unsupported", (long long)p->geo.Nfft);
   const uint32_t mask = p->cfg.stage_mask ? p->cfg.stage_mask : SMILEHIP_STAGE_ALL;
   // the tables built: the prosodyAcf chain has no mel bank and no DCT (its frames may be shorter than a bank has bands)
-  const uint32_t tmask = p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_ACF ? (mask & ~(SMILEHIP_STAGE_MEL | SMILEHIP_STAGE_MFCC)) : mask;
+  const bool no_mel = p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_ACF || p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT;   // (chroma_fft likewise)
+  const uint32_t tmask = no_mel ? (mask & ~(SMILEHIP_STAGE_MEL | SMILEHIP_STAGE_MFCC)) : mask;
   p->h_window.assign(size_t(p->geo.N), 1.0f);
   if ((mask & SMILEHIP_STAGE_WINDOW) && (rc = make_window(p->cfg, p->geo.N, p->h_window)) != SMILEHIP_OK)
     return fail(rc, "unknown window function %d", p->cfg.win_func);
@@ -257,6 +293,30 @@ static int build_tables(smilehip_plan *p, bool upload = true) {
     if (p->geo.Nfft < 64 || p->geo.Nfft > 8192)
       return fail(SMILEHIP_ERR_INVALID, "prosodyAcf chain: the transform length must be 64 .. 8192 points; frame_size_sec at this sample_rate gives %lld",
                   (long long)p->geo.Nfft);
+  } else if (p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT) {
+    // everything the chain cannot express is refused with the option named
+    const smilehip_lld_config &c = p->cfg;
+    if (c.struct_size < sizeof(smilehip_lld_config))
+      return fail(SMILEHIP_ERR_INVALID, "chroma_fft chain: struct_size %u does not cover the tonespec / chroma fields (%zu)", c.struct_size, sizeof(smilehip_lld_config));
+    if (mask != SMILEHIP_STAGE_ALL) return fail(SMILEHIP_ERR_INVALID, "chroma_fft chain: stage_mask must be all stages");
+    if (c.n_delta != 0) return fail(SMILEHIP_ERR_INVALID, "chroma_fft chain: n_delta must be 0 (the file has no cDeltaRegression); got %d", c.n_delta);
+    if (c.preemph) return fail(SMILEHIP_ERR_INVALID, "chroma_fft chain: preemph must be 0 (the file has no cVectorPreemphasis)");
+    if (c.win_offset != 0.0) return fail(SMILEHIP_ERR_INVALID, "chroma_fft chain: win_offset must be 0");
+    if (p->geo.Nfft < 64 || p->geo.Nfft > 8192)
+      return fail(SMILEHIP_ERR_INVALID, "chroma_fft chain: the transform length must be 64 .. 8192 points; frame_size_sec at this sample_rate gives %lld",
+                  (long long)p->geo.Nfft);
+    if (c.chroma_octave_size < 1 || c.chroma_octave_size > chroma::kMaxOctaveSize)
+      return fail(SMILEHIP_ERR_INVALID, "chroma_fft chain: chroma_octave_size (cChroma octaveSize) must be 1 .. %d; got %d", chroma::kMaxOctaveSize, c.chroma_octave_size);
+    if (c.tonespec_n_octaves < 1 || c.tonespec_n_octaves * 12 > chroma::kMaxNotes)
+      return fail(SMILEHIP_ERR_INVALID, "chroma_fft chain: tonespec_n_octaves (cTonespec nOctaves) must be 1 .. %d; got %d", chroma::kMaxNotes / 12, c.tonespec_n_octaves);
+    if ((c.tonespec_n_octaves * 12) % c.chroma_octave_size)
+      return fail(SMILEHIP_ERR_INVALID, "chroma_fft chain: 12 tonespec_n_octaves = %d notes are no multiple of chroma_octave_size %d (cChroma writes no values then)",
+                  c.tonespec_n_octaves * 12, c.chroma_octave_size);
+    if (!(c.chroma_sil_thresh == c.chroma_sil_thresh)) return fail(SMILEHIP_ERR_INVALID, "chroma_fft chain: chroma_sil_thresh is not a number");
+    const smilehip_tonespec_opts to = {c.tonespec_n_octaves, c.tonespec_first_note, c.tonespec_filter_type, c.tonespec_use_power, c.tonespec_dba};
+    const char *why = "";
+    if ((rc = make_tonespec_tables(to, p->geo.K, p->geo.fft_frame_size_sec, p->tonespec, &why)))
+      return fail(rc, "chroma_fft chain: cTonespec (tonespec_*): %s", why);
   } else if (p->cfg.chain_kind != SMILEHIP_CHAIN_MFCC) {
     return fail(SMILEHIP_ERR_INVALID, "unknown chain_kind %d", p->cfg.chain_kind);
   }
@@ -314,6 +374,8 @@ static int build_tables(smilehip_plan *p, bool upload = true) {
   // (shorter frames: a plan that windows, frames or pre-emphasises only; what would transform refuses it, require_transform)
   if (p->geo.Nfft >= 64 && (rc = p->oo.build((int)p->geo.Nfft, true))) return rc;
   if (is_plp && ((rc = p->d_plp_eql.upload(plp_eql)) || (rc = p->d_plp_cos.upload(p->h_plp_cos)) || (rc = p->d_plp_sin.upload(plp_sin))))
+    return rc;
+  if (p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT && ((rc = p->d_ts_fmap.upload(p->tonespec.filter_map)) || (rc = p->d_ts_rec.upload(p->tonespec.rec))))
     return rc;
   if (f0_front_chain(p->cfg.chain_kind) &&
       ((rc = p->d_f0_rec.upload(p->f0.sp_rec)) || (rc = p->d_f0_d1.upload(p->f0.sp_d1)) || (rc = p->d_f0_d2.upload(p->f0.sp_d2)) ||
@@ -506,14 +568,14 @@ static int build_tables(smilehip_plan *p, bool upload = true) {
 extern "C" int smilehip_plan_create(smilehip_context *ctx, const smilehip_lld_config *cfg, smilehip_plan **out) {
   if (!ctx || !cfg || !out) return fail(SMILEHIP_ERR_INVALID, "smilehip_plan_create: null argument");
   *out = nullptr;
-  if (cfg->struct_size != sizeof(smilehip_lld_config))
+  if (cfg->struct_size != sizeof(smilehip_lld_config) && cfg->struct_size != SMILEHIP_LLD_CONFIG_SIZE_V1)
     return fail(SMILEHIP_ERR_INVALID, "smilehip_lld_config.struct_size %u != %zu (ABI mismatch)", cfg->struct_size,
                 sizeof(smilehip_lld_config));
   HIP_TRY(hipSetDevice(ctx->device));
   auto *p = new (std::nothrow) smilehip_plan();
   if (!p) return fail(SMILEHIP_ERR_NOMEM, "out of host memory");
   p->ctx = ctx;
-  p->cfg = *cfg;
+  copy_config(p->cfg, cfg);
   const char *fg = getenv("SMILEHIP_FORCE_GENERIC");
   p->force_generic = (fg && fg[0] == '1') ? 1 : 0;
   int rc = build_tables(p);
@@ -572,12 +634,12 @@ extern "C" int smilehip_plan_create(smilehip_context *ctx, const smilehip_lld_co
 extern "C" int smilehip_plan_create_host_only(const smilehip_lld_config *cfg, smilehip_plan **out) {
   if (!cfg || !out) return fail(SMILEHIP_ERR_INVALID, "smilehip_plan_create_host_only: null argument");
   *out = nullptr;
-  if (cfg->struct_size != sizeof(smilehip_lld_config))
+  if (cfg->struct_size != sizeof(smilehip_lld_config) && cfg->struct_size != SMILEHIP_LLD_CONFIG_SIZE_V1)
     return fail(SMILEHIP_ERR_INVALID, "smilehip_lld_config.struct_size %u != %zu (ABI mismatch)", cfg->struct_size,
                 sizeof(smilehip_lld_config));
   auto *p = new (std::nothrow) smilehip_plan();
   if (!p) return fail(SMILEHIP_ERR_NOMEM, "out of host memory");
-  p->cfg = *cfg;
+  copy_config(p->cfg, cfg);
   int rc = build_tables(p, false);
   if (rc != SMILEHIP_OK) {
     delete p;
@@ -592,6 +654,7 @@ extern "C" void smilehip_plan_destroy(smilehip_plan *plan) { delete plan; }
 int plan_n_static(const smilehip_plan *p) {
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE_F0) return 2;
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_SHS || p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_ACF) return 3;
+  if (p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT) return p->cfg.chroma_octave_size;
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE) return 65;
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_EGEMAPS) return 25;
   return p->cfg.chain_kind == SMILEHIP_CHAIN_IS09 ? 16
@@ -633,7 +696,7 @@ extern "C" double smilehip_row_time(const smilehip_plan *plan, int64_t n_frames,
   // prosodyShs: the rows carry the time stamps of cPitchSmoother's level, whose frame j has that of input frame j + 1
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_SHS)
     return smilehip_frame_time(plan, n_frames >= 2 ? (row < n_frames - 2 ? row : n_frames - 2) + 1 : 0);
-  if (plan->cfg.chain_kind == SMILEHIP_CHAIN_MFCC || plan->cfg.chain_kind == SMILEHIP_CHAIN_PLP ||
+  if (plan->cfg.chain_kind == SMILEHIP_CHAIN_MFCC || plan->cfg.chain_kind == SMILEHIP_CHAIN_PLP || plan->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT ||
       plan->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE_F0 || plan->cfg.chain_kind == SMILEHIP_CHAIN_EGEMAPS || n_frames <= 1)
     return smilehip_frame_time(plan, row);
   // IS09 and prosodyAcf (lld_prosody_acf_ops.hpp: row_time_frame): the smoother's end-of-input rows repeat the last frame's time

@@ -237,6 +237,86 @@ extern "C" int smilehip_specscale_op_frames(smilehip_specscale_op *op, const flo
   STAGE_RET(stage_specscale_general(op->S, d_src, ld_src, d_dst, ld_dst, n_frames, (hipStream_t)stream), "specscale (general)");
 }
 
+// ---- cTonespec and cChroma per component: the row functions of the fused chroma_fft chain (lld_chroma_ops.hpp) on strided rows
+struct smilehip_tonespec_op {
+  smilehip_context *ctx = nullptr;
+  int32_t n_src = 0, n_notes = 0, use_power = 0;
+  DevBuf<float> d_fmap;
+  DevBuf<chroma::NoteRec> d_rec;
+};
+extern "C" int smilehip_tonespec_op_destroy(smilehip_tonespec_op *op) {
+  delete op;
+  return SMILEHIP_OK;
+}
+extern "C" int smilehip_tonespec_op_n_out(const smilehip_tonespec_op *op) { return op ? op->n_notes : -1; }
+extern "C" int smilehip_tonespec_op_tables(const smilehip_tonespec_opts *o, int64_t n_src, double frame_size_sec, float *pitch_class_freq,
+                                           int32_t *bin_key, int32_t *nbins, float *filter_map, int32_t *note_rec, int32_t *first_last) {
+  if (!o) return fail(SMILEHIP_ERR_INVALID, "smilehip_tonespec_op_tables: null argument");
+  TonespecHost h;
+  const char *why = "";
+  const int rc = make_tonespec_tables(*o, n_src, frame_size_sec, h, &why);
+  if (rc) return fail(rc, "cTonespec (%lld bins, frame size %g s): %s", (long long)n_src, frame_size_sec, why);
+  if (pitch_class_freq) std::memcpy(pitch_class_freq, h.pitch_class_freq.data(), h.pitch_class_freq.size() * sizeof(float));
+  if (bin_key) std::memcpy(bin_key, h.bin_key.data(), h.bin_key.size() * sizeof(int32_t));
+  if (nbins) std::memcpy(nbins, h.nbins.data(), h.nbins.size() * sizeof(int32_t));
+  if (filter_map) std::memcpy(filter_map, h.filter_map.data(), h.filter_map.size() * sizeof(float));
+  if (note_rec) std::memcpy(note_rec, h.rec.data(), h.rec.size() * sizeof(chroma::NoteRec));
+  if (first_last) { first_last[0] = h.first_bin; first_last[1] = h.last_bin; }
+  return h.n_notes;
+}
+extern "C" int smilehip_tonespec_op_create(smilehip_context *ctx, const smilehip_tonespec_opts *o, int64_t n_src, double frame_size_sec,
+                                           smilehip_tonespec_op **out) {
+  if (!ctx || !o || !out) return fail(SMILEHIP_ERR_INVALID, "smilehip_tonespec_op_create: null argument");
+  TonespecHost h;
+  const char *why = "";
+  int rc = make_tonespec_tables(*o, n_src, frame_size_sec, h, &why);
+  if (rc) return fail(rc, "cTonespec (%lld bins, frame size %g s): %s", (long long)n_src, frame_size_sec, why);
+  std::unique_ptr<smilehip_tonespec_op> op(new smilehip_tonespec_op);
+  op->ctx = ctx;
+  op->n_src = h.n_src; op->n_notes = h.n_notes; op->use_power = o->use_power != 0;
+  if ((rc = op->d_fmap.upload(h.filter_map)) || (rc = op->d_rec.upload(h.rec))) return rc;
+  *out = op.release();
+  return SMILEHIP_OK;
+}
+extern "C" int smilehip_tonespec_op_frames(smilehip_tonespec_op *op, const float *d_src, int64_t ld_src, float *d_dst, int64_t ld_dst,
+                                           int64_t n_frames, void *stream) {
+  if (!op) return fail(SMILEHIP_ERR_INVALID, "smilehip_tonespec_op_frames: null operator");
+  int rc = check_frames(d_src, d_dst, ld_src, ld_dst, n_frames, op->n_src, op->n_notes, "smilehip_tonespec_op_frames");
+  if (rc) return rc;
+  STAGE_RET(stage_tonespec(op->d_fmap.p, op->d_rec.p, op->n_src, op->n_notes, op->use_power, d_src, ld_src, d_dst, ld_dst, n_frames,
+                           (hipStream_t)stream), "tonespec");
+}
+
+struct smilehip_chroma_op {
+  smilehip_context *ctx = nullptr;
+  int32_t n_src = 0, octave_size = 0;
+  float sil_thresh = 0.0f;
+};
+extern "C" int smilehip_chroma_op_destroy(smilehip_chroma_op *op) {
+  delete op;
+  return SMILEHIP_OK;
+}
+extern "C" int smilehip_chroma_op_create(smilehip_context *ctx, const smilehip_chroma_opts *o, int64_t n_src, smilehip_chroma_op **out) {
+  if (!ctx || !o || !out) return fail(SMILEHIP_ERR_INVALID, "smilehip_chroma_op_create: null argument");
+  if (o->octave_size < 1 || o->octave_size > chroma::kMaxOctaveSize)
+    return fail(SMILEHIP_ERR_INVALID, "cChroma: octaveSize must be 1 .. %d; got %d", chroma::kMaxOctaveSize, o->octave_size);
+  if (n_src < o->octave_size || n_src > (1 << 20) || n_src % o->octave_size)
+    return fail(SMILEHIP_ERR_INVALID, "cChroma: an input of %lld values is no multiple of octaveSize %d", (long long)n_src, o->octave_size);
+  if (!(o->sil_thresh == o->sil_thresh)) return fail(SMILEHIP_ERR_INVALID, "cChroma: silThresh is not a number");
+  std::unique_ptr<smilehip_chroma_op> op(new smilehip_chroma_op);
+  op->ctx = ctx;
+  op->n_src = (int32_t)n_src; op->octave_size = o->octave_size; op->sil_thresh = o->sil_thresh;
+  *out = op.release();
+  return SMILEHIP_OK;
+}
+extern "C" int smilehip_chroma_op_frames(smilehip_chroma_op *op, const float *d_src, int64_t ld_src, float *d_dst, int64_t ld_dst,
+                                         int64_t n_frames, void *stream) {
+  if (!op) return fail(SMILEHIP_ERR_INVALID, "smilehip_chroma_op_frames: null operator");
+  int rc = check_frames(d_src, d_dst, ld_src, ld_dst, n_frames, op->n_src, op->octave_size, "smilehip_chroma_op_frames");
+  if (rc) return rc;
+  STAGE_RET(stage_chroma(op->n_src, op->octave_size, op->sil_thresh, d_src, ld_src, d_dst, ld_dst, n_frames, (hipStream_t)stream), "chroma");
+}
+
 extern "C" int smilehip_preemphasis_frames(smilehip_context *ctx, const float *d_src, int64_t ld_src, float *d_dst,
                                            int64_t ld_dst, int64_t n_frames, int64_t N, float k, int de, void *stream) {
   if (!ctx || N < 1) return fail(SMILEHIP_ERR_INVALID, "smilehip_preemphasis_frames: bad argument");

@@ -390,6 +390,13 @@ void conf_apply_f0_params(const ConfPlan &p, smilehip_lld_config &c) {
     else if (kv.first == "shs_n_candidates") c.shs_n_candidates = (int32_t)kv.second;
     else if (kv.first == "specscale_min_f") c.specscale_min_f = kv.second;
     else if (kv.first == "sma_win") c.sma_win = (int32_t)kv.second;
+    else if (kv.first == "tonespec_n_octaves") c.tonespec_n_octaves = (int32_t)kv.second;
+    else if (kv.first == "tonespec_first_note") c.tonespec_first_note = (float)kv.second;
+    else if (kv.first == "tonespec_filter_type") c.tonespec_filter_type = (int32_t)kv.second;
+    else if (kv.first == "tonespec_use_power") c.tonespec_use_power = (int32_t)kv.second;
+    else if (kv.first == "tonespec_dba") c.tonespec_dba = (int32_t)kv.second;
+    else if (kv.first == "chroma_octave_size") c.chroma_octave_size = (int32_t)kv.second;
+    else if (kv.first == "chroma_sil_thresh") c.chroma_sil_thresh = (float)kv.second;
   }
 }
 
@@ -412,7 +419,7 @@ const KnownSet kKnownSets[] = {
 };
 }  // namespace
 
-bool conf_check_io(const ConfFile &f, const std::set<std::string> &produced, std::string &err) {
+bool conf_check_io(const ConfFile &f, const std::set<std::string> &produced, std::string &err, bool values_only_csv) {
   auto num_is = [](const std::string &v, double want) {
     char *end = nullptr;
     const double d = strtod(v.c_str(), &end);
@@ -483,7 +490,8 @@ bool conf_check_io(const ConfFile &f, const std::set<std::string> &produced, std
       return Want{key, value_of(key, dflt, bad), implemented, set(key), exact};
     };
     if (i.type == "cCsvSink")
-      wants = {{"timestamp / frameTime", stamp, 1, stamp_set, false}, plain("printHeader", 1, 1), {"number / frameIndex", number, 0, number_set, false},
+      wants = {{"timestamp / frameTime", stamp, values_only_csv ? 0.0 : 1.0, stamp_set, false}, plain("printHeader", 1, values_only_csv ? 0 : 1),
+               {"number / frameIndex", number, 0, number_set, false},
                plain("frameLength", 0, 0), plain("lag", 0, 0, true), plain("append", 0, on_func ? 1.0 : 0.0)};
     if (i.type == "cArffSink")
       wants = {{"number / frameIndex", number, 0, number_set, false}, {"timestamp / frameTime", stamp, on_func ? 0.0 : 1.0, stamp_set, false},
@@ -798,6 +806,134 @@ bool conf_to_prosody_acf(const ConfFile &f, ConfPlan &p, std::string &err) {
     what += buf;
   }
   p.describe = "the graph of prosodyAcf.conf with the file's own parameter values (" + what + ")";
+  return true;
+}
+
+// ---- smilextract_hip --set chroma_fft -C file: config/chroma/chroma_fft.conf, possibly with other values of the options the chain takes
+// as parameters (cTonespec nOctaves, firstNote, filterType, usePower, dbA; cChroma octaveSize, silThresh). Walked like prosodyAcf.conf
+// above: every other option has the one value SMILEHIP_CHAIN_CHROMA_FFT implements or is refused by name. The file's one sink is a
+// cCsvSink of values only (no header, time stamp or number column): what -O writes for this set. (Plain -C does not map the file.)
+bool conf_to_chroma_fft(const ConfFile &f, ConfPlan &p, std::string &err) {
+  p = ConfPlan();
+  static const std::vector<std::string> types = {"cFramer", "cWindower", "cTransformFFT", "cFFTmagphase", "cTonespec", "cChroma"};
+  std::map<std::string, const ConfInstance *> one;
+  for (const ConfInstance &i : f.inst) {
+    if (is_io_type(i.type)) continue;
+    if (std::find(types.begin(), types.end(), i.type) == types.end()) {
+      err = "component [" + i.name + ":" + i.type + "] is not part of the graph of chroma_fft.conf";
+      return false;
+    }
+    if (one.count(i.type)) { err = "more than one " + i.type + " ([" + i.name + "]): not the graph of chroma_fft.conf"; return false; }
+    one[i.type] = &i;
+  }
+  for (const std::string &t : types)
+    if (!one.count(t)) { err = "the graph has no " + t + ": not the graph of chroma_fft.conf"; return false; }
+  auto lvl = [](const ConfInstance *i, const char *k) { const std::string *v = i->find(k); return v ? *v : std::string(); };
+  auto wired = [&](const ConfInstance *i, const std::string &want) {
+    if (lvl(i, "reader.dmLevel") == want) return true;
+    err = "[" + i->name + ":" + i->type + "] reader.dmLevel = '" + lvl(i, "reader.dmLevel") + "', expected '" + want + "' (not the wiring of chroma_fft.conf)";
+    return false;
+  };
+  auto must_be = [](OptReader &o, const char *key, const char *want, const char *dflt) {
+    const std::string v = o.str(key, dflt);
+    if (lower(v) != lower(want) && o.err.empty())
+      o.err = "[" + o.ci.name + ":" + o.ci.type + "] " + key + " = " + v + " is not expressible on the fused path (needs " + want + ")";
+  };
+  const ConfInstance *fr = one["cFramer"], *win = one["cWindower"], *fft = one["cTransformFFT"], *mag = one["cFFTmagphase"],
+                     *ts = one["cTonespec"], *ch = one["cChroma"];
+  for (const ConfInstance &i : f.inst)
+    if (i.type == "cWaveSource" && !wired(fr, lvl(&i, "writer.dmLevel"))) return false;
+  {                                                       // src/core/winToVecProcessor.cpp:51-83
+    OptReader o(*fr);
+    o.require("frameSize", 0.064, 0.025); o.require("frameStep", 0.01, 0.0);
+    must_be(o, "frameMode", "fixed", "fixed"); must_be(o, "frameCenterSpecial", "left", "left");
+    o.require("noPostEOIprocessing", 1, 1); o.require("frameSizeFrames", 0, 0); o.require("frameStepFrames", 0, 0);
+    o.require("frameCenter", 0, 0); o.require("frameCenterFrames", 0, 0); o.require("allowLastFrameIncomplete", 0, 0);
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  {                                                       // src/dspcore/windower.cpp:36-49
+    OptReader o(*win);
+    if (!wired(win, lvl(fr, "writer.dmLevel"))) return false;
+    const std::string wf = o.str("winFunc", "Han");
+    if (win_func_of(wf) != SMILEHIP_WIN_GAUSS) o.err = "[" + win->name + ":cWindower] winFunc = " + wf + " is not expressible on the fused path (needs gauss)";
+    o.require("gain", 1, 1); o.require("sigma", 0.4, 0.4); o.require("offset", 0, 0);
+    o.require("fade", 0, 0); o.require("squareRoot", 0, 0); o.require("xshift", 0, 0); o.require("processArrayFields", 1, 1);
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  {                                                       // src/dspcore/transformFft.cpp:34-35
+    OptReader o(*fft);
+    if (!wired(fft, lvl(win, "writer.dmLevel"))) return false;
+    o.require("inverse", 0, 0); o.require("zeroPadSymmetric", 1, 1); o.require("processArrayFields", 1, 1);
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  {                                                       // src/dspcore/fftmagphase.cpp:39-49
+    OptReader o(*mag);
+    if (!wired(mag, lvl(fft, "writer.dmLevel"))) return false;
+    o.require("inverse", 0, 0); o.require("magnitude", 1, 1); o.require("phase", 0, 0); o.require("joinMagphase", 0, 0);
+    o.require("normalise", 0, 0); o.require("power", 0, 0); o.require("dBpsd", 0, 0); o.require("processArrayFields", 1, 1);
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  int n_notes = 0;
+  {                                                       // src/lld/tonespec.cpp:47-52, :89-117
+    OptReader o(*ts);
+    if (!wired(ts, lvl(mag, "writer.dmLevel"))) return false;
+    const double no = o.num("nOctaves", 6), fn = o.num("firstNote", 55.0);
+    if ((no < 1 || no > 10 || no != std::floor(no)) && o.err.empty())
+      o.err = "[" + ts->name + ":cTonespec] nOctaves = " + canonical_value(std::to_string(no)) + " is not expressible on the fused path (needs 1 .. 10)";
+    if (!(fn > 0.0) && o.err.empty())
+      o.err = "[" + ts->name + ":cTonespec] firstNote = " + canonical_value(std::to_string(fn)) + " is not expressible on the fused path (needs a positive frequency)";
+    n_notes = 12 * (int)no;
+    const std::string ft = o.str("filterType", "gau");    // the spellings of :107-111; anything else leaves the component at gau
+    static const std::pair<const char *, int> spell[] = {
+        {"gau", 0}, {"Gau", 0}, {"gauss", 0}, {"Gauss", 0}, {"gaussian", 0}, {"Gaussian", 0}, {"tri", 1}, {"Tri", 1}, {"triangular", 1},
+        {"Triangular", 1}, {"trp", 2}, {"TrP", 2}, {"Trp", 2}, {"triangular-powered", 2}, {"Triangular-Powered", 2}, {"rec", 3}, {"Rec", 3},
+        {"rectangular", 3}, {"Rectangular", 3}};
+    int type = -1;
+    for (const auto &sp : spell)
+      if (ft == sp.first) type = sp.second;
+    if (type < 0 && o.err.empty())
+      o.err = "[" + ts->name + ":cTonespec] filterType = " + ft + " is not expressible on the fused path (needs gau, tri, trp or rec)";
+    p.f0_params["tonespec_n_octaves"] = no;
+    p.f0_params["tonespec_first_note"] = (double)(float)fn;
+    p.f0_params["tonespec_filter_type"] = type;
+    p.f0_params["tonespec_use_power"] = o.num("usePower", 0) != 0.0;
+    p.f0_params["tonespec_dba"] = o.num("dbA", 1) != 0.0;
+    o.require("processArrayFields", 0, 1);
+    o.str("nameAppend", "note");                          // (cChroma names its outputs itself: copyInputName = 0)
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  {                                                       // src/lld/chroma.cpp:46-49, :67-75
+    OptReader o(*ch);
+    if (!wired(ch, lvl(ts, "writer.dmLevel"))) return false;
+    const double os = o.num("octaveSize", 12), st = o.num("silThresh", 0.001);
+    if ((os < 1 || os > 64 || os != std::floor(os) || (n_notes % (int)os)) && o.err.empty())
+      o.err = "[" + ch->name + ":cChroma] octaveSize = " + canonical_value(std::to_string(os)) + " is not expressible on the fused path (needs 1 .. 64 and a divisor of the " +
+              std::to_string(n_notes) + " notes)";
+    p.f0_params["chroma_octave_size"] = os;
+    p.f0_params["chroma_sil_thresh"] = (double)(float)st;
+    o.require("processArrayFields", 0, 1);
+    must_be(o, "nameAppend", "chroma", "chroma");
+    o.require("copyInputName", 0, 0);
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  if (!conf_check_io(f, {lvl(ch, "writer.dmLevel")}, err, true)) return false;
+  p.preset = "chroma_fft";
+  for (const ConfInstance &i : f.inst)
+    if (i.type == "cWaveSource") { const std::string *fn = i.find("filename"); if (fn) p.wave_file = *fn; }
+  const std::map<std::string, double> shipped = {{"tonespec_n_octaves", 6}, {"tonespec_first_note", 55}, {"tonespec_filter_type", 0}, {"tonespec_use_power", 1},
+                                                 {"tonespec_dba", 1}, {"chroma_octave_size", 12}, {"chroma_sil_thresh", (double)(float)0.001}};
+  if (p.f0_params == shipped) {                           // the shipped file's values: the preset as it is
+    p.f0_params.clear();
+    p.describe = "the graph of chroma_fft.conf (every processing component and option identical)";
+    return true;
+  }
+  std::string what;
+  for (const auto &kv : p.f0_params) {
+    char buf[64];
+    snprintf(buf, sizeof(buf), "%s%s = %.9g", what.empty() ? "" : ", ", kv.first.c_str(), kv.second);
+    what += buf;
+  }
+  p.describe = "the graph of chroma_fft.conf with the file's own parameter values (" + what + ")";
   return true;
 }
 

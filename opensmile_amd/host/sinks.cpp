@@ -253,12 +253,12 @@ bool write_csv(const std::string &path, const std::vector<std::string> &names, c
   if (!f) { err = "cannot open '" + path + "' for writing"; return false; }
   const char d = ';';
   if (!ap && opt.print_header) {
-    fprintf(f, "name%c", d);
+    if (opt.name_column) fprintf(f, "name%c", d);
     if (opt.timestamp) fprintf(f, "frameTime%c", d);
     for (int c = 0; c < cols - 1; ++c) fprintf(f, "%s%c", names[(size_t)c].c_str(), d);
     fprintf(f, "%s\n", names[(size_t)cols - 1].c_str());
   }
-  const std::string name = "'" + opt.instance_name + "'" + d;
+  const std::string name = opt.name_column ? "'" + opt.instance_name + "'" + d : std::string();
   const size_t max_row = name.size() + 64 + (size_t)cols * 50;
   const bool wrote = write_text_rows(f, rows, max_row, [&](int64_t t, char *p) {
     size_t n = name.size();

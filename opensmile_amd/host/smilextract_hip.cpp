@@ -25,6 +25,10 @@
 //                   take as a parameter is refused by name (plain -C does not map this file)
 //   smilextract_hip --set prosody_acf   config/prosody/prosodyAcf.conf: voicing probability, ACF / cepstrum F0 and loudness contours
 //                   [-C prosodyAcf.conf]  with that file's (edited) maxPitch, voicingCutoff and smaWin; anything else is refused by name
+//   smilextract_hip --set chroma_fft    config/chroma/chroma_fft.conf: 12 chroma values per frame; -O out.csv is the file's own sink (values
+//                   [-C chroma_fft.conf]  only: no header, name, time stamp or number column), -csvoutput the other sets' CSV with header and
+//                                       time stamps. With -C: that file's (edited) nOctaves, firstNote, filterType, usePower, dbA,
+//                                       octaveSize and silThresh; anything else is refused by name
 //   smilextract_hip --set gemapsv01a | egemapsv01a   the v01a files: the same columns, zeroPadSymmetric = 0, useBrokenJitterThresh = 1, maxF = 5500
 //   smilextract_hip --set gemapsv01b | egemapsv01b   config/gemaps/v01b/GeMAPSv01b.conf (18 LLDs, 62 functionals) / config/egemaps/v01b/
 //                                       eGeMAPSv01b.conf (23, 88): sub-graphs of eGeMAPSv02.conf, written as column subsets of its levels
@@ -160,9 +164,10 @@ static int run_main(int argc, char **argv, Persist *ps) {
   if (with_conf) {
     // --set prosody_shs | prosody_acf -C file: the set with the file's own parameter values (conf_to_prosody_shs / _acf); otherwise one or the other
     const bool set_acf = opt.count("--set") && opt["--set"] == "prosody_acf";
-    const bool set_with_conf = opt.count("--set") && (opt["--set"] == "prosody_shs" || set_acf);
+    const bool set_chroma = opt.count("--set") && opt["--set"] == "chroma_fft";
+    const bool set_with_conf = opt.count("--set") && (opt["--set"] == "prosody_shs" || set_acf || set_chroma);
     if (opt.count("--set") && !set_with_conf)
-      die("-C and --set exclude each other (except --set prosody_shs -C prosodyShs.conf and --set prosody_acf -C prosodyAcf.conf)");
+      die("-C and --set exclude each other (except --set prosody_shs -C prosodyShs.conf, --set prosody_acf -C prosodyAcf.conf and --set chroma_fft -C chroma_fft.conf)");
     ConfFile cf;
     std::string cerr_;
     if (!conf_parse(opt["-C"], conf_cmdline, cf, cerr_)) die("-C " + opt["-C"] + ": " + cerr_);
@@ -204,14 +209,17 @@ static int run_main(int argc, char **argv, Persist *ps) {
           opt[o.second] = dflt->second;
       }
     }
-    if (!(set_acf ? conf_to_prosody_acf(cf, conf_plan, cerr_)
-                  : (set_with_conf ? conf_to_prosody_shs(cf, conf_plan, cerr_) : conf_to_plan(cf, conf_plan, cerr_)))) {
+    if (!(set_chroma ? conf_to_chroma_fft(cf, conf_plan, cerr_)
+          : set_acf  ? conf_to_prosody_acf(cf, conf_plan, cerr_)
+                     : (set_with_conf ? conf_to_prosody_shs(cf, conf_plan, cerr_) : conf_to_plan(cf, conf_plan, cerr_)))) {
       ConfPlan as_set;
       std::string e2;
       const bool hint = !set_with_conf && conf_to_prosody_shs(cf, as_set, e2);
       const bool hint_acf = !set_with_conf && !hint && conf_to_prosody_acf(cf, as_set, e2);
+      const bool hint_chroma = !set_with_conf && !hint && !hint_acf && conf_to_chroma_fft(cf, as_set, e2);
       die("-C " + opt["-C"] + " cannot run on the fused path: " + cerr_ +
-          (hint ? " -- this file runs as --set prosody_shs -C <file>" : (hint_acf ? " -- this file runs as --set prosody_acf -C <file>" : "")));
+          (hint ? " -- this file runs as --set prosody_shs -C <file>"
+                : (hint_acf ? " -- this file runs as --set prosody_acf -C <file>" : (hint_chroma ? " -- this file runs as --set chroma_fft -C <file>" : ""))));
     }
     fprintf(stderr, "smilextract_hip: %s -> %s\n", opt["-C"].c_str(), conf_plan.describe.c_str());
     if (!conf_plan.preset.empty()) opt["--set"] = conf_plan.preset;
@@ -288,13 +296,18 @@ static int run_main(int argc, char **argv, Persist *ps) {
   if (free_chain) vcfg = conf_plan.cfg;
   // config/prosody/prosodyShs.conf: an LLD-only set like the cepstral files (-O = HTK, -csvoutput = CSV of the lld level)
   const bool prosody_acf = set == "prosody_acf";         // config/prosody/prosodyAcf.conf: the same kind of set
-  const bool prosody = set == "prosody_shs" || prosody_acf;
-  if (prosody_acf) smilehip_config_prosody_acf(&vcfg);
+  // config/chroma/chroma_fft.conf: an LLD-only set as well; its -O is the file's cCsvSink (values only), not an HTK file
+  const bool chroma = set == "chroma_fft";
+  const bool prosody = set == "prosody_shs" || prosody_acf || chroma;
+  if (chroma) {
+    smilehip_config_chroma_fft(&vcfg, 16000.0);         // (the rate is each file's own: make_plan)
+    if (with_conf) conf_apply_f0_params(conf_plan, vcfg);   // (the names follow the file's octaveSize)
+  } else if (prosody_acf) smilehip_config_prosody_acf(&vcfg);
   else if (prosody) smilehip_config_prosody_shs(&vcfg);
   const bool htk_variant = free_chain || prosody || (!is09 && !cmp16 && !egm && smilehip_config_htk_variant(&vcfg, variant.c_str()) == SMILEHIP_OK);
   const bool plp = htk_variant && vcfg.chain_kind == SMILEHIP_CHAIN_PLP;
   if (!is09 && !cmp16 && !egm && !htk_variant)
-    die("--set must be mfcc12_{0,e}_d_a[_z], plp_{0,e}_d_a[_z], is09_emotion, compare16, compare16_lld, is13_compare, egemapsv02, gemapsv01b, egemapsv01b, gemapsv01a, egemapsv01a, prosody_shs or prosody_acf (or use -C file.conf)");
+    die("--set must be mfcc12_{0,e}_d_a[_z], plp_{0,e}_d_a[_z], is09_emotion, compare16, compare16_lld, is13_compare, egemapsv02, gemapsv01b, egemapsv01b, gemapsv01a, egemapsv01a, prosody_shs, prosody_acf or chroma_fft (or use -C file.conf)");
   // parmKind of the files' own cHtkSink sections (the _Z files); the others write through standard_data_output_lldonly (9)
   int parm_kind = 9;
   if (variant == "MFCC12_0_D_A_Z") parm_kind = 11014;
@@ -467,6 +480,7 @@ static int run_main(int argc, char **argv, Persist *ps) {
   };
   const std::vector<std::string> lld_names =
       free_chain ? conf_plan.lld_names
+                 : chroma ? lld_names_chroma_fft(vcfg.chroma_octave_size)
                  : prosody_acf ? lld_names_prosody_acf()
                  : prosody ? lld_names_prosody_shs()
                  : (is09 ? lld_names_is09() : (cmp16 ? (cmp_subset ? select_names(lld_names_compare16(), sel_lld) : lld_names_compare16())
@@ -809,7 +823,7 @@ static int run_main(int argc, char **argv, Persist *ps) {
       if (!lld) { w->lld_vec.resize(lld_bytes / 4); lld = w->lld_vec.data(); }
       w->lld = lld;
       dlap(t_dev_reserve);
-      w->be = !no_pinned && want_lld_htk && !want_lld_csv && !out_subset && rows > 0;
+      w->be = !no_pinned && want_lld_htk && !want_lld_csv && !out_subset && rows > 0 && !chroma;   // (chroma_fft: -O is a CSV file)
       if (w->be) check(smilehip_htk_rows_be(ctx, (const float *)d_lld, rows * n_out, d_lld, st), "smilehip_htk_rows_be");
       if (defer) { check(smilehip_event_record(ctx, chunk_computed[slot], st), "event_record"); computed_recorded[slot] = true; }
       if (rows > 0) check(smilehip_copy_to_host(ctx, lld, d_lld, (uint64_t)rows * n_out * 4, st), "copy_to_host");
@@ -859,7 +873,11 @@ static int run_main(int argc, char **argv, Persist *ps) {
           int n_w = n_out;                                  // columns written (a subset preset writes its selection)
           std::vector<float> x_sel;
           if (out_subset) { x_sel = select_columns(x, r, n_out, sel_lld); x = x_sel.data(); n_w = (int)sel_lld.size(); }
-          if (want_lld_htk) {
+          if (want_lld_htk && chroma) {                     // chroma_fft.conf's own sink: values only (printHeader = 0, timestamp = 0, number = 0)
+            CsvOptions co;
+            co.print_header = co.timestamp = co.name_column = false;
+            if (!write_csv(per_file(job, "-O", ".csv"), lld_names, x, r, n_w, n_w, g.frame_period, nullptr, co, err)) { die(err); return; }
+          } else if (want_lld_htk) {
             const std::string path = per_file(job, lld_htk_opt, lld_opts ? ".lld.htk" : ".htk");
             const bool ok = w->be ? write_htk_be(path, x, r, n_w, g.frame_period, lld_opts ? 9 : parm_kind, err)
                                   : write_htk(path, x, r, n_w, n_w, g.frame_period, lld_opts ? 9 : parm_kind, err);
@@ -872,7 +890,7 @@ static int run_main(int argc, char **argv, Persist *ps) {
             const int64_t n_frames = (cmp16 || egm) ? r - 1 : smilehip_num_frames(plan, w->true_off[i + 1] - w->true_off[i]);
             std::vector<double> times((size_t)r);
             for (int64_t t = 0; t < r; ++t) times[(size_t)t] = smilehip_row_time(plan, n_frames, t);
-            if (!write_csv(per_file(job, lld_csv_opt, lld_opts ? ".lld.csv" : ".csv"), lld_names, x, r, n_w, n_w, g.frame_period,
+            if (!write_csv(per_file(job, lld_csv_opt, (lld_opts || chroma) ? ".lld.csv" : ".csv"), lld_names, x, r, n_w, n_w, g.frame_period,
                            times.data(), co, err)) {
               die(err);
               return;
