@@ -62,7 +62,7 @@ typedef enum smilehip_winfunc {
 /* Parameters of the MFCC chain. Each group carries exactly the options the
  * corresponding reference component reads in myFetchConfig(). */
 typedef struct smilehip_lld_config {
-  uint32_t struct_size;        /* = sizeof(smilehip_lld_config), or SMILEHIP_LLD_CONFIG_SIZE_V1 (see behind the struct) */
+  uint32_t struct_size;        /* = sizeof(smilehip_lld_config), or SMILEHIP_LLD_CONFIG_SIZE_V1 / _V2 (see behind the struct) */
   /* cWaveSource (src/iocore/waveSource.cpp:190) + cFramer
    * (src/core/winToVecProcessor.cpp:435-456): frameMode=fixed,
    * frameCenterSpecial=left, noPostEOIprocessing=1 */
@@ -185,13 +185,26 @@ typedef struct smilehip_lld_config {
   int32_t  chroma_octave_size;          /* octaveSize: the chain's outputs; 12 nOctaves must be a multiple of it (1 .. 64) */
   float    chroma_sil_thresh;           /* silThresh */
   int32_t  reserved_chroma;             /* 0 */
+  /* ---- everything below lies behind SMILEHIP_LLD_CONFIG_SIZE_V2 and is read only where struct_size covers it ----
+   * SMILEHIP_CHAIN_CHROMA_FILT: [tonefilt:cTonefilt] (src/lld/tonefilt.cpp:65-98), doubles as the component keeps them; cChroma's
+   * chroma_octave_size and chroma_sil_thresh above are this chain's as well. */
+  int32_t  tonefilt_n_notes;            /* nNotes (1 .. 120; the component raises anything below 1 to 1) */
+  int32_t  reserved_tonefilt;           /* 0 */
+  double   tonefilt_first_note;         /* firstNote in Hz (<= 0 reads as 1) */
+  double   tonefilt_decay_f0;           /* decayF0, clamped as the component clamps it (:78-82) */
+  double   tonefilt_decay_fn;           /* decayFN (:73-76) */
+  double   tonefilt_output_period;      /* outputPeriod in seconds (<= 0 reads as 0.1) */
 } smilehip_lld_config;
 /* struct_size rules. The struct only ever grows at its end. SMILEHIP_LLD_CONFIG_SIZE_V1 is its size up to and including
  * acf_cep_use_power, i.e. sizeof(smilehip_lld_config) of every header before the chroma fields. The presets that existed then
  * (everything but smilehip_config_chroma_fft) still zero and fill exactly that many bytes and set struct_size to it, so a caller
  * compiled against such a header, whose struct ends there, is never written past its end. smilehip_plan_create accepts either
- * size; fields a struct_size does not cover read as zero, and SMILEHIP_CHAIN_CHROMA_FFT requires the full size. */
+ * size; fields a struct_size does not cover read as zero, and SMILEHIP_CHAIN_CHROMA_FFT requires at least V2.
+ * The same rule one step on: SMILEHIP_LLD_CONFIG_SIZE_V2 is the struct's size up to and including reserved_chroma, i.e.
+ * sizeof(smilehip_lld_config) of the header that brought the chroma fields. smilehip_config_chroma_fft keeps filling and reporting
+ * exactly V2; smilehip_plan_create accepts V1, V2 and the full size; SMILEHIP_CHAIN_CHROMA_FILT requires the full size. */
 #define SMILEHIP_LLD_CONFIG_SIZE_V1 280u
+#define SMILEHIP_LLD_CONFIG_SIZE_V2 312u
 #define SMILEHIP_TONESPEC_GAUSS 0
 #define SMILEHIP_TONESPEC_TRI 1
 #define SMILEHIP_TONESPEC_TRI_POWERED 2
@@ -253,6 +266,19 @@ typedef struct smilehip_lld_config {
  * per frame for transforms of 512 / 1024 points, a workgroup per frame otherwise). smilehip_batch_chroma_taps returns the tonespec
  * level. */
 #define SMILEHIP_CHAIN_CHROMA_FFT 9
+/* SMILEHIP_CHAIN_CHROMA_FILT: the level `chroma` of config/chroma/chroma_filt.conf, what its one cCsvSink writes: chroma_octave_size
+ * (12) columns chroma[0] .. chroma[11], one row per block of P samples. There is no framer and no transform: cTonefilt
+ * (src/lld/tonefilt.cpp:101-226) runs tonefilt_n_notes (72) decaying sine / cosine correlators over the samples themselves, two
+ * double states per note carried over the whole input, and writes 10 |state| per note at the end of every block
+ * (P = (long)round(outputPeriod / T): 80, 110, 160, 221, 320, 441, 480 samples at 8 .. 48 kHz); cChroma (src/lld/chroma.cpp:86-118)
+ * folds the octaves. Rows per utterance, as measured against the binary: ceil(n / P) for n samples -- at the end of input the reader
+ * hands out the samples left over as one more block, padded to P with the last sample repeated, and cTonefilt filters all P of them
+ * (tonefilt::rows_of, lld_tonefilt_ops.hpp); row r carries the time r * outputPeriod. One scan kernel
+ * (lld_tonefilt_scan: a lane per (utterance, note) chain walks its samples in order), then lld_chroma_rows over the tonespec level,
+ * which smilehip_batch_chroma_taps returns. The device's double sine and cosine (sincos_d, at most 1 ulp) are not the C library's:
+ * the float levels equal the binary's, the double states need not (README "Parity"). Inputs long enough to carry
+ * 2 pi freq[nNotes - 1] t past sincos_d's domain, 2^30, are refused at batch creation with SMILEHIP_ERR_INVALID. */
+#define SMILEHIP_CHAIN_CHROMA_FILT 10
 
 #define SMILEHIP_STAGE_WINDOW 1u
 #define SMILEHIP_STAGE_FFT    2u
@@ -331,13 +357,19 @@ void smilehip_config_prosody_shs(smilehip_lld_config *c);
  *   its default 0 = acf_cep_use_power 0 (:68-71, acf.cpp:91-102); [pitch:cPitchACF] maxPitch 500, voicingCutoff 0.55, voiceProb +
  *   F0 (:73-86); [smo:cContourSmoother] smaWin 3, noPostEOIprocessing 0 (:88-94) */
 void smilehip_config_prosody_acf(smilehip_lld_config *c);
-/* fills c -- the FULL struct, struct_size = sizeof(smilehip_lld_config) -- with config/chroma/chroma_fft.conf at this sample rate
+/* fills c -- SMILEHIP_LLD_CONFIG_SIZE_V2 bytes, struct_size = that -- with config/chroma/chroma_fft.conf at this sample rate
  * (chain_kind = CHROMA_FFT, 12 columns):
  *   [framer:cFramer] 0.064 / 0.010 s, frameCenterSpecial = left, noPostEOIprocessing = 1 (:43-53); [windower:cWindower] Gau, sigma 0.4,
  *   gain 1, offset 0 (:55-64); [transformFFT:cTransformFFT] (:66-72); [fFTmagphase:cFFTmagphase] magnitudes (:74-82);
  *   [tonespec:cTonespec] nOctaves 6, firstNote 55, filterType gau, usePower 1, dbA 1 (:84-94); [chroma:cChroma] octaveSize 12 and
  *   silThresh at its default 0.001 (:96-102, chroma.cpp:49) */
 void smilehip_config_chroma_fft(smilehip_lld_config *c, double sample_rate);
+/* fills c -- the FULL struct, struct_size = sizeof(smilehip_lld_config) -- with config/chroma/chroma_filt.conf at this sample rate
+ * (chain_kind = CHROMA_FILT, 12 columns):
+ *   [tonefilt:cTonefilt] nNotes 72, firstNote 55, decayF0 0.9999, decayFN 0.999, outputPeriod 0.01 (:43-52); [chroma:cChroma]
+ *   octaveSize 12 and silThresh at its default 0.001 (:54-59, chroma.cpp:49).
+ * frame_size_sec = frame_step_sec = outputPeriod: the plan's frame_size / frame_step are the block length P. */
+void smilehip_config_chroma_filt(smilehip_lld_config *c, double sample_rate);
 
 /* F0 group, per component, on an F0 chain plan (smilehip_config_compare16_f0; the plan's spectrum geometry -- n_bins and
  * the level's frameSizeSec, force_fft_frame_size_sec -- must be the input level's):
@@ -361,8 +393,9 @@ int smilehip_batch_f0_taps(smilehip_batch *b, float *d_hps_dst, const float **d_
  * smilehip_lld_run of this batch filled, [total_frames x 3] = voiceProb | F0 (the contour) | pcm_loudness: the levels `pitch` and
  * `intens` in front of the smoother. n_frames (optional) receives total_frames. */
 int smilehip_batch_prosody_acf_taps(smilehip_batch *batch, float **d_raw3, int64_t *n_frames);
-/* chroma_fft chain tap (tests / diagnostics; SMILEHIP_CHAIN_CHROMA_FFT batches): device pointer to the level `tonespec` the last
- * smilehip_lld_run of this batch filled, [total_frames x 12 tonespec_n_octaves], packed. n_frames (optional) receives total_frames. */
+/* chroma_fft / chroma_filt chain tap (tests / diagnostics; SMILEHIP_CHAIN_CHROMA_FFT and _FILT batches): device pointer to the level
+ * `tonespec` the last smilehip_lld_run of this batch filled, [total_frames x 12 tonespec_n_octaves] resp.
+ * [total_frames x tonefilt_n_notes], packed. n_frames (optional) receives total_frames. */
 int smilehip_batch_chroma_taps(smilehip_batch *batch, float **d_tonespec, int64_t *n_frames);
 /* Frames per utterance that cPitchSmootherViterbi had not decided when the input ended (they are flushed at the end of input:
  * src/lld/pitchSmootherViterbi.cpp:451-570), [n_utt] device ints filled by the last smilehip_lld_run of an F0 / ComParE / eGeMAPS
@@ -1301,6 +1334,42 @@ int smilehip_chroma_op_create(smilehip_context *ctx, const smilehip_chroma_opts 
 int smilehip_chroma_op_frames(smilehip_chroma_op *op, const float *d_src, int64_t ld_src, float *d_dst, int64_t ld_dst,
                               int64_t n_frames, void *stream);
 int smilehip_chroma_op_destroy(smilehip_chroma_op *op);
+
+/* ---- cTonefilt per component (src/lld/tonefilt.cpp): the scan of the fused chroma_filt chain (lld_tonefilt_ops.hpp) as a stream.
+ * This operator is outside the strided-row contract of the operators above, and has no ld_* parameter, for two reasons: its input
+ * is not rows but ONE stream of samples, cut into blocks only to say where rows are written; and it is not a function of its input
+ * alone -- the position and two doubles per note are carried from call to call, so a call cannot be repeated or reordered. Its
+ * output rows are packed, n_notes floats apart. */
+typedef struct smilehip_tonefilt_opts {
+  int32_t n_notes;          /* nNotes, 1 .. 120 */
+  int32_t reserved;         /* 0 */
+  double  first_note;       /* firstNote in Hz */
+  double  decay_f0;         /* decayF0 */
+  double  decay_fn;         /* decayFN */
+  double  output_period;    /* outputPeriod in seconds */
+} smilehip_tonefilt_opts;
+typedef struct smilehip_tonefilt_op smilehip_tonefilt_op;
+/* cTonefilt::configureWriter and setupNewNames for a wave level of sample_rate Hz. max_samples is the longest stream the state will
+ * see between resets: where 2 pi freq[nNotes - 1] max_samples / sample_rate exceeds sincos_d's domain (2^30) the call returns
+ * SMILEHIP_ERR_INVALID naming it. */
+int smilehip_tonefilt_op_create(smilehip_context *ctx, const smilehip_tonefilt_opts *opts, double sample_rate, int64_t max_samples,
+                                smilehip_tonefilt_op **out);
+int smilehip_tonefilt_op_n_out(const smilehip_tonefilt_op *op);           /* nNotes */
+int64_t smilehip_tonefilt_op_block_len(const smilehip_tonefilt_op *op);  /* P */
+/* cTonefilt::doFilter on the next n_blocks blocks: d_samples holds n_blocks * P float samples, d_dst receives n_blocks rows of nNotes
+ * floats, packed. State and position carry over from the previous call. One lane per note. The stream's last block is the
+ * caller's to complete as the reader does: with its last sample repeated. */
+int smilehip_tonefilt_op_blocks(smilehip_tonefilt_op *op, const float *d_samples, int64_t n_blocks, float *d_dst, void *stream);
+/* copies the state out (synchronises the device): pos, s [nNotes], c [nNotes]; every output is optional */
+int smilehip_tonefilt_op_state(smilehip_tonefilt_op *op, int64_t *pos, double *s, double *c);
+int smilehip_tonefilt_op_reset(smilehip_tonefilt_op *op);                 /* the state of a fresh operator */
+int smilehip_tonefilt_op_destroy(smilehip_tonefilt_op *op);
+/* The operator's host tables without a device: returns nNotes, or a negative value where smilehip_tonefilt_op_create refuses. Every
+ * output is optional: block_len [1] = P; freq, decay [nNotes] */
+/* sincos_d, the device's double sine and cosine behind cTonefilt (tests / diagnostics): d_sin[i], d_cos[i] of d_x[i], |x| <= 2^30
+ * (the function's domain: at most 1 ulp inside it, unspecified outside; sin(-0) is +0) */
+int smilehip_sincos_d_values(smilehip_context *ctx, const double *d_x, int64_t n, double *d_sin, double *d_cos, void *stream);
+int smilehip_tonefilt_op_tables(const smilehip_tonefilt_opts *opts, double sample_rate, int64_t *block_len, double *freq, double *decay);
 
 #ifdef __cplusplus
 }

@@ -144,7 +144,27 @@ class LldConfigChroma(LldConfig):
                 ("chroma_sil_thresh", C.c_float), ("reserved_chroma", C.c_int32)]
 
 
+class LldConfigChromaFilt(LldConfigChroma):
+    """the full smilehip_lld_config: LldConfigChroma (SMILEHIP_LLD_CONFIG_SIZE_V2 bytes, what smilehip_config_chroma_fft fills and
+    reports) and behind it the fields SMILEHIP_CHAIN_CHROMA_FILT reads. Every entry point that takes a LldConfig takes this."""
+    _fields_ = [("tonefilt_n_notes", C.c_int32), ("reserved_tonefilt", C.c_int32), ("tonefilt_first_note", C.c_double),
+                ("tonefilt_decay_f0", C.c_double), ("tonefilt_decay_fn", C.c_double), ("tonefilt_output_period", C.c_double)]
+
+
 LLD_CONFIG_SIZE_V1 = 280
+LLD_CONFIG_SIZE_V2 = 312
+
+
+class TonefiltOpts(C.Structure):
+    """smilehip_tonefilt_opts"""
+    _fields_ = [("n_notes", C.c_int32), ("reserved", C.c_int32), ("first_note", C.c_double), ("decay_f0", C.c_double),
+                ("decay_fn", C.c_double), ("output_period", C.c_double)]
+
+
+def tonefilt_opts(n_notes=72, first_note=55.0, decay_f0=0.9999, decay_fn=0.999, output_period=0.01):
+    o = TonefiltOpts()
+    o.n_notes, o.first_note, o.decay_f0, o.decay_fn, o.output_period = int(n_notes), float(first_note), float(decay_f0), float(decay_fn), float(output_period)
+    return o
 TONESPEC_FILTER = {"gau": 0, "tri": 1, "trp": 2, "rec": 3}          # SMILEHIP_TONESPEC_*
 
 
@@ -221,6 +241,16 @@ SYMBOLS = {
     "smilehip_chroma_op_create": (C.c_int, [_vp, _vp, _i64, _vp]),
     "smilehip_chroma_op_frames": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp]),
     "smilehip_chroma_op_destroy": (C.c_int, [_vp]),
+    "smilehip_config_chroma_filt": (None, [C.POINTER(LldConfigChromaFilt), _dbl]),
+    "smilehip_tonefilt_op_create": (C.c_int, [_vp, _vp, _dbl, _i64, _vp]),
+    "smilehip_tonefilt_op_n_out": (C.c_int, [_vp]),
+    "smilehip_tonefilt_op_block_len": (_i64, [_vp]),
+    "smilehip_tonefilt_op_blocks": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    "smilehip_tonefilt_op_state": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "smilehip_tonefilt_op_reset": (C.c_int, [_vp]),
+    "smilehip_tonefilt_op_destroy": (C.c_int, [_vp]),
+    "smilehip_tonefilt_op_tables": (C.c_int, [_vp, _dbl, _vp, _vp, _vp]),
+    "smilehip_sincos_d_values": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "smilehip_config_htk_variant": (C.c_int, [C.POINTER(LldConfig), C.c_char_p]),
     "smilehip_config_compare16": (None, [C.POINTER(LldConfig)]),
     "smilehip_specscale_frames": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp]),
@@ -611,6 +641,104 @@ def chroma_fft_config(sample_rate=16000.0):
     return c
 
 
+CHAIN_CHROMA_FILT = 10
+
+
+def chroma_filt_config(sample_rate=16000.0):
+    """config/chroma/chroma_filt.conf (chain_kind = CHROMA_FILT): chroma[0] .. chroma[11]; the full struct (LldConfigChromaFilt)"""
+    c = LldConfigChromaFilt()
+    load().smilehip_config_chroma_filt(C.byref(c), float(sample_rate))
+    return c
+
+
+def tonefilt_tables(opts, sample_rate):
+    """smilehip_tonefilt_op_tables: dict of P (samples per block), freq, decay"""
+    L = load()
+    n = L.smilehip_tonefilt_op_tables(C.byref(opts), float(sample_rate), None, None, None)
+    if n < 0:
+        raise SmileHipError(L.smilehip_last_error().decode())
+    P, freq, decay = _i64(0), np.zeros(n), np.zeros(n)
+    assert L.smilehip_tonefilt_op_tables(C.byref(opts), float(sample_rate), C.addressof(P), freq.ctypes.data, decay.ctypes.data) == n
+    return dict(P=int(P.value), freq=freq, decay=decay)
+
+
+def sincos_d_host(ctx, x):
+    """smilehip_sincos_d_values on host doubles: (sin, cos) as the device computes them"""
+    L = load()
+    x = np.ascontiguousarray(x, np.float64)
+    s, c = np.zeros(len(x)), np.zeros(len(x))
+    d = [_vp(), _vp(), _vp()]
+    for p in d:
+        _check(L.smilehip_alloc(ctx._h, max(x.nbytes, 8), C.byref(p)))
+    try:
+        if len(x):
+            _check(L.smilehip_copy_to_device(ctx._h, d[0], x.ctypes.data, x.nbytes, None))
+            _check(L.smilehip_sincos_d_values(ctx._h, d[0], len(x), d[1], d[2], None))
+            _check(L.smilehip_stream_synchronize(ctx._h, None))
+            _check(L.smilehip_copy_to_host(ctx._h, s.ctypes.data, d[1], s.nbytes, None))
+            _check(L.smilehip_copy_to_host(ctx._h, c.ctypes.data, d[2], c.nbytes, None))
+    finally:
+        for p in d:
+            L.smilehip_free(ctx._h, p)
+    return s, c
+
+
+class TonefiltOp:
+    """smilehip_tonefilt_op: cTonefilt as a stream of blocks with carried state (not a strided-row operator: no leading dimensions)"""
+
+    def __init__(self, ctx, opts, sample_rate, max_samples):
+        self.ctx = ctx
+        self._h = _vp()
+        _check(load().smilehip_tonefilt_op_create(ctx._h, C.byref(opts), float(sample_rate), int(max_samples), C.byref(self._h)))
+        self.n_out = int(load().smilehip_tonefilt_op_n_out(self._h))
+        self.block_len = int(load().smilehip_tonefilt_op_block_len(self._h))
+
+    def blocks(self, d_samples, n_blocks, d_dst, stream=None):
+        _check(load().smilehip_tonefilt_op_blocks(self._h, d_samples, int(n_blocks), d_dst, stream))
+
+    def blocks_host(self, samples):
+        """float32 samples on the host, a whole number of blocks -> rows [n_blocks x n_out]"""
+        L = load()
+        ctx = self.ctx._h
+        x = np.ascontiguousarray(samples, np.float32)
+        assert len(x) % self.block_len == 0
+        nb = len(x) // self.block_len
+        out = np.zeros((nb, self.n_out), np.float32)
+        d_x, d_out = _vp(), _vp()
+        _check(L.smilehip_alloc(ctx, max(x.nbytes, 4), C.byref(d_x)))
+        _check(L.smilehip_alloc(ctx, max(out.nbytes, 4), C.byref(d_out)))
+        try:
+            if nb:
+                _check(L.smilehip_copy_to_device(ctx, d_x, x.ctypes.data, x.nbytes, None))
+                self.blocks(d_x, nb, d_out)
+                _check(L.smilehip_stream_synchronize(ctx, None))
+                _check(L.smilehip_copy_to_host(ctx, out.ctypes.data, d_out, out.nbytes, None))
+        finally:
+            L.smilehip_free(ctx, d_x)
+            L.smilehip_free(ctx, d_out)
+        return out
+
+    def state(self):
+        """(pos, s [n_out], c [n_out])"""
+        pos, s, c = _i64(0), np.zeros(self.n_out), np.zeros(self.n_out)
+        _check(load().smilehip_tonefilt_op_state(self._h, C.addressof(pos), s.ctypes.data, c.ctypes.data))
+        return int(pos.value), s, c
+
+    def reset(self):
+        _check(load().smilehip_tonefilt_op_reset(self._h))
+
+    def close(self):
+        if self._h:
+            load().smilehip_tonefilt_op_destroy(self._h)
+            self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def tonespec_tables(opts, n_src, frame_size_sec):
     """smilehip_tonespec_op_tables: dict of pitch_class_freq, bin_key, nbins, filter_map, note_rec [n_notes x 4], first_last"""
     L = load()
@@ -979,12 +1107,13 @@ class Batch:
         return out, tap
 
     def chroma_run_host(self, pcm, ld_out=None, fill=0.0, runs=1):
-        """chroma_fft chain plans: run on host data (int16 samples through smilehip_lld_run, a float32 array through
+        """chroma_fft / chroma_filt chain plans: run on host data (int16 samples through smilehip_lld_run, a float32 array through
         smilehip_lld_run_f32) into a matrix [total_rows x ld_out] that held `fill` everywhere before, `runs` times over.
         Returns it and the tap [total_frames x n_notes], the level tonespec (smilehip_batch_chroma_taps)."""
         L = load()
         ctx = self.plan.ctx._h
-        n_notes = 12 * self.plan.cfg.tonespec_n_octaves
+        cfg = self.plan.cfg
+        n_notes = max(cfg.tonefilt_n_notes, 1) if cfg.chain_kind == CHAIN_CHROMA_FILT else 12 * cfg.tonespec_n_octaves
         ld_out = self.plan.geometry.n_out if ld_out is None else ld_out
         f32 = np.asarray(pcm).dtype == np.float32
         pcm = np.ascontiguousarray(pcm, dtype=np.float32 if f32 else np.int16)

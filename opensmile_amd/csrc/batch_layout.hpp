@@ -11,6 +11,7 @@
 
 #include "../../include/smilehip.h"
 #include "lld_tile_rec.hpp"
+#include "lld_tonefilt_ops.hpp"
 
 namespace smilehip {
 
@@ -54,6 +55,11 @@ inline int compare_run_frames(int64_t total_frames) {
 }
 
 inline int64_t layout_num_frames(int64_t len, int64_t N, int64_t H) { return len < N ? 0 : (len - N) / H + 1; }
+// chroma_filt has no framer: cTonefilt reads blocks of N = H samples and, at the end of input, one more that holds the samples left
+// over (tonefilt::rows_of, lld_tonefilt_ops.hpp)
+inline int64_t layout_num_frames(const BatchLayoutSpec &s, int64_t len) {
+  return s.chain_kind == SMILEHIP_CHAIN_CHROMA_FILT ? tonefilt::rows_of(len, s.H) : layout_num_frames(len, s.N, s.H);
+}
 inline int64_t samples_60ms(double period) { return std::lround(0.060 / period); }
 
 // Output rows of an utterance of `len` samples / T frames. The 20 ms chains hold rows = T60 + 1, T60 = frames of the 60 ms
@@ -62,7 +68,7 @@ inline int64_t layout_rows(const BatchLayoutSpec &s, int64_t len, int64_t T) {
   const bool compare = s.chain_kind == SMILEHIP_CHAIN_COMPARE_AB || s.chain_kind == SMILEHIP_CHAIN_COMPARE;
   // prosodyShs: cPitchSmoother's level holds T - 1 frames (no output for its first call), the smoother adds its end-of-input rows
   if (s.chain_kind == SMILEHIP_CHAIN_PROSODY_SHS) return T >= 2 ? T - 1 + s.row_extra : 0;
-  // (IS09 and prosodyAcf: T + smaWin / 2 rows, prosody_acf::rows_of; chroma_fft: T rows, chroma::rows_of)
+  // (IS09 and prosodyAcf: T + smaWin / 2 rows, prosody_acf::rows_of; chroma_fft and chroma_filt: T rows, chroma::rows_of / tonefilt::rows_of)
   if (!compare && s.chain_kind != SMILEHIP_CHAIN_EGEMAPS) return T > 0 ? T + s.row_extra : 0;
   const int64_t T60 = layout_num_frames(len, samples_60ms(s.period), s.H);
   return T60 >= (compare ? 4 : 1) ? T60 + 1 : 0;
@@ -123,13 +129,13 @@ inline int batch_layout(const BatchLayoutSpec &s, const int64_t *h_off, int32_t 
   if (egemaps) out.fin_off.assign(size_t(n_utt) + 1, 0);
   {                                                      // the run length of the 20 ms frame kernels (lld_compare.hip / lld_gemaps.hip)
     int64_t total_T = 0;
-    for (int32_t u = 0; u < n_utt; ++u) total_T += layout_num_frames(h_off[u + 1] - h_off[u], s.N, s.H);
+    for (int32_t u = 0; u < n_utt; ++u) total_T += layout_num_frames(s, h_off[u + 1] - h_off[u]);
     out.run_frames = s.run_frames_override >= 1 ? s.run_frames_override : compare_run_frames(total_T);
   }
   for (int32_t u = 0; u < n_utt; ++u) {
     const int64_t len = h_off[u + 1] - h_off[u];
     if (len < 0) return u + 1;
-    const int64_t T = layout_num_frames(len, s.N, s.H);
+    const int64_t T = layout_num_frames(s, len);
     const int64_t rows = layout_rows(s, len, T);
     if (compare || egemaps)
       for (int64_t t0 = 0; t0 < T; t0 += out.run_frames) {

@@ -81,6 +81,13 @@ hipError_t stage_tonespec(const float *fmap, const chroma::NoteRec *rec, int n_s
                           float *dst, int64_t ld_dst, int64_t n_frames, hipStream_t s);
 hipError_t stage_chroma(int n_src, int octave_size, float sil_thresh, const float *src, int64_t ld_src, float *dst, int64_t ld_dst,
                         int64_t n_frames, hipStream_t s);
+// chroma_filt.conf: lld_tonefilt_scan writes Q.tonespec (lld_tonefilt.hip); cChroma follows as stage_chroma over that level
+hipError_t launch_tonefilt(const TonefiltParams &Q, const int16_t *pcm, const float *pcm_f32, hipStream_t s);
+// cTonefilt as a stream (smilehip_tonefilt_op_blocks): n_blocks x P samples that start at sample pos0, state [n_notes] in device memory
+hipError_t stage_tonefilt_blocks(const TonefiltParams &Q, const float *samples, int64_t n_blocks, int64_t pos0, tonefilt::State *state,
+                                 float *dst, hipStream_t s);
+// sincos_d (lld_sincos_d.hpp) on n doubles: smilehip_sincos_d_values
+hipError_t stage_sincos_d(const double *x, int64_t n, double *sn, double *cs, hipStream_t s);
 int f0_chunk_tiles();
 int f0_tile_frames();
 // cPitchSmootherViterbi as a stream: one frame (or the flush) per launch, state in global memory

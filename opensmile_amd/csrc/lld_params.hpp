@@ -2,6 +2,7 @@
 // code (lld_kernels.hip). Plain data, passed by value at launch.
 #pragma once
 #include "lld_chroma_ops.hpp"
+#include "lld_tonefilt_ops.hpp"
 #include "lld_device.hpp"
 #include "lld_ooura.hpp"
 #include "lld_ooura_wave.hpp"
@@ -208,6 +209,20 @@ struct ChromaParams {
   int32_t n_notes, use_power;
   int32_t octave_size;              // the chain's outputs per frame
   float sil_thresh;
+};
+
+// chroma_filt.conf (lld_tonefilt.hip, lld_tonefilt_ops.hpp): the parameters of lld_tonefilt_scan and of the stream operator's kernel
+// (which reads tab, n_notes, P and period alone)
+struct TonefiltParams {
+  const tonefilt::NoteTab *tab;     // [n_notes]
+  int32_t n_notes;
+  int32_t P;                        // samples per block
+  double period;                    // inputPeriod
+  const int64_t *samp_off;          // [n_utt + 1]
+  const int64_t *frame_off;         // [n_utt + 1] rows (= whole blocks) in front of each utterance
+  int32_t n_utt;
+  int64_t total_frames;
+  float *tonespec;                  // [total_frames x n_notes] the level tonespec (smilehip_batch_chroma_taps), packed
 };
 
 // eGeMAPSv02 / GeMAPSv01b LLD level (lld_gemaps.hip): per-frame scratch and constants

@@ -62,6 +62,19 @@ static int alloc_chroma_scratch(smilehip_plan *plan, smilehip_batch *b, const Ba
   return SMILEHIP_OK;
 }
 
+// chroma_filt: the level tonespec; inputs that would carry the recursion's argument out of sincos_d's domain are refused here
+static int alloc_chroma_filt_scratch(smilehip_plan *plan, smilehip_batch *b) {
+  int64_t longest = 0;
+  for (int32_t u = 0; u < b->n_utt; ++u) longest = std::max(longest, b->h_samp_off[u + 1] - b->h_samp_off[u]);
+  longest = tonefilt::rows_of(longest, plan->tonefilt.P) * plan->tonefilt.P;   // (the last block runs to its end)
+  if (tonefilt_check_domain(plan->tonefilt, longest))
+    return fail(SMILEHIP_ERR_INVALID, "chroma_filt chain: an utterance of %lld samples carries 2 pi freq[nNotes - 1] t past the domain of sincos_d (2^30)",
+                (long long)longest);
+  if (b->d_tonespec.alloc(at_least_one(b->total_frames) * (size_t)plan->tonefilt.n_notes))
+    return fail(SMILEHIP_ERR_HIP, "hipMalloc of the chroma_filt scratch matrix failed");
+  return SMILEHIP_OK;
+}
+
 static int alloc_compare_ab_scratch(smilehip_batch *b, const BatchLayout &L) {
   int rc;
   b->n_runs = (int32_t)L.run_utt.size();
@@ -154,7 +167,8 @@ extern "C" int smilehip_batch_create(smilehip_plan *plan, const int64_t *h_off, 
   *out = nullptr;
   if (!plan->ctx) return fail(SMILEHIP_ERR_NO_DEVICE, "host-only plan: no device attached (tables only)");
   if (plan->stage_mask != SMILEHIP_STAGE_ALL) return fail(SMILEHIP_ERR_INVALID, "single-component plan cannot run the fused chain");
-  if (int rt = require_transform(plan, "smilehip_batch_create")) return rt;
+  if (plan->cfg.chain_kind != SMILEHIP_CHAIN_CHROMA_FILT)   // (the one chain without a transform: its blocks may be shorter than 64 samples)
+    if (int rt = require_transform(plan, "smilehip_batch_create")) return rt;
   HIP_TRY(hipSetDevice(plan->ctx->device));
   std::unique_ptr<smilehip_batch> b(new (std::nothrow) smilehip_batch());
   if (!b) return fail(SMILEHIP_ERR_NOMEM, "out of host memory");
@@ -181,6 +195,7 @@ extern "C" int smilehip_batch_create(smilehip_plan *plan, const int64_t *h_off, 
     case SMILEHIP_CHAIN_PROSODY_SHS: rc = alloc_f0_frame_scratch(plan, b.get()); break;   // (no Viterbi, no jitter pass: their vectors stay empty)
     case SMILEHIP_CHAIN_PROSODY_ACF: rc = alloc_prosody_acf_scratch(b.get(), L); break;
     case SMILEHIP_CHAIN_CHROMA_FFT: rc = alloc_chroma_scratch(plan, b.get(), L); break;
+    case SMILEHIP_CHAIN_CHROMA_FILT: rc = alloc_chroma_filt_scratch(plan, b.get()); break;
     case SMILEHIP_CHAIN_COMPARE: rc = alloc_compare_scratch(plan, b.get(), L); break;
     case SMILEHIP_CHAIN_EGEMAPS: rc = alloc_egemaps_scratch(plan, b.get(), L); break;
     case SMILEHIP_CHAIN_MFCC:
@@ -503,6 +518,34 @@ static int chroma_run(smilehip_plan *plan, smilehip_batch *b, const int16_t *d_p
   hipError_t e = launch_chroma(P, Q, s);
   if (e != hipSuccess) return fail(SMILEHIP_ERR_HIP, "chroma_fft kernel launch failed: %s", hipGetErrorString(e));
   if ((trc = timing_mark(plan, 1, s))) return trc;
+  return timing_mark(plan, 2, s);
+}
+
+// SMILEHIP_CHAIN_CHROMA_FILT: lld_tonefilt_scan writes the tonespec level into the scratch, lld_chroma_rows the chroma rows into d_out
+static int chroma_filt_run(smilehip_plan *plan, smilehip_batch *b, const int16_t *d_pcm, float *d_out, int64_t ld_out, void *stream) {
+  const int n_out = plan->cfg.chroma_octave_size;
+  if (ld_out < n_out) return fail(SMILEHIP_ERR_INVALID, "ld_out %lld < n_out %d", (long long)ld_out, n_out);
+  if (b->total_frames == 0) return SMILEHIP_OK;
+  if (!(d_pcm || b->run_pcm_f32) || !d_out) return fail(SMILEHIP_ERR_INVALID, "smilehip_lld_run: null device pointer");
+  hipStream_t s = (hipStream_t)stream;
+  TonefiltParams Q;
+  std::memset(&Q, 0, sizeof(Q));
+  Q.tab = plan->d_tf_tab.p;
+  Q.n_notes = plan->tonefilt.n_notes;
+  Q.P = (int32_t)plan->tonefilt.P;
+  Q.period = plan->tonefilt.period;
+  Q.samp_off = b->d_samp_off.p;
+  Q.frame_off = b->d_frame_off.p;
+  Q.n_utt = b->n_utt;
+  Q.total_frames = b->total_frames;
+  Q.tonespec = b->d_tonespec.p;
+  int trc;
+  if ((trc = timing_mark(plan, 0, s))) return trc;
+  hipError_t e = launch_tonefilt(Q, d_pcm, b->run_pcm_f32, s);
+  if (e != hipSuccess) return fail(SMILEHIP_ERR_HIP, "chroma_filt scan kernel launch failed: %s", hipGetErrorString(e));
+  if ((trc = timing_mark(plan, 1, s))) return trc;
+  e = stage_chroma(Q.n_notes, n_out, plan->cfg.chroma_sil_thresh, Q.tonespec, Q.n_notes, d_out, ld_out, b->total_frames, s);
+  if (e != hipSuccess) return fail(SMILEHIP_ERR_HIP, "chroma_filt chroma kernel launch failed: %s", hipGetErrorString(e));
   return timing_mark(plan, 2, s);
 }
 
@@ -871,10 +914,10 @@ extern "C" int smilehip_batch_prosody_acf_taps(smilehip_batch *b, float **d_raw3
   return SMILEHIP_OK;
 }
 
-// chroma_fft chain tap: the level tonespec of the last run, [total_frames x n_notes]
+// chroma_fft / chroma_filt chain tap: the level tonespec of the last run, [total_frames x n_notes]
 extern "C" int smilehip_batch_chroma_taps(smilehip_batch *b, float **d_tonespec, int64_t *n_frames) {
-  if (!b || b->plan->cfg.chain_kind != SMILEHIP_CHAIN_CHROMA_FFT)
-    return fail(SMILEHIP_ERR_INVALID, "smilehip_batch_chroma_taps: not a chroma_fft chain batch");
+  if (!b || (b->plan->cfg.chain_kind != SMILEHIP_CHAIN_CHROMA_FFT && b->plan->cfg.chain_kind != SMILEHIP_CHAIN_CHROMA_FILT))
+    return fail(SMILEHIP_ERR_INVALID, "smilehip_batch_chroma_taps: not a chroma_fft chain batch (nor a chroma_filt one)");
   if (d_tonespec) *d_tonespec = b->d_tonespec.p;
   if (n_frames) *n_frames = b->total_frames;
   return SMILEHIP_OK;
@@ -960,6 +1003,7 @@ extern "C" int smilehip_lld_run(smilehip_plan *plan, smilehip_batch *b, const in
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_SHS) return prosody_shs_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_ACF) return prosody_acf_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT) return chroma_run(plan, b, d_pcm, d_out, ld_out, stream);
+  if (plan->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FILT) return chroma_filt_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE) return compare_full_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_EGEMAPS) return egemaps_run(plan, b, d_pcm, d_out, ld_out, stream);
   return is09_run(plan, b, d_pcm, d_out, ld_out, stream);

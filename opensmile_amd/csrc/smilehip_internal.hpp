@@ -17,6 +17,7 @@
 
 #include "../../include/smilehip.h"
 #include "chroma_tables.hpp"
+#include "tonefilt_tables.hpp"
 #include "lld_launch.hpp"
 #include "lld_ooura.hpp"
 #include "lld_params.hpp"
@@ -170,6 +171,9 @@ struct smilehip_plan {
   TonespecHost tonespec;
   DevBuf<float> d_ts_fmap;
   DevBuf<chroma::NoteRec> d_ts_rec;
+  // chroma_filt chain: cTonefilt's per-note table (tonefilt_tables.hpp)
+  TonefiltHost tonefilt;
+  DevBuf<tonefilt::NoteTab> d_tf_tab;
   // eGeMAPS chain: cSpecResample's tables (transposed), cSpectral's band-slope edges and frequency range
   DevBuf<float> d_rs_cos, d_rs_sin;
   DevBuf<uint64_t> d_fm_flags;              // smilehip_formantlpc_rows: GemapsParams::fm_flags of the largest call so far
@@ -249,7 +253,7 @@ struct smilehip_batch {
   int32_t run_frames = 8;               // frames per run (compare_run_frames)
   std::vector<int32_t> h_short;
   DevBuf<int64_t> d_samp_off, d_frame_off;
-  DevBuf<float> d_tonespec;        // chroma_fft chain: the level tonespec, [total_frames x n_notes]
+  DevBuf<float> d_tonespec;        // chroma_fft / chroma_filt chain: the level tonespec, [total_frames x n_notes]
   DevBuf<float> d_raw3;            // prosodyAcf chain: [total_frames x 3] voiceProb | pitch candidate -> contour | loudness
   DevBuf<int32_t> d_frame_utt;     // IS09 / prosodyAcf chain: utterance of every frame (the frame kernel has one frame per wave and would search frame_off for it)
   DevBuf<int32_t> d_tile_utt, d_tile_t0, d_short, d_dtile_utt, d_dtile_t0;

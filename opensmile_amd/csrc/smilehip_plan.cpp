@@ -4,6 +4,9 @@
 static_assert(offsetof(smilehip_lld_config, acf_cep_use_power) + sizeof(int32_t) == SMILEHIP_LLD_CONFIG_SIZE_V1,
               "SMILEHIP_LLD_CONFIG_SIZE_V1 is the struct's size up to and including acf_cep_use_power");
 static_assert(offsetof(smilehip_lld_config, tonespec_n_octaves) == SMILEHIP_LLD_CONFIG_SIZE_V1, "the chroma fields start where the older struct ends");
+static_assert(offsetof(smilehip_lld_config, reserved_chroma) + sizeof(int32_t) == SMILEHIP_LLD_CONFIG_SIZE_V2 &&
+                  offsetof(smilehip_lld_config, tonefilt_n_notes) == SMILEHIP_LLD_CONFIG_SIZE_V2,
+              "SMILEHIP_LLD_CONFIG_SIZE_V2 is the struct's size up to and including reserved_chroma; the tonefilt fields start there");
 
 // the base of every preset that existed before the struct grew: it fills SMILEHIP_LLD_CONFIG_SIZE_V1 bytes and says so in struct_size (the
 // header's struct_size rules: a caller whose struct ends there is not written past its end)
@@ -185,11 +188,11 @@ extern "C" void smilehip_config_prosody_acf(smilehip_lld_config *c) {
   c->sma_win = 3;                    // [smo:cContourSmoother] smaWin = 3
 }
 
-// config/chroma/chroma_fft.conf: the full struct
+// config/chroma/chroma_fft.conf: the struct as far as its own fields reach (SMILEHIP_LLD_CONFIG_SIZE_V2)
 extern "C" void smilehip_config_chroma_fft(smilehip_lld_config *c, double sample_rate) {
-  std::memset(c, 0, sizeof(*c));
+  std::memset(c, 0, SMILEHIP_LLD_CONFIG_SIZE_V2);
   smilehip_config_mfcc12_0_d_a(c);   // (the mel / DCT fields are not read by this chain)
-  c->struct_size = sizeof(*c);
+  c->struct_size = SMILEHIP_LLD_CONFIG_SIZE_V2;
   c->chain_kind = SMILEHIP_CHAIN_CHROMA_FFT;
   c->sample_rate = sample_rate;
   c->frame_size_sec = 0.064;         // [framer:cFramer] frameSize = 0.064, frameStep = 0.010
@@ -208,12 +211,35 @@ extern "C" void smilehip_config_chroma_fft(smilehip_lld_config *c, double sample
   c->chroma_sil_thresh = (float)0.001;   // the default (chroma.cpp:49), kept as FLOAT_DMEM (:71)
 }
 
+// config/chroma/chroma_filt.conf: the full struct
+extern "C" void smilehip_config_chroma_filt(smilehip_lld_config *c, double sample_rate) {
+  std::memset(c, 0, sizeof(*c));
+  smilehip_config_mfcc12_0_d_a(c);   // (nothing of the window / transform / mel / DCT part is read by this chain)
+  c->struct_size = sizeof(*c);
+  c->chain_kind = SMILEHIP_CHAIN_CHROMA_FILT;
+  c->sample_rate = sample_rate;
+  c->tonefilt_n_notes = 72;          // [tonefilt:cTonefilt]
+  c->tonefilt_first_note = 55.0;
+  c->tonefilt_decay_f0 = 0.9999;
+  c->tonefilt_decay_fn = 0.999;
+  c->tonefilt_output_period = 0.01;
+  c->frame_size_sec = c->frame_step_sec = c->tonefilt_output_period;   // the block length as the plan's frame geometry
+  c->preemph = 0;
+  c->win_func = SMILEHIP_WIN_RECT;
+  c->n_delta = 0;
+  c->chroma_octave_size = 12;        // [chroma:cChroma]
+  c->chroma_sil_thresh = (float)0.001;
+}
+
 static inline bool is_compare_ab_like(const smilehip_lld_config &c) {
   return c.chain_kind == SMILEHIP_CHAIN_COMPARE_AB || c.chain_kind == SMILEHIP_CHAIN_COMPARE;
 }
 
 // ------------------------------------------------------------------- plan
 // the caller's struct as far as its struct_size reaches (the header's struct_size rules), zeros behind it
+static bool config_size_known(uint32_t n) {
+  return n == sizeof(smilehip_lld_config) || n == SMILEHIP_LLD_CONFIG_SIZE_V2 || n == SMILEHIP_LLD_CONFIG_SIZE_V1;
+}
 static void copy_config(smilehip_lld_config &dst, const smilehip_lld_config *src) {
   std::memset(&dst, 0, sizeof(dst));
   std::memcpy(&dst, src, std::min<size_t>(src->struct_size, sizeof(dst)));
@@ -225,7 +251,8 @@ static int build_tables(smilehip_plan *p, bool upload = true) {
   if (p->geo.Nfft > 8192) return fail(SMILEHIP_ERR_INVALID, "FFT length %lld > 8192 unsupported", (long long)p->geo.Nfft);
   const uint32_t mask = p->cfg.stage_mask ? p->cfg.stage_mask : SMILEHIP_STAGE_ALL;
   // the tables built: the prosodyAcf chain has no mel bank and no DCT (its frames may be shorter than a bank has bands)
-  const bool no_mel = p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_ACF || p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT;   // (chroma_fft likewise)
+  const bool no_mel = p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_ACF || p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT ||
+                      p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FILT;   // (chroma_fft and chroma_filt likewise)
   const uint32_t tmask = no_mel ? (mask & ~(SMILEHIP_STAGE_MEL | SMILEHIP_STAGE_MFCC)) : mask;
   p->h_window.assign(size_t(p->geo.N), 1.0f);
   if ((mask & SMILEHIP_STAGE_WINDOW) && (rc = make_window(p->cfg, p->geo.N, p->h_window)) != SMILEHIP_OK)
@@ -296,8 +323,8 @@ static int build_tables(smilehip_plan *p, bool upload = true) {
   } else if (p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT) {
     // everything the chain cannot express is refused with the option named
     const smilehip_lld_config &c = p->cfg;
-    if (c.struct_size < sizeof(smilehip_lld_config))
-      return fail(SMILEHIP_ERR_INVALID, "chroma_fft chain: struct_size %u does not cover the tonespec / chroma fields (%zu)", c.struct_size, sizeof(smilehip_lld_config));
+    if (c.struct_size < SMILEHIP_LLD_CONFIG_SIZE_V2)
+      return fail(SMILEHIP_ERR_INVALID, "chroma_fft chain: struct_size %u does not cover the tonespec / chroma fields (%u)", c.struct_size, SMILEHIP_LLD_CONFIG_SIZE_V2);
     if (mask != SMILEHIP_STAGE_ALL) return fail(SMILEHIP_ERR_INVALID, "chroma_fft chain: stage_mask must be all stages");
     if (c.n_delta != 0) return fail(SMILEHIP_ERR_INVALID, "chroma_fft chain: n_delta must be 0 (the file has no cDeltaRegression); got %d", c.n_delta);
     if (c.preemph) return fail(SMILEHIP_ERR_INVALID, "chroma_fft chain: preemph must be 0 (the file has no cVectorPreemphasis)");
@@ -317,6 +344,26 @@ static int build_tables(smilehip_plan *p, bool upload = true) {
     const char *why = "";
     if ((rc = make_tonespec_tables(to, p->geo.K, p->geo.fft_frame_size_sec, p->tonespec, &why)))
       return fail(rc, "chroma_fft chain: cTonespec (tonespec_*): %s", why);
+  } else if (p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FILT) {
+    const smilehip_lld_config &c = p->cfg;
+    if (c.struct_size < sizeof(smilehip_lld_config))
+      return fail(SMILEHIP_ERR_INVALID, "chroma_filt chain: struct_size %u does not cover the tonefilt fields (%zu)", c.struct_size, sizeof(smilehip_lld_config));
+    if (mask != SMILEHIP_STAGE_ALL) return fail(SMILEHIP_ERR_INVALID, "chroma_filt chain: stage_mask must be all stages");
+    if (c.n_delta != 0) return fail(SMILEHIP_ERR_INVALID, "chroma_filt chain: n_delta must be 0 (the file has no cDeltaRegression); got %d", c.n_delta);
+    if (c.preemph) return fail(SMILEHIP_ERR_INVALID, "chroma_filt chain: preemph must be 0 (the file has no cVectorPreemphasis)");
+    const smilehip_tonefilt_opts to = {c.tonefilt_n_notes, 0, c.tonefilt_first_note, c.tonefilt_decay_f0, c.tonefilt_decay_fn, c.tonefilt_output_period};
+    const char *why = "";
+    if ((rc = make_tonefilt_tables(to, c.sample_rate, p->tonefilt, &why))) return fail(rc, "chroma_filt chain: cTonefilt (tonefilt_*): %s", why);
+    // the batch layout's frames are the blocks: frame_size_sec = frame_step_sec = outputPeriod must have given N = H = P
+    if (p->geo.N != p->tonefilt.P || p->geo.H != p->tonefilt.P)
+      return fail(SMILEHIP_ERR_INVALID, "chroma_filt chain: frame_size_sec and frame_step_sec must both be tonefilt_output_period (blocks of %lld samples; they give %lld / %lld)",
+                  (long long)p->tonefilt.P, (long long)p->geo.N, (long long)p->geo.H);
+    if (c.chroma_octave_size < 1 || c.chroma_octave_size > chroma::kMaxOctaveSize)
+      return fail(SMILEHIP_ERR_INVALID, "chroma_filt chain: chroma_octave_size (cChroma octaveSize) must be 1 .. %d; got %d", chroma::kMaxOctaveSize, c.chroma_octave_size);
+    if (p->tonefilt.n_notes % c.chroma_octave_size)
+      return fail(SMILEHIP_ERR_INVALID, "chroma_filt chain: tonefilt_n_notes = %d notes are no multiple of chroma_octave_size %d (cChroma writes no values then)",
+                  p->tonefilt.n_notes, c.chroma_octave_size);
+    if (!(c.chroma_sil_thresh == c.chroma_sil_thresh)) return fail(SMILEHIP_ERR_INVALID, "chroma_filt chain: chroma_sil_thresh is not a number");
   } else if (p->cfg.chain_kind != SMILEHIP_CHAIN_MFCC) {
     return fail(SMILEHIP_ERR_INVALID, "unknown chain_kind %d", p->cfg.chain_kind);
   }
@@ -377,6 +424,7 @@ static int build_tables(smilehip_plan *p, bool upload = true) {
     return rc;
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT && ((rc = p->d_ts_fmap.upload(p->tonespec.filter_map)) || (rc = p->d_ts_rec.upload(p->tonespec.rec))))
     return rc;
+  if (p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FILT && (rc = p->d_tf_tab.upload(p->tonefilt.tab))) return rc;
   if (f0_front_chain(p->cfg.chain_kind) &&
       ((rc = p->d_f0_rec.upload(p->f0.sp_rec)) || (rc = p->d_f0_d1.upload(p->f0.sp_d1)) || (rc = p->d_f0_d2.upload(p->f0.sp_d2)) ||
        (rc = p->d_f0_co.upload(p->f0.ip_co)) || (rc = p->d_f0_audw.upload(p->f0.audw)) || (rc = p->d_f0_k.upload(p->f0.ip_k)) ||
@@ -568,7 +616,7 @@ static int build_tables(smilehip_plan *p, bool upload = true) {
 extern "C" int smilehip_plan_create(smilehip_context *ctx, const smilehip_lld_config *cfg, smilehip_plan **out) {
   if (!ctx || !cfg || !out) return fail(SMILEHIP_ERR_INVALID, "smilehip_plan_create: null argument");
   *out = nullptr;
-  if (cfg->struct_size != sizeof(smilehip_lld_config) && cfg->struct_size != SMILEHIP_LLD_CONFIG_SIZE_V1)
+  if (!config_size_known(cfg->struct_size))
     return fail(SMILEHIP_ERR_INVALID, "smilehip_lld_config.struct_size %u != %zu (ABI mismatch)", cfg->struct_size,
                 sizeof(smilehip_lld_config));
   HIP_TRY(hipSetDevice(ctx->device));
@@ -634,7 +682,7 @@ extern "C" int smilehip_plan_create(smilehip_context *ctx, const smilehip_lld_co
 extern "C" int smilehip_plan_create_host_only(const smilehip_lld_config *cfg, smilehip_plan **out) {
   if (!cfg || !out) return fail(SMILEHIP_ERR_INVALID, "smilehip_plan_create_host_only: null argument");
   *out = nullptr;
-  if (cfg->struct_size != sizeof(smilehip_lld_config) && cfg->struct_size != SMILEHIP_LLD_CONFIG_SIZE_V1)
+  if (!config_size_known(cfg->struct_size))
     return fail(SMILEHIP_ERR_INVALID, "smilehip_lld_config.struct_size %u != %zu (ABI mismatch)", cfg->struct_size,
                 sizeof(smilehip_lld_config));
   auto *p = new (std::nothrow) smilehip_plan();
@@ -654,7 +702,7 @@ extern "C" void smilehip_plan_destroy(smilehip_plan *plan) { delete plan; }
 int plan_n_static(const smilehip_plan *p) {
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE_F0) return 2;
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_SHS || p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_ACF) return 3;
-  if (p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT) return p->cfg.chroma_octave_size;
+  if (p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT || p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FILT) return p->cfg.chroma_octave_size;
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE) return 65;
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_EGEMAPS) return 25;
   return p->cfg.chain_kind == SMILEHIP_CHAIN_IS09 ? 16
@@ -681,6 +729,7 @@ extern "C" int smilehip_plan_geometry(const smilehip_plan *p, smilehip_geometry 
 
 extern "C" int64_t smilehip_num_frames(const smilehip_plan *p, int64_t n_samples) {
   if (!p) return fail(SMILEHIP_ERR_INVALID, "smilehip_num_frames: null plan");
+  if (p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FILT) return tonefilt::rows_of(n_samples, p->tonefilt.P);   // blocks, the last one padded
   if (n_samples < p->geo.N) return 0;
   return (n_samples - p->geo.N) / p->geo.H + 1;
 }
@@ -697,6 +746,7 @@ extern "C" double smilehip_row_time(const smilehip_plan *plan, int64_t n_frames,
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_SHS)
     return smilehip_frame_time(plan, n_frames >= 2 ? (row < n_frames - 2 ? row : n_frames - 2) + 1 : 0);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_MFCC || plan->cfg.chain_kind == SMILEHIP_CHAIN_PLP || plan->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT ||
+      plan->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FILT ||
       plan->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE_F0 || plan->cfg.chain_kind == SMILEHIP_CHAIN_EGEMAPS || n_frames <= 1)
     return smilehip_frame_time(plan, row);
   // IS09 and prosodyAcf (lld_prosody_acf_ops.hpp: row_time_frame): the smoother's end-of-input rows repeat the last frame's time

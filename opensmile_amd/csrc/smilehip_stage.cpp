@@ -317,6 +317,95 @@ extern "C" int smilehip_chroma_op_frames(smilehip_chroma_op *op, const float *d_
   STAGE_RET(stage_chroma(op->n_src, op->octave_size, op->sil_thresh, d_src, ld_src, d_dst, ld_dst, n_frames, (hipStream_t)stream), "chroma");
 }
 
+// ---- cTonefilt per component: the scan of the fused chroma_filt chain (lld_tonefilt_ops.hpp) as a stream with carried state
+struct smilehip_tonefilt_op {
+  smilehip_context *ctx = nullptr;
+  TonefiltHost h;
+  int64_t pos = 0, max_samples = 0;
+  DevBuf<tonefilt::NoteTab> d_tab;
+  DevBuf<tonefilt::State> d_state;
+};
+extern "C" int smilehip_tonefilt_op_destroy(smilehip_tonefilt_op *op) {
+  delete op;
+  return SMILEHIP_OK;
+}
+extern "C" int smilehip_tonefilt_op_n_out(const smilehip_tonefilt_op *op) { return op ? op->h.n_notes : -1; }
+extern "C" int64_t smilehip_tonefilt_op_block_len(const smilehip_tonefilt_op *op) { return op ? op->h.P : -1; }
+extern "C" int smilehip_tonefilt_op_tables(const smilehip_tonefilt_opts *o, double sample_rate, int64_t *block_len, double *freq, double *decay) {
+  if (!o) return fail(SMILEHIP_ERR_INVALID, "smilehip_tonefilt_op_tables: null argument");
+  TonefiltHost h;
+  const char *why = "";
+  const int rc = make_tonefilt_tables(*o, sample_rate, h, &why);
+  if (rc) return fail(rc, "cTonefilt (%g Hz): %s", sample_rate, why);
+  if (block_len) *block_len = h.P;
+  for (int n = 0; n < h.n_notes; ++n) {
+    if (freq) freq[n] = h.tab[(size_t)n].freq;
+    if (decay) decay[n] = h.tab[(size_t)n].decay;
+  }
+  return h.n_notes;
+}
+extern "C" int smilehip_tonefilt_op_reset(smilehip_tonefilt_op *op) {
+  if (!op) return fail(SMILEHIP_ERR_INVALID, "smilehip_tonefilt_op_reset: null operator");
+  HIP_TRY(hipSetDevice(op->ctx->device));
+  HIP_TRY(hipDeviceSynchronize());
+  op->pos = 0;
+  return op->d_state.upload(std::vector<tonefilt::State>((size_t)op->h.n_notes, tonefilt::State{0.0, 0.0}));
+}
+extern "C" int smilehip_tonefilt_op_create(smilehip_context *ctx, const smilehip_tonefilt_opts *o, double sample_rate, int64_t max_samples,
+                                           smilehip_tonefilt_op **out) {
+  if (!ctx || !o || !out) return fail(SMILEHIP_ERR_INVALID, "smilehip_tonefilt_op_create: null argument");
+  *out = nullptr;
+  std::unique_ptr<smilehip_tonefilt_op> op(new smilehip_tonefilt_op);
+  const char *why = "";
+  int rc = make_tonefilt_tables(*o, sample_rate, op->h, &why);
+  if (rc) return fail(rc, "cTonefilt (%g Hz): %s", sample_rate, why);
+  if (max_samples < 0 || tonefilt_check_domain(op->h, max_samples))
+    return fail(SMILEHIP_ERR_INVALID, "cTonefilt: a stream of %lld samples carries 2 pi freq[nNotes - 1] t past the domain of sincos_d (2^30)",
+                (long long)max_samples);
+  op->ctx = ctx;
+  op->max_samples = max_samples;
+  if ((rc = op->d_tab.upload(op->h.tab)) || (rc = smilehip_tonefilt_op_reset(op.get()))) return rc;
+  *out = op.release();
+  return SMILEHIP_OK;
+}
+extern "C" int smilehip_tonefilt_op_blocks(smilehip_tonefilt_op *op, const float *d_samples, int64_t n_blocks, float *d_dst, void *stream) {
+  if (!op) return fail(SMILEHIP_ERR_INVALID, "smilehip_tonefilt_op_blocks: null operator");
+  if (n_blocks < 0 || (n_blocks > 0 && (!d_samples || !d_dst))) return fail(SMILEHIP_ERR_INVALID, "smilehip_tonefilt_op_blocks: bad argument");
+  if (n_blocks == 0) return SMILEHIP_OK;
+  if (n_blocks > (op->max_samples - op->pos) / op->h.P)
+    return fail(SMILEHIP_ERR_INVALID, "smilehip_tonefilt_op_blocks: %lld blocks behind sample %lld leave the %lld samples the operator was created for "
+                "(the domain of sincos_d was checked for those)", (long long)n_blocks, (long long)op->pos, (long long)op->max_samples);
+  TonefiltParams Q;
+  std::memset(&Q, 0, sizeof(Q));
+  Q.tab = op->d_tab.p;
+  Q.n_notes = op->h.n_notes;
+  Q.P = (int32_t)op->h.P;
+  Q.period = op->h.period;
+  const hipError_t e = stage_tonefilt_blocks(Q, d_samples, n_blocks, op->pos, op->d_state.p, d_dst, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(SMILEHIP_ERR_HIP, "tonefilt kernel launch failed: %s", hipGetErrorString(e));
+  op->pos += n_blocks * op->h.P;
+  return SMILEHIP_OK;
+}
+extern "C" int smilehip_tonefilt_op_state(smilehip_tonefilt_op *op, int64_t *pos, double *s, double *c) {
+  if (!op) return fail(SMILEHIP_ERR_INVALID, "smilehip_tonefilt_op_state: null operator");
+  HIP_TRY(hipSetDevice(op->ctx->device));
+  HIP_TRY(hipDeviceSynchronize());
+  std::vector<tonefilt::State> st((size_t)op->h.n_notes);
+  HIP_TRY(hipMemcpy(st.data(), op->d_state.p, st.size() * sizeof(tonefilt::State), hipMemcpyDeviceToHost));
+  if (pos) *pos = op->pos;
+  for (size_t n = 0; n < st.size(); ++n) {
+    if (s) s[n] = st[n].s;
+    if (c) c[n] = st[n].c;
+  }
+  return SMILEHIP_OK;
+}
+
+// the device's sincos_d on n doubles (tests / diagnostics)
+extern "C" int smilehip_sincos_d_values(smilehip_context *ctx, const double *d_x, int64_t n, double *d_sin, double *d_cos, void *stream) {
+  if (!ctx || n < 0 || (n > 0 && (!d_x || !d_sin || !d_cos))) return fail(SMILEHIP_ERR_INVALID, "smilehip_sincos_d_values: bad argument");
+  STAGE_RET(stage_sincos_d(d_x, n, d_sin, d_cos, (hipStream_t)stream), "sincos_d");
+}
+
 extern "C" int smilehip_preemphasis_frames(smilehip_context *ctx, const float *d_src, int64_t ld_src, float *d_dst,
                                            int64_t ld_dst, int64_t n_frames, int64_t N, float k, int de, void *stream) {
   if (!ctx || N < 1) return fail(SMILEHIP_ERR_INVALID, "smilehip_preemphasis_frames: bad argument");

@@ -397,6 +397,11 @@ void conf_apply_f0_params(const ConfPlan &p, smilehip_lld_config &c) {
     else if (kv.first == "tonespec_dba") c.tonespec_dba = (int32_t)kv.second;
     else if (kv.first == "chroma_octave_size") c.chroma_octave_size = (int32_t)kv.second;
     else if (kv.first == "chroma_sil_thresh") c.chroma_sil_thresh = (float)kv.second;
+    else if (kv.first == "tonefilt_n_notes") c.tonefilt_n_notes = (int32_t)kv.second;
+    else if (kv.first == "tonefilt_first_note") c.tonefilt_first_note = kv.second;
+    else if (kv.first == "tonefilt_decay_f0") c.tonefilt_decay_f0 = kv.second;
+    else if (kv.first == "tonefilt_decay_fn") c.tonefilt_decay_fn = kv.second;
+    else if (kv.first == "tonefilt_output_period") c.tonefilt_output_period = c.frame_size_sec = c.frame_step_sec = kv.second;   // (the block is the plan's frame)
   }
 }
 
@@ -934,6 +939,98 @@ bool conf_to_chroma_fft(const ConfFile &f, ConfPlan &p, std::string &err) {
     what += buf;
   }
   p.describe = "the graph of chroma_fft.conf with the file's own parameter values (" + what + ")";
+  return true;
+}
+
+// ---- smilextract_hip --set chroma_filt -C file: config/chroma/chroma_filt.conf, possibly with other values of the options the chain takes
+// as parameters (cTonefilt nNotes, firstNote, decayF0, decayFN, outputPeriod; cChroma octaveSize, silThresh). Walked like chroma_fft.conf
+// above. An nNotes that is no multiple of octaveSize is refused: the binary then writes rows of zeros (cChroma logs an error per frame,
+// chroma.cpp:113-115), which no chain here reproduces. (Plain -C does not map the file.)
+bool conf_to_chroma_filt(const ConfFile &f, ConfPlan &p, std::string &err) {
+  p = ConfPlan();
+  static const std::vector<std::string> types = {"cTonefilt", "cChroma"};
+  std::map<std::string, const ConfInstance *> one;
+  for (const ConfInstance &i : f.inst) {
+    if (is_io_type(i.type)) continue;
+    if (std::find(types.begin(), types.end(), i.type) == types.end()) {
+      err = "component [" + i.name + ":" + i.type + "] is not part of the graph of chroma_filt.conf";
+      return false;
+    }
+    if (one.count(i.type)) { err = "more than one " + i.type + " ([" + i.name + "]): not the graph of chroma_filt.conf"; return false; }
+    one[i.type] = &i;
+  }
+  for (const std::string &t : types)
+    if (!one.count(t)) { err = "the graph has no " + t + ": not the graph of chroma_filt.conf"; return false; }
+  auto lvl = [](const ConfInstance *i, const char *k) { const std::string *v = i->find(k); return v ? *v : std::string(); };
+  auto wired = [&](const ConfInstance *i, const std::string &want) {
+    if (lvl(i, "reader.dmLevel") == want) return true;
+    err = "[" + i->name + ":" + i->type + "] reader.dmLevel = '" + lvl(i, "reader.dmLevel") + "', expected '" + want + "' (not the wiring of chroma_filt.conf)";
+    return false;
+  };
+  auto must_be = [](OptReader &o, const char *key, const char *want, const char *dflt) {
+    const std::string v = o.str(key, dflt);
+    if (lower(v) != lower(want) && o.err.empty())
+      o.err = "[" + o.ci.name + ":" + o.ci.type + "] " + key + " = " + v + " is not expressible on the fused path (needs " + want + ")";
+  };
+  const ConfInstance *tf = one["cTonefilt"], *ch = one["cChroma"];
+  for (const ConfInstance &i : f.inst)
+    if (i.type == "cWaveSource") {
+      if (!wired(tf, lvl(&i, "writer.dmLevel"))) return false;
+      const std::string *mm = i.find("monoMixdown");        // (waveSource.cpp: the default is 1; the chain filters ONE channel)
+      if (mm && canonical_value(*mm) != "1") { err = "[" + i.name + ":cWaveSource] monoMixdown = " + *mm + " is not expressible on the fused path (needs 1)"; return false; }
+    }
+  int n_notes = 0;
+  {                                                       // src/lld/tonefilt.cpp:33-41, :65-98
+    OptReader o(*tf);
+    double nn = o.num("nNotes", 48), fn = o.num("firstNote", 55.0), d0 = o.num("decayF0", 0.9995), dn = o.num("decayFN", 0.998), op = o.num("outputPeriod", 0.1);
+    if ((nn < 1 || nn > 120 || nn != std::floor(nn)) && o.err.empty())
+      o.err = "[" + tf->name + ":cTonefilt] nNotes = " + canonical_value(std::to_string(nn)) + " is not expressible on the fused path (needs 1 .. 120)";
+    if (!(fn > 0.0) && o.err.empty())
+      o.err = "[" + tf->name + ":cTonefilt] firstNote = " + canonical_value(std::to_string(fn)) + " is not expressible on the fused path (needs a positive frequency)";
+    if (!(op > 0.0) && o.err.empty())
+      o.err = "[" + tf->name + ":cTonefilt] outputPeriod = " + canonical_value(std::to_string(op)) + " is not expressible on the fused path (needs a positive period)";
+    n_notes = (int)nn;
+    p.f0_params["tonefilt_n_notes"] = nn;
+    p.f0_params["tonefilt_first_note"] = fn;
+    p.f0_params["tonefilt_decay_f0"] = d0;                // (clamped by the chain as the component clamps them)
+    p.f0_params["tonefilt_decay_fn"] = dn;
+    p.f0_params["tonefilt_output_period"] = op;
+    o.str("nameAppend", "tonefilt");                      // (cChroma names its outputs itself: copyInputName = 0)
+    o.num("copyInputName", 1);
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  {                                                       // src/lld/chroma.cpp:46-49, :67-75
+    OptReader o(*ch);
+    if (!wired(ch, lvl(tf, "writer.dmLevel"))) return false;
+    const double os = o.num("octaveSize", 12), st = o.num("silThresh", 0.001);
+    if ((os < 1 || os > 64 || os != std::floor(os) || (n_notes % (int)os)) && o.err.empty())
+      o.err = "[" + ch->name + ":cChroma] octaveSize = " + canonical_value(std::to_string(os)) + " is not expressible on the fused path (needs 1 .. 64 and a divisor of the " +
+              std::to_string(n_notes) + " notes of nNotes)";
+    p.f0_params["chroma_octave_size"] = os;
+    p.f0_params["chroma_sil_thresh"] = (double)(float)st;
+    o.num("processArrayFields", 1);                       // (either value: cTonefilt writes ONE array field of nNotes elements per input channel)
+    must_be(o, "nameAppend", "chroma", "chroma");
+    o.require("copyInputName", 0, 0);
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  if (!conf_check_io(f, {lvl(ch, "writer.dmLevel")}, err, true)) return false;
+  p.preset = "chroma_filt";
+  for (const ConfInstance &i : f.inst)
+    if (i.type == "cWaveSource") { const std::string *fn = i.find("filename"); if (fn) p.wave_file = *fn; }
+  const std::map<std::string, double> shipped = {{"tonefilt_n_notes", 72}, {"tonefilt_first_note", 55}, {"tonefilt_decay_f0", 0.9999}, {"tonefilt_decay_fn", 0.999},
+                                                 {"tonefilt_output_period", 0.01}, {"chroma_octave_size", 12}, {"chroma_sil_thresh", (double)(float)0.001}};
+  if (p.f0_params == shipped) {                           // the shipped file's values: the preset as it is
+    p.f0_params.clear();
+    p.describe = "the graph of chroma_filt.conf (every processing component and option identical)";
+    return true;
+  }
+  std::string what;
+  for (const auto &kv : p.f0_params) {
+    char buf[64];
+    snprintf(buf, sizeof(buf), "%s%s = %.9g", what.empty() ? "" : ", ", kv.first.c_str(), kv.second);
+    what += buf;
+  }
+  p.describe = "the graph of chroma_filt.conf with the file's own parameter values (" + what + ")";
   return true;
 }
 

@@ -89,13 +89,17 @@ bool conf_to_prosody_acf(const ConfFile &f, ConfPlan &p, std::string &err);
 // nOctaves, firstNote, filterType (as SMILEHIP_TONESPEC_*), usePower, dbA and cChroma octaveSize, silThresh under the config struct's
 // field names (tonespec_n_octaves .. chroma_sil_thresh)
 bool conf_to_chroma_fft(const ConfFile &f, ConfPlan &p, std::string &err);
+// smilextract_hip --set chroma_filt -C file: the same for config/chroma/chroma_filt.conf; preset = "chroma_filt", f0_params holds cTonefilt
+// nNotes, firstNote, decayF0, decayFN, outputPeriod and cChroma octaveSize, silThresh under the config struct's field names
+// (tonefilt_n_notes .. tonefilt_output_period, chroma_octave_size, chroma_sil_thresh)
+bool conf_to_chroma_filt(const ConfFile &f, ConfPlan &p, std::string &err);
 
 // Sources and sinks are outside the fingerprint and the plan: this checks them. Every cWaveSource must read the whole file
 // (start 0, end -1, no sample-based range, a RIFF header), every ACTIVE sink (filename other than "?") must be one
 // smilextract_hip writes (cHtkSink / cCsvSink on the lld level, cArffSink / cCsvSink / cHtkSink on the functionals level, or
 // the cepstral files' own cHtkSink) with the option values its writers implement; produced: the levels the plan writes
 // (a sink reading any other level would get nothing). false + err names the instance and option. values_only_csv: the active
-// cCsvSink must be the one of chroma_fft.conf (printHeader = 0, timestamp = 0, number = 0), what -O writes for that set.
+// cCsvSink must be the one of chroma_fft.conf / chroma_filt.conf (printHeader = 0, timestamp = 0, number = 0), what -O writes for that set.
 bool conf_check_io(const ConfFile &f, const std::set<std::string> &produced, std::string &err, bool values_only_csv = false);
 
 }  // namespace smilehip_host

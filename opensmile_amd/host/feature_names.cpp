@@ -37,7 +37,7 @@ std::vector<std::string> lld_names_htk_variant(bool plp, bool energy) {
 // the framer's "pcm" field), each with cContourSmoother's nameAppend = sma
 // config/prosody/prosodyAcf.conf, level lld: cPitchACF's outputs in the order of setupNewNames (pitchACF.cpp:111-132), then cIntensity's
 std::vector<std::string> lld_names_prosody_acf() { return {"voiceProb_sma", "F0_sma", "pcm_loudness_sma"}; }
-// config/chroma/chroma_fft.conf, level chroma: cChroma with copyInputName = 0 and nameAppend = chroma names one array field "chroma"
+// config/chroma/chroma_fft.conf and config/chroma/chroma_filt.conf (the same [chroma:cChroma] section), level chroma: cChroma with copyInputName = 0 and nameAppend = chroma names one array field "chroma"
 // of octaveSize elements (chroma.cpp:78-81); a header-printing run of the binary prints chroma[0];chroma[1]; ... ;chroma[11]
 std::vector<std::string> lld_names_chroma_fft(int octave_size) {
   std::vector<std::string> n;

@@ -43,7 +43,7 @@ std::vector<std::string> lld_names_htk_variant(bool plp, bool energy);   // MFCC
 std::vector<std::string> lld_names_is09();
 std::vector<std::string> lld_names_prosody_shs();   // prosodyShs.conf: F0final_sma, voicingFinalUnclipped_sma, pcm_loudness_sma
 std::vector<std::string> lld_names_prosody_acf();   // prosodyAcf.conf: voiceProb_sma, F0_sma, pcm_loudness_sma
-std::vector<std::string> lld_names_chroma_fft(int octave_size = 12);   // chroma_fft.conf: chroma[0] .. chroma[octaveSize - 1]
+std::vector<std::string> lld_names_chroma_fft(int octave_size = 12);   // chroma_fft.conf and chroma_filt.conf: chroma[0] .. chroma[octaveSize - 1]
 std::vector<std::string> lld_names_compare16();
 std::vector<std::string> func_names_is09();     // 384: <lld>_<functional>
 std::vector<std::string> func_names_compare16();   // 6373, the functionals level of ComParE_2016.conf
@@ -80,7 +80,7 @@ int format_f0(float v, char *dst);                   // "%.0f"; exact for every 
 // cCsvSink (src/iocore/csvSink.cpp:157-240): optional header line, 'name';frameTime;values with
 // "%.0f" for integral values and "%e" otherwise, ';' delimiter. name_column = false: no instance name in front of a row (and no
 // "name" in the header), what the component writes when the file gives it no instanceName (csvSink.cpp:205-209); a number
-// (frameIndex) column is never written. Values only = print_header, timestamp and name_column all false (chroma_fft.conf's sink).
+// (frameIndex) column is never written. Values only = print_header, timestamp and name_column all false (the sink of chroma_fft.conf and chroma_filt.conf).
 struct CsvOptions {
   bool append = false, print_header = true, timestamp = true, name_column = true;
   std::string instance_name = "unknown";

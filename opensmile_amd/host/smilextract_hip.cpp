@@ -29,6 +29,9 @@
 //                   [-C chroma_fft.conf]  only: no header, name, time stamp or number column), -csvoutput the other sets' CSV with header and
 //                                       time stamps. With -C: that file's (edited) nOctaves, firstNote, filterType, usePower, dbA,
 //                                       octaveSize and silThresh; anything else is refused by name
+//   smilextract_hip --set chroma_filt   config/chroma/chroma_filt.conf: 12 chroma values per block of 10 ms from cTonefilt's sine filter bank;
+//                   [-C chroma_filt.conf] -O and -csvoutput as for chroma_fft. With -C: that file's (edited) nNotes, firstNote, decayF0,
+//                                       decayFN, outputPeriod, octaveSize and silThresh; anything else is refused by name
 //   smilextract_hip --set gemapsv01a | egemapsv01a   the v01a files: the same columns, zeroPadSymmetric = 0, useBrokenJitterThresh = 1, maxF = 5500
 //   smilextract_hip --set gemapsv01b | egemapsv01b   config/gemaps/v01b/GeMAPSv01b.conf (18 LLDs, 62 functionals) / config/egemaps/v01b/
 //                                       eGeMAPSv01b.conf (23, 88): sub-graphs of eGeMAPSv02.conf, written as column subsets of its levels
@@ -165,9 +168,10 @@ static int run_main(int argc, char **argv, Persist *ps) {
     // --set prosody_shs | prosody_acf -C file: the set with the file's own parameter values (conf_to_prosody_shs / _acf); otherwise one or the other
     const bool set_acf = opt.count("--set") && opt["--set"] == "prosody_acf";
     const bool set_chroma = opt.count("--set") && opt["--set"] == "chroma_fft";
-    const bool set_with_conf = opt.count("--set") && (opt["--set"] == "prosody_shs" || set_acf || set_chroma);
+    const bool set_filt = opt.count("--set") && opt["--set"] == "chroma_filt";
+    const bool set_with_conf = opt.count("--set") && (opt["--set"] == "prosody_shs" || set_acf || set_chroma || set_filt);
     if (opt.count("--set") && !set_with_conf)
-      die("-C and --set exclude each other (except --set prosody_shs -C prosodyShs.conf, --set prosody_acf -C prosodyAcf.conf and --set chroma_fft -C chroma_fft.conf)");
+      die("-C and --set exclude each other (except --set prosody_shs -C prosodyShs.conf, --set prosody_acf -C prosodyAcf.conf, --set chroma_fft -C chroma_fft.conf and --set chroma_filt -C chroma_filt.conf)");
     ConfFile cf;
     std::string cerr_;
     if (!conf_parse(opt["-C"], conf_cmdline, cf, cerr_)) die("-C " + opt["-C"] + ": " + cerr_);
@@ -209,7 +213,8 @@ static int run_main(int argc, char **argv, Persist *ps) {
           opt[o.second] = dflt->second;
       }
     }
-    if (!(set_chroma ? conf_to_chroma_fft(cf, conf_plan, cerr_)
+    if (!(set_filt   ? conf_to_chroma_filt(cf, conf_plan, cerr_)
+          : set_chroma ? conf_to_chroma_fft(cf, conf_plan, cerr_)
           : set_acf  ? conf_to_prosody_acf(cf, conf_plan, cerr_)
                      : (set_with_conf ? conf_to_prosody_shs(cf, conf_plan, cerr_) : conf_to_plan(cf, conf_plan, cerr_)))) {
       ConfPlan as_set;
@@ -217,6 +222,8 @@ static int run_main(int argc, char **argv, Persist *ps) {
       const bool hint = !set_with_conf && conf_to_prosody_shs(cf, as_set, e2);
       const bool hint_acf = !set_with_conf && !hint && conf_to_prosody_acf(cf, as_set, e2);
       const bool hint_chroma = !set_with_conf && !hint && !hint_acf && conf_to_chroma_fft(cf, as_set, e2);
+      const bool hint_filt = !set_with_conf && !hint && !hint_acf && !hint_chroma && conf_to_chroma_filt(cf, as_set, e2);
+      if (hint_filt) die("-C " + opt["-C"] + " cannot run on the fused path: " + cerr_ + " -- this file runs as --set chroma_filt -C <file>");
       die("-C " + opt["-C"] + " cannot run on the fused path: " + cerr_ +
           (hint ? " -- this file runs as --set prosody_shs -C <file>"
                 : (hint_acf ? " -- this file runs as --set prosody_acf -C <file>" : (hint_chroma ? " -- this file runs as --set chroma_fft -C <file>" : ""))));
@@ -297,17 +304,20 @@ static int run_main(int argc, char **argv, Persist *ps) {
   // config/prosody/prosodyShs.conf: an LLD-only set like the cepstral files (-O = HTK, -csvoutput = CSV of the lld level)
   const bool prosody_acf = set == "prosody_acf";         // config/prosody/prosodyAcf.conf: the same kind of set
   // config/chroma/chroma_fft.conf: an LLD-only set as well; its -O is the file's cCsvSink (values only), not an HTK file
-  const bool chroma = set == "chroma_fft";
+  // config/chroma/chroma_filt.conf: the same kind of set and the same sink
+  const bool chroma_filt = set == "chroma_filt";
+  const bool chroma = set == "chroma_fft" || chroma_filt;
   const bool prosody = set == "prosody_shs" || prosody_acf || chroma;
   if (chroma) {
-    smilehip_config_chroma_fft(&vcfg, 16000.0);         // (the rate is each file's own: make_plan)
+    if (chroma_filt) smilehip_config_chroma_filt(&vcfg, 16000.0);
+    else smilehip_config_chroma_fft(&vcfg, 16000.0);     // (the rate is each file's own: make_plan)
     if (with_conf) conf_apply_f0_params(conf_plan, vcfg);   // (the names follow the file's octaveSize)
   } else if (prosody_acf) smilehip_config_prosody_acf(&vcfg);
   else if (prosody) smilehip_config_prosody_shs(&vcfg);
   const bool htk_variant = free_chain || prosody || (!is09 && !cmp16 && !egm && smilehip_config_htk_variant(&vcfg, variant.c_str()) == SMILEHIP_OK);
   const bool plp = htk_variant && vcfg.chain_kind == SMILEHIP_CHAIN_PLP;
   if (!is09 && !cmp16 && !egm && !htk_variant)
-    die("--set must be mfcc12_{0,e}_d_a[_z], plp_{0,e}_d_a[_z], is09_emotion, compare16, compare16_lld, is13_compare, egemapsv02, gemapsv01b, egemapsv01b, gemapsv01a, egemapsv01a, prosody_shs, prosody_acf or chroma_fft (or use -C file.conf)");
+    die("--set must be mfcc12_{0,e}_d_a[_z], plp_{0,e}_d_a[_z], is09_emotion, compare16, compare16_lld, is13_compare, egemapsv02, gemapsv01b, egemapsv01b, gemapsv01a, egemapsv01a, prosody_shs, prosody_acf, chroma_fft or chroma_filt (or use -C file.conf)");
   // parmKind of the files' own cHtkSink sections (the _Z files); the others write through standard_data_output_lldonly (9)
   int parm_kind = 9;
   if (variant == "MFCC12_0_D_A_Z") parm_kind = 11014;
