@@ -279,6 +279,22 @@ typedef struct smilehip_lld_config {
  * the float levels equal the binary's, the double states need not (README "Parity"). Inputs long enough to carry
  * 2 pi freq[nNotes - 1] t past sincos_d's domain, 2^30, are refused at batch creation with SMILEHIP_ERR_INVALID. */
 #define SMILEHIP_CHAIN_CHROMA_FILT 10
+/* SMILEHIP_CHAIN_AUDSPEC: the level `lld` of config/audspec/audspec.conf and audspec_compat.conf ([audspec_lldconcat:cVectorConcat]
+ * reader.dmLevel = plp;plpde;plpdede), n_bands (1 + n_delta) columns, 78 as shipped:
+ *   audSpec[0..25] | audSpec_de[0..25] | audSpec_de_de[0..25]
+ * on 25 ms frames every 10 ms: cVectorPreemphasis (k 0.97, src/dspcore/vectorPreemphasis.cpp:88-106), Hamming window,
+ * cTransformFFT zero-padded to a power of two (symmetrically in audspec.conf, behind the frame in audspec_compat.conf),
+ * cFFTmagphase, cMelspec with usePower and htkcompatible (26 bands 0 .. 8000 Hz, src/lldcore/melspec.cpp:520-570), cPlp with
+ * htkcompatible = 1 and doAud alone (src/lldcore/plp.cpp:489-510: melfloor forced to 1.0, :153-163; the HTK equal-loudness weight
+ * at the band centre; (FLOAT_DMEM)pow((double)v, (double)compression); doIDFT = doLP = doLpToCeps = 0 copies the bands out, :584-588,
+ * under the name audSpec, :259-266), two cDeltaRegression stages (src/dspcore/deltaRegression.cpp:144-152) and cVectorConcat.
+ * first_mfcc, last_mfcc, cep_lifter and plp_lp_order are not read: cPlp's lpOrder, firstCC, cepLifter and nCeps have no effect on
+ * this output (measured: an edited copy gives the same bytes). melfloor is 1.0 whatever the field holds.
+ * Rows per utterance, as measured against the binary: T = (n - N) / H + 1 for n >= N samples, none below (audspec::rows_of,
+ * lld_audspec_ops.hpp) -- the MFCC chain's rule, T = 1, 2 and 3 included: the regression levels hold as many rows as the static one.
+ * One frame kernel (lld_audspec_frame: a wave per frame for transforms of 512 / 1024 points, a workgroup per frame otherwise), then
+ * the window chain. The static level is the output's first block: there is no tap. */
+#define SMILEHIP_CHAIN_AUDSPEC 11
 
 #define SMILEHIP_STAGE_WINDOW 1u
 #define SMILEHIP_STAGE_FFT    2u
@@ -370,6 +386,15 @@ void smilehip_config_chroma_fft(smilehip_lld_config *c, double sample_rate);
  *   octaveSize 12 and silThresh at its default 0.001 (:54-59, chroma.cpp:49).
  * frame_size_sec = frame_step_sec = outputPeriod: the plan's frame_size / frame_step are the block length P. */
 void smilehip_config_chroma_filt(smilehip_lld_config *c, double sample_rate);
+/* fills c -- SMILEHIP_LLD_CONFIG_SIZE_V1 bytes, struct_size = that -- with config/audspec/audspec.conf (chain_kind = AUDSPEC, 78
+ * columns); the caller sets sample_rate afterwards, as with the MFCC / PLP presets:
+ *   [audspec_frame:cFramer] 0.025 / 0.010 s; [audspec_pe:cVectorPreemphasis] k 0.97, de 0; [audspec_win:cWindower] ham, gain 1,
+ *   offset 0; [audspec_fft:cTransformFFT] sets nothing: zeroPadSymmetric at its default 1; [audspec_melspec:cMelspec] htkcompatible,
+ *   nBands 26, usePower, 0 .. 8000 Hz; [audspec_plp:cPlp] compression 0.33, htkcompatible, doAud alone; [audspec_delta], [audspec_accel]
+ *   deltawin 2 */
+void smilehip_config_audspec(smilehip_lld_config *c);
+/* ... with config/audspec/audspec_compat.conf: the same graph with [fft:cTransformFFT] zeroPadSymmetric = 0 */
+void smilehip_config_audspec_compat(smilehip_lld_config *c);
 
 /* F0 group, per component, on an F0 chain plan (smilehip_config_compare16_f0; the plan's spectrum geometry -- n_bins and
  * the level's frameSizeSec, force_fft_frame_size_sec -- must be the input level's):

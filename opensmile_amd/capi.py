@@ -233,6 +233,8 @@ SYMBOLS = {
     "smilehip_batch_prosody_acf_taps": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
     "smilehip_config_chroma_fft": (None, [C.POINTER(LldConfigChroma), _dbl]),
     "smilehip_batch_chroma_taps": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "smilehip_config_audspec": (None, [C.POINTER(LldConfig)]),
+    "smilehip_config_audspec_compat": (None, [C.POINTER(LldConfig)]),
     "smilehip_tonespec_op_create": (C.c_int, [_vp, _vp, _i64, _dbl, _vp]),
     "smilehip_tonespec_op_n_out": (C.c_int, [_vp]),
     "smilehip_tonespec_op_frames": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp]),
@@ -648,6 +650,18 @@ def chroma_filt_config(sample_rate=16000.0):
     """config/chroma/chroma_filt.conf (chain_kind = CHROMA_FILT): chroma[0] .. chroma[11]; the full struct (LldConfigChromaFilt)"""
     c = LldConfigChromaFilt()
     load().smilehip_config_chroma_filt(C.byref(c), float(sample_rate))
+    return c
+
+
+CHAIN_AUDSPEC = 11
+
+
+def audspec_config(sample_rate=16000.0, compat=False):
+    """config/audspec/audspec.conf (chain_kind = AUDSPEC): audSpec[0..25] | audSpec_de[0..25] | audSpec_de_de[0..25]; compat:
+    audspec_compat.conf (zeroPadSymmetric = 0). The presets fill LLD_CONFIG_SIZE_V1 bytes; the sample rate is set here."""
+    c = LldConfig()
+    (load().smilehip_config_audspec_compat if compat else load().smilehip_config_audspec)(C.byref(c))
+    c.sample_rate = float(sample_rate)
     return c
 
 
@@ -1141,6 +1155,35 @@ class Batch:
             L.smilehip_free(ctx, d_pcm)
             L.smilehip_free(ctx, d_out)
         return out, tap
+
+    def audspec_run_host(self, pcm, ld_out=None, fill=0.0, runs=1):
+        """audspec chain plans (run_host serves them as well): run on host data (int16 samples through smilehip_lld_run, a float32
+        array through smilehip_lld_run_f32) into a matrix [total_rows x ld_out] that held `fill` everywhere before, `runs` times
+        over. The static level is the matrix's first n_static columns: there is no tap."""
+        L = load()
+        ctx = self.plan.ctx._h
+        assert self.plan.cfg.chain_kind == CHAIN_AUDSPEC, "not an audspec chain plan"
+        ld_out = self.plan.geometry.n_out if ld_out is None else ld_out
+        f32 = np.asarray(pcm).dtype == np.float32
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32 if f32 else np.int16)
+        out = np.full((self.total_rows, ld_out), fill, np.float32)
+        d_pcm, d_out = _vp(), _vp()
+        _check(L.smilehip_alloc(ctx, max(pcm.nbytes, 4), C.byref(d_pcm)))
+        _check(L.smilehip_alloc(ctx, max(out.nbytes, 4), C.byref(d_out)))
+        try:
+            if pcm.nbytes:
+                _check(L.smilehip_copy_to_device(ctx, d_pcm, pcm.ctypes.data, pcm.nbytes, None))
+            if out.nbytes:
+                _check(L.smilehip_copy_to_device(ctx, d_out, out.ctypes.data, out.nbytes, None))
+            for _ in range(runs):
+                _check((L.smilehip_lld_run_f32 if f32 else L.smilehip_lld_run)(self.plan._h, self._h, d_pcm, d_out, ld_out, None))
+            _check(L.smilehip_stream_synchronize(ctx, None))
+            if out.nbytes:
+                _check(L.smilehip_copy_to_host(ctx, out.ctypes.data, d_out, out.nbytes, None))
+        finally:
+            L.smilehip_free(ctx, d_pcm)
+            L.smilehip_free(ctx, d_out)
+        return out
 
     def func_rows(self):
         """LLD rows each utterance's functionals summarise (IS09 chain plans)."""

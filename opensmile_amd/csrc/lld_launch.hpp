@@ -76,6 +76,11 @@ int prosody_acf_wave_frames();      // frames per workgroup of the wave form
 // chain's rows P.out (lld_chroma.hip). P.frame_utt is required.
 hipError_t launch_chroma(const LldParams &P, const ChromaParams &Q, hipStream_t s);
 int64_t chroma_wave_grid_cap(int n_cu, int64_t lds_bytes);   // workgroups of the wave form a device of n_cu CUs gets at most
+// audspec.conf: lld_audspec_frame (wave per frame for Nfft 512 / 1024, workgroup per frame otherwise) writes the auditory-spectrum
+// rows P.out, n_bands wide (lld_audspec.hip). P.frame_utt and P.plp_eql are required; the regression stages are the caller's.
+hipError_t launch_audspec(const LldParams &P, hipStream_t s);
+int64_t audspec_wave_grid_cap(int n_cu, int64_t lds_bytes);  // workgroups of the wave form a device of n_cu CUs gets at most
+int audspec_wave_frames();                                   // frames in flight per workgroup of the wave form
 // cTonespec / cChroma per component (smilehip_tonespec_op_frames / smilehip_chroma_op_frames): strided rows
 hipError_t stage_tonespec(const float *fmap, const chroma::NoteRec *rec, int n_src, int n_notes, int use_power, const float *src, int64_t ld_src,
                           float *dst, int64_t ld_dst, int64_t n_frames, hipStream_t s);

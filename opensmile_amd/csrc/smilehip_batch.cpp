@@ -62,6 +62,15 @@ static int alloc_chroma_scratch(smilehip_plan *plan, smilehip_batch *b, const Ba
   return SMILEHIP_OK;
 }
 
+// audspec: the utterance of every frame, and -- with deltas to follow -- the compact static block (smilehip_mfcc_run's arrangement)
+static int alloc_audspec_scratch(const smilehip_plan *plan, smilehip_batch *b, const BatchLayout &L) {
+  int rc;
+  if (b->total_frames > 0 && (rc = b->d_frame_utt.upload(L.frame_utt))) return rc;
+  if (plan->cfg.n_delta > 0 && b->total_frames > 0 && b->d_static.alloc(size_t(b->total_frames) * size_t(plan_n_static(plan))))
+    return fail(SMILEHIP_ERR_HIP, "hipMalloc of the static-block scratch failed");
+  return SMILEHIP_OK;
+}
+
 // chroma_filt: the level tonespec; inputs that would carry the recursion's argument out of sincos_d's domain are refused here
 static int alloc_chroma_filt_scratch(smilehip_plan *plan, smilehip_batch *b) {
   int64_t longest = 0;
@@ -196,6 +205,7 @@ extern "C" int smilehip_batch_create(smilehip_plan *plan, const int64_t *h_off, 
     case SMILEHIP_CHAIN_PROSODY_ACF: rc = alloc_prosody_acf_scratch(b.get(), L); break;
     case SMILEHIP_CHAIN_CHROMA_FFT: rc = alloc_chroma_scratch(plan, b.get(), L); break;
     case SMILEHIP_CHAIN_CHROMA_FILT: rc = alloc_chroma_filt_scratch(plan, b.get()); break;
+    case SMILEHIP_CHAIN_AUDSPEC: rc = alloc_audspec_scratch(plan, b.get(), L); break;
     case SMILEHIP_CHAIN_COMPARE: rc = alloc_compare_scratch(plan, b.get(), L); break;
     case SMILEHIP_CHAIN_EGEMAPS: rc = alloc_egemaps_scratch(plan, b.get(), L); break;
     case SMILEHIP_CHAIN_MFCC:
@@ -546,6 +556,34 @@ static int chroma_filt_run(smilehip_plan *plan, smilehip_batch *b, const int16_t
   if ((trc = timing_mark(plan, 1, s))) return trc;
   e = stage_chroma(Q.n_notes, n_out, plan->cfg.chroma_sil_thresh, Q.tonespec, Q.n_notes, d_out, ld_out, b->total_frames, s);
   if (e != hipSuccess) return fail(SMILEHIP_ERR_HIP, "chroma_filt chroma kernel launch failed: %s", hipGetErrorString(e));
+  return timing_mark(plan, 2, s);
+}
+
+// SMILEHIP_CHAIN_AUDSPEC: lld_audspec_frame writes the band rows -- into the compact static scratch when deltas follow, into d_out
+// otherwise --, then the window chain writes static | de | de_de
+static int audspec_run(smilehip_plan *plan, smilehip_batch *b, const int16_t *d_pcm, float *d_out, int64_t ld_out, void *stream) {
+  const int n_static = plan_n_static(plan), n_out = plan_n_out(plan);
+  if (ld_out < n_out) return fail(SMILEHIP_ERR_INVALID, "ld_out %lld < n_out %d", (long long)ld_out, n_out);
+  if (b->total_frames == 0) return SMILEHIP_OK;
+  if (!d_pcm || !d_out) return fail(SMILEHIP_ERR_INVALID, "smilehip_lld_run: null device pointer");
+  hipStream_t s = (hipStream_t)stream;
+  LldParams P;
+  fill_params(plan, b, d_pcm, d_out, ld_out, P);
+  const bool compact = plan->cfg.n_delta > 0;              // (P.plp_eql: the chain's 64 HTK weights, P.melfloor: 1.0)
+  if (compact) {
+    if (!b->d_static.p) return fail(SMILEHIP_ERR_INVALID, "audspec chain: the batch has no static-block scratch");
+    P.out = b->d_static.p;
+    P.ld_out = n_static;
+  }
+  int trc;
+  if ((trc = timing_mark(plan, 0, s))) return trc;
+  hipError_t e = launch_audspec(P, s);
+  if (e != hipSuccess) return fail(SMILEHIP_ERR_HIP, "audspec kernel launch failed: %s", hipGetErrorString(e));
+  if ((trc = timing_mark(plan, 1, s))) return trc;
+  if (compact) {
+    const int rc = delta_chain_from(plan, b, b->d_static.p, n_static, 0, d_out, ld_out, n_static, plan->cfg.delta_win, plan->cfg.n_delta, stream);
+    if (rc) return rc;
+  }
   return timing_mark(plan, 2, s);
 }
 
@@ -1004,6 +1042,7 @@ extern "C" int smilehip_lld_run(smilehip_plan *plan, smilehip_batch *b, const in
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_ACF) return prosody_acf_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT) return chroma_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FILT) return chroma_filt_run(plan, b, d_pcm, d_out, ld_out, stream);
+  if (plan->cfg.chain_kind == SMILEHIP_CHAIN_AUDSPEC) return audspec_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE) return compare_full_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_EGEMAPS) return egemaps_run(plan, b, d_pcm, d_out, ld_out, stream);
   return is09_run(plan, b, d_pcm, d_out, ld_out, stream);

@@ -18,6 +18,7 @@
 #include "../../include/smilehip.h"
 #include "chroma_tables.hpp"
 #include "tonefilt_tables.hpp"
+#include "lld_audspec_ops.hpp"
 #include "lld_launch.hpp"
 #include "lld_ooura.hpp"
 #include "lld_params.hpp"
@@ -152,7 +153,7 @@ struct smilehip_plan {
   Fast512Host fast;
   bool use_fast = false;
   DevBuf<float> d_eql, d_eql_log;
-  DevBuf<float> d_plp_eql, d_plp_cos, d_plp_sin;     // PLP chain tables
+  DevBuf<float> d_plp_eql, d_plp_cos, d_plp_sin;     // PLP chain tables (d_plp_eql: the audspec chain's as well, 64 entries there)
   std::vector<float> h_plp_cos;
   DevBuf<double> d_sharp;
   // F0 group (SMILEHIP_CHAIN_COMPARE_F0); the whole-level chain (SMILEHIP_CHAIN_COMPARE) owns a second plan for it
@@ -225,7 +226,7 @@ struct smilehip_batch {
   int64_t total_rows = 0;
   DevBuf<int64_t> d_row_off;
   DevBuf<float> d_raw16;        // IS09: pre-smoothing LLD columns, total_frames x 16
-  DevBuf<float> d_static;       // MFCC chain with deltas: compact static block, total_frames x n_mfcc
+  DevBuf<float> d_static;       // MFCC / PLP / audspec chain with deltas: compact static block, total_frames x n_static
   DevBuf<float> d_rawA, d_rawB, d_mel1;   // ComParE A+B scratch
   DevBuf<float> d_b_extra;                // [n_utt x 110] row T60+1 of group B's sma / delta levels (functionals)
   DevBuf<float> d_shs, d_e60;             // F0 group: candidates (total_frames x 21) and frame energies

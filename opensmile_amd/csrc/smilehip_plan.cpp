@@ -231,6 +231,21 @@ extern "C" void smilehip_config_chroma_filt(smilehip_lld_config *c, double sampl
   c->chroma_sil_thresh = (float)0.001;
 }
 
+// config/audspec/audspec.conf: the MFCC12 front end, cPlp as auditory spectrum in cMfcc's place; every field lies in V1
+extern "C" void smilehip_config_audspec(smilehip_lld_config *c) {
+  smilehip_config_mfcc12_0_d_a(c);   // 25 ms / 10 ms, k = 0.97, ham, 26 HTK power mel bands 0 .. 8000 Hz, two delta stages of deltawin 2
+  c->chain_kind = SMILEHIP_CHAIN_AUDSPEC;
+  c->zero_pad_symmetric = 1;         // [audspec_fft:cTransformFFT] sets nothing: the component's default
+  c->plp_compression = 0.33f;        // [audspec_plp:cPlp] compression = 0.33
+  c->plp_lp_order = 5;               // (lpOrder = 5, firstCC = 0, cepLifter = 22: as the file has them; not read by this chain)
+  c->first_mfcc = 0;
+  c->last_mfcc = 5;
+}
+extern "C" void smilehip_config_audspec_compat(smilehip_lld_config *c) {
+  smilehip_config_audspec(c);
+  c->zero_pad_symmetric = 0;         // [fft:cTransformFFT] zeroPadSymmetric = 0: "for compatibility with 2.2.0 and older versions"
+}
+
 static inline bool is_compare_ab_like(const smilehip_lld_config &c) {
   return c.chain_kind == SMILEHIP_CHAIN_COMPARE_AB || c.chain_kind == SMILEHIP_CHAIN_COMPARE;
 }
@@ -253,12 +268,19 @@ static int build_tables(smilehip_plan *p, bool upload = true) {
   // the tables built: the prosodyAcf chain has no mel bank and no DCT (its frames may be shorter than a bank has bands)
   const bool no_mel = p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_ACF || p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT ||
                       p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FILT;   // (chroma_fft and chroma_filt likewise)
-  const uint32_t tmask = no_mel ? (mask & ~(SMILEHIP_STAGE_MEL | SMILEHIP_STAGE_MFCC)) : mask;
+  const bool is_aud = p->cfg.chain_kind == SMILEHIP_CHAIN_AUDSPEC;   // (a mel bank and no DCT: first_mfcc / last_mfcc are not read)
+  const uint32_t tmask = no_mel ? (mask & ~(SMILEHIP_STAGE_MEL | SMILEHIP_STAGE_MFCC)) : (is_aud ? (mask & ~SMILEHIP_STAGE_MFCC) : mask);
   p->h_window.assign(size_t(p->geo.N), 1.0f);
   if ((mask & SMILEHIP_STAGE_WINDOW) && (rc = make_window(p->cfg, p->geo.N, p->h_window)) != SMILEHIP_OK)
     return fail(rc, "unknown window function %d", p->cfg.win_func);
+  if (is_aud && (p->cfg.n_bands < 1 || p->cfg.n_bands > audspec::kMaxBands))
+    return fail(SMILEHIP_ERR_INVALID, "audspec chain: n_bands (cMelspec nBands) must be 1 .. %d (a lane per band, the window chain's widest level); got %d",
+                audspec::kMaxBands, p->cfg.n_bands);
   if (tmask & SMILEHIP_STAGE_MEL) {
-    if ((rc = make_mel(p->cfg, p->geo, p->mel)) != SMILEHIP_OK) return fail(rc, "invalid mel bank parameters");
+    if ((rc = make_mel(p->cfg, p->geo, p->mel)) != SMILEHIP_OK)
+      return is_aud ? fail(rc, "audspec chain: n_bands = %d, lofreq = %g, hifreq = %g build no mel bank on %lld bins", p->cfg.n_bands, (double)p->cfg.lofreq,
+                           (double)p->cfg.hifreq, (long long)p->geo.K)
+                    : fail(rc, "invalid mel bank parameters");
   } else {
     p->mel = MelBank();
     p->mel.n_bands = p->cfg.n_bands;
@@ -364,6 +386,22 @@ static int build_tables(smilehip_plan *p, bool upload = true) {
       return fail(SMILEHIP_ERR_INVALID, "chroma_filt chain: tonefilt_n_notes = %d notes are no multiple of chroma_octave_size %d (cChroma writes no values then)",
                   p->tonefilt.n_notes, c.chroma_octave_size);
     if (!(c.chroma_sil_thresh == c.chroma_sil_thresh)) return fail(SMILEHIP_ERR_INVALID, "chroma_filt chain: chroma_sil_thresh is not a number");
+  } else if (is_aud) {
+    // everything the chain cannot express is refused with the parameter named
+    const smilehip_lld_config &c = p->cfg;
+    if (mask != SMILEHIP_STAGE_ALL) return fail(SMILEHIP_ERR_INVALID, "audspec chain: stage_mask must be all stages");
+    if (!c.use_power) return fail(SMILEHIP_ERR_INVALID, "audspec chain: use_power must be 1 (cPlp reads a power mel spectrum)");
+    if (!c.mel_htk_compatible) return fail(SMILEHIP_ERR_INVALID, "audspec chain: mel_htk_compatible must be 1 (cPlp's htkcompatible floor is that of HTK-scaled bands)");
+    if (!(c.plp_compression >= 0.0f)) return fail(SMILEHIP_ERR_INVALID, "audspec chain: plp_compression (cPlp compression) must be >= 0; got %g", (double)c.plp_compression);
+    if (c.append_log_energy) return fail(SMILEHIP_ERR_INVALID, "audspec chain: append_log_energy must be 0 (cEnergy is not built for this chain)");
+    if (c.cms) return fail(SMILEHIP_ERR_INVALID, "audspec chain: cms must be 0 (cFullinputMean is not built for this chain)");
+    if (p->geo.Nfft < 64 || p->geo.Nfft > 8192)
+      return fail(SMILEHIP_ERR_INVALID, "audspec chain: the transform length must be 64 .. 8192 points; frame_size_sec at this sample_rate gives %lld",
+                  (long long)p->geo.Nfft);
+    for (int b = 0; b < p->mel.n_bands; ++b)               // what the band's lane walks lies in the spectrum
+      if (p->mel.rise_lo[b] < 0 || p->mel.rise_hi[b] > p->geo.K || p->mel.fall_lo[b] < 0 || p->mel.fall_hi[b] > p->geo.K)
+        return fail(SMILEHIP_ERR_INVALID, "audspec chain: n_bands / lofreq / hifreq: band %d reaches outside the %lld bins", b, (long long)p->geo.K);
+    p->dct.melfloor = 1.0f;                               // htkcompatible forces melfloor = 1.0 (plp.cpp:153-163)
   } else if (p->cfg.chain_kind != SMILEHIP_CHAIN_MFCC) {
     return fail(SMILEHIP_ERR_INVALID, "unknown chain_kind %d", p->cfg.chain_kind);
   }
@@ -401,6 +439,10 @@ static int build_tables(smilehip_plan *p, bool upload = true) {
       plp_eql[m - 1] = (float)(fs * fs * ((f2 + 1.44e6) / (f2 + 9.61e6)));   // smileDsp_equalLoudnessWeight_htk
     }
   }
+  if (is_aud) {                                           // the same weights (smileDsp_equalLoudnessWeight_htk), a lane per band: up to 64
+    plp_eql.assign(audspec::kMaxBands, 0.0f);
+    for (int m = 1; m <= p->mel.n_bands; ++m) plp_eql[m - 1] = audspec::eql_htk(p->mel.centres[m]);
+  }
   // fast Nfft=512 kernel if the geometry allows it (SMILEHIP_FORCE_GENERIC=1 disables it)
   p->use_fast = false;
   if (mask == SMILEHIP_STAGE_ALL && (p->cfg.chain_kind == SMILEHIP_CHAIN_MFCC || (is_plp && p->mel.n_bands == 26 && p->cfg.use_power)) &&
@@ -422,6 +464,7 @@ static int build_tables(smilehip_plan *p, bool upload = true) {
   if (p->geo.Nfft >= 64 && (rc = p->oo.build((int)p->geo.Nfft, true))) return rc;
   if (is_plp && ((rc = p->d_plp_eql.upload(plp_eql)) || (rc = p->d_plp_cos.upload(p->h_plp_cos)) || (rc = p->d_plp_sin.upload(plp_sin))))
     return rc;
+  if (is_aud && (rc = p->d_plp_eql.upload(plp_eql))) return rc;
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT && ((rc = p->d_ts_fmap.upload(p->tonespec.filter_map)) || (rc = p->d_ts_rec.upload(p->tonespec.rec))))
     return rc;
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FILT && (rc = p->d_tf_tab.upload(p->tonefilt.tab))) return rc;
@@ -703,6 +746,7 @@ int plan_n_static(const smilehip_plan *p) {
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE_F0) return 2;
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_SHS || p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_ACF) return 3;
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT || p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FILT) return p->cfg.chroma_octave_size;
+  if (p->cfg.chain_kind == SMILEHIP_CHAIN_AUDSPEC) return p->mel.n_bands;
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE) return 65;
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_EGEMAPS) return 25;
   return p->cfg.chain_kind == SMILEHIP_CHAIN_IS09 ? 16
@@ -746,7 +790,7 @@ extern "C" double smilehip_row_time(const smilehip_plan *plan, int64_t n_frames,
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_SHS)
     return smilehip_frame_time(plan, n_frames >= 2 ? (row < n_frames - 2 ? row : n_frames - 2) + 1 : 0);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_MFCC || plan->cfg.chain_kind == SMILEHIP_CHAIN_PLP || plan->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT ||
-      plan->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FILT ||
+      plan->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FILT || plan->cfg.chain_kind == SMILEHIP_CHAIN_AUDSPEC ||
       plan->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE_F0 || plan->cfg.chain_kind == SMILEHIP_CHAIN_EGEMAPS || n_frames <= 1)
     return smilehip_frame_time(plan, row);
   // IS09 and prosodyAcf (lld_prosody_acf_ops.hpp: row_time_frame): the smoother's end-of-input rows repeat the last frame's time

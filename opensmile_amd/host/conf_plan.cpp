@@ -1034,15 +1034,23 @@ bool conf_to_chroma_filt(const ConfFile &f, ConfPlan &p, std::string &err) {
   return true;
 }
 
-static bool conf_to_plan_inner(const ConfFile &f, ConfPlan &p, std::string &err);
-bool conf_to_plan(const ConfFile &f, ConfPlan &p, std::string &err) {
-  const bool ok = conf_to_plan_inner(f, p, err);
+static bool conf_to_plan_inner(const ConfFile &f, ConfPlan &p, std::string &err, bool audspec_set);
+static bool conf_to_plan_any(const ConfFile &f, ConfPlan &p, std::string &err, bool audspec_set) {
+  const bool ok = conf_to_plan_inner(f, p, err, audspec_set);
   if (ok && p.wave_file.empty())                         // (the big sets return before the cepstral walk that records it)
     for (const ConfInstance &i : f.inst)
       if (i.type == "cWaveSource") { const std::string *fn = i.find("filename"); if (fn) p.wave_file = *fn; }
   return ok;
 }
-static bool conf_to_plan_inner(const ConfFile &f, ConfPlan &p, std::string &err) {
+bool conf_to_plan(const ConfFile &f, ConfPlan &p, std::string &err) { return conf_to_plan_any(f, p, err, false); }
+// smilextract_hip --set audspec | audspec_compat -C file: the same walk with the auditory-spectrum cut of cPlp admitted (plain -C keeps
+// to the files it has always mapped and names this route); any other graph is refused here
+bool conf_to_audspec(const ConfFile &f, ConfPlan &p, std::string &err) {
+  if (!conf_to_plan_any(f, p, err, true)) return false;
+  if (!p.audspec) { err = "the file is not an auditory-spectrum chain (a cPlp with doIDFT = 0, doLP = 0, doLpToCeps = 0): use plain -C for it"; return false; }
+  return true;
+}
+static bool conf_to_plan_inner(const ConfFile &f, ConfPlan &p, std::string &err, bool audspec_set) {
   p = ConfPlan();
   const uint64_t fp = conf_fingerprint(f);
   for (const KnownSet &k : kKnownSets)
@@ -1252,22 +1260,50 @@ static bool conf_to_plan_inner(const ConfFile &f, ConfPlan &p, std::string &err)
     const int first_cc = (int)o.num("firstCC", 1);
     int last_cc = (int)o.num("lastCC", -1);
     const int n_ceps = (int)o.num("nCeps", -1);
-    if (last_cc < 0) last_cc = n_ceps < 0 ? c.plp_lp_order : n_ceps;
-    if (last_cc != c.plp_lp_order || first_cc < 0 || first_cc > 1) o.err = "[" + pl->name + ":cPlp] only firstCC = 0|1 with lastCC = lpOrder is expressible";
-    c.first_mfcc = first_cc;
-    c.last_mfcc = c.plp_lp_order;
+    // where the component stops (plp.cpp:132-139: doLpToCeps switches doLP on, doLP switches doIDFT on): all three off = the
+    // auditory spectrum itself (config/audspec), all three on = PLP-CC (config/plp); the cuts in between exist as operators only
+    const int do_idft = (int)o.num("doIDFT", 1), do_lp = (int)o.num("doLP", 1), do_ceps = (int)o.num("doLpToCeps", 1);
+    p.audspec = !do_idft && !do_lp && !do_ceps;
+    if (p.audspec && !audspec_set) {
+      err = "[" + pl->name + ":cPlp] doIDFT = 0, doLP = 0, doLpToCeps = 0 (the auditory spectrum) is not mapped by plain -C -- this file runs as --set audspec -C <file>";
+      return false;
+    }
+    if (!p.audspec) {
+      if (last_cc < 0) last_cc = n_ceps < 0 ? c.plp_lp_order : n_ceps;
+      if (last_cc != c.plp_lp_order || first_cc < 0 || first_cc > 1) o.err = "[" + pl->name + ":cPlp] only firstCC = 0|1 with lastCC = lpOrder is expressible";
+    }
+    c.first_mfcc = first_cc;                            // (the auditory-spectrum chain does not read lpOrder, firstCC, lastCC, nCeps, cepLifter:
+    c.last_mfcc = c.plp_lp_order;                       //  they have no effect on that output, measured on the binary)
     c.cep_lifter = (float)o.num("cepLifter", 0.0);
     c.plp_compression = (float)o.num("compression", 0.33);
-    o.require("htkcompatible", 1, 1);
-    // the PLP-CC branch the fused kernel implements is the one of config/plp: power mel spectrum in, no log / inverse log
+    if ((int)o.num("htkcompatible", 1) != 1)
+      o.err = "[" + pl->name + ":cPlp] htkcompatible = 0 is not expressible on the fused path (melfloor 1.0 and the HTK equal-loudness curve are built)";
+    // the branch the fused kernels implement is the one of config/plp and config/audspec: power mel spectrum in, no log / inverse log
     o.require("doLog", 0, 1); o.require("doAud", 1, 1); o.require("RASTA", 0, 0); o.require("newRASTA", 0, 0);
-    o.require("doInvLog", 0, 1); o.require("doIDFT", 1, 1); o.require("doLP", 1, 1); o.require("doLpToCeps", 1, 1);
+    o.require("doInvLog", 0, 1);
+    if (o.err.empty() && !p.audspec) {
+      if (do_lp && !do_ceps)
+        o.err = "[" + pl->name + ":cPlp] doLP = 1 with doLpToCeps = 0 (the LP coefficients) is not expressible on the fused path (the per-component operators have it)";
+      else if (do_idft && !do_lp && !do_ceps)
+        o.err = "[" + pl->name + ":cPlp] doIDFT = 1 with doLP = 0 (the autocorrelation) is not expressible on the fused path (the per-component operators have it)";
+      else { o.require("doIDFT", 1, 1); o.require("doLP", 1, 1); o.require("doLpToCeps", 1, 1); }
+    }
     o.require("processArrayFields", 1, 1);
     if (!o.finish(kBenign)) { err = o.err; return false; }
     std::vector<Col> cols;
-    for (int i = first_cc; i <= c.plp_lp_order; ++i) cols.push_back(Col{0, i, 0, false});
+    if (p.audspec) {                                    // one column per band: the static block of SMILEHIP_CHAIN_AUDSPEC
+      if (!c.use_power) { err = "[" + mel->name + ":cMelspec] usePower = 0 is not expressible in front of a cPlp (it reads a power mel spectrum)"; return false; }
+      if (en) { err = "[" + en->name + ":cEnergy] is not built for the auditory-spectrum chain"; return false; }
+      if (by_type.count("cFullinputMean")) { err = "[" + by_type["cFullinputMean"][0]->name + ":cFullinputMean] is not built for the auditory-spectrum chain"; return false; }
+      c.chain_kind = SMILEHIP_CHAIN_AUDSPEC;
+      p.plp = false;
+      for (int i = 0; i < c.n_bands; ++i) cols.push_back(Col{0, i, 0, false});
+      cep_name = "audSpec";
+    } else {
+      for (int i = first_cc; i <= c.plp_lp_order; ++i) cols.push_back(Col{0, i, 0, false});
+      cep_name = "PlpCC";
+    }
     levels[lvl(pl, "writer.dmLevel")] = cols;
-    cep_name = "PlpCC";
   }
   c.append_log_energy = 0;
   if (en) {                                             // src/lldcore/energy.cpp:33-44: HTK log energy of the raw frame
@@ -1334,13 +1370,13 @@ static bool conf_to_plan_inner(const ConfFile &f, ConfPlan &p, std::string &err)
     }
   }
   {
-    const int n_cep_ = p.plp ? c.plp_lp_order - c.first_mfcc + 1 : c.last_mfcc - c.first_mfcc + 1;
+    const int n_cep_ = p.audspec ? c.n_bands : (p.plp ? c.plp_lp_order - c.first_mfcc + 1 : c.last_mfcc - c.first_mfcc + 1);
     for (const auto &kv : levels) {
       std::vector<int> cols;
       bool plain = true;
       for (const Col &cc : kv.second) {
         if (cc.delta != 0 || cc.cms) { plain = false; break; }
-        cols.push_back(cc.kind == 1 ? n_cep_ : cc.index - c.first_mfcc);
+        cols.push_back(cc.kind == 1 ? n_cep_ : cc.index - (p.audspec ? 0 : c.first_mfcc));
       }
       if (plain && !cols.empty()) p.static_levels[kv.first] = cols;
     }
@@ -1378,7 +1414,7 @@ static bool conf_to_plan_inner(const ConfFile &f, ConfPlan &p, std::string &err)
       }
   }
   // must be [cepstra (, energy)] x (1 + n_delta) blocks, the cepstra of block 0 either all normalised or none
-  const int n_cep = p.plp ? c.plp_lp_order - c.first_mfcc + 1 : c.last_mfcc - c.first_mfcc + 1;
+  const int n_cep = p.audspec ? c.n_bands : (p.plp ? c.plp_lp_order - c.first_mfcc + 1 : c.last_mfcc - c.first_mfcc + 1);
   const int block = n_cep + (c.append_log_energy ? 1 : 0);
   if (block == 0 || outc.size() % (size_t)block != 0 || outc.size() / (size_t)block > 3) {
     err = "the sink's columns are not [static | delta | acceleration] blocks of the cepstral chain";
@@ -1391,7 +1427,7 @@ static bool conf_to_plan_inner(const ConfFile &f, ConfPlan &p, std::string &err)
     const int b = (int)(k / (size_t)block), j = (int)(k % (size_t)block);
     const Col &cc = outc[k];
     const bool want_energy = c.append_log_energy && j == n_cep;
-    const int first = c.first_mfcc;
+    const int first = p.audspec ? 0 : c.first_mfcc;
     const bool ok = cc.delta == b && (want_energy ? cc.kind == 1 : (cc.kind == 0 && cc.index == first + j)) &&
                     cc.cms == (b == 0 && !want_energy && c.cms);
     if (!ok) { err = "the sink's column order is not [cepstra, energy | their deltas | their accelerations]"; return false; }
@@ -1404,7 +1440,7 @@ static bool conf_to_plan_inner(const ConfFile &f, ConfPlan &p, std::string &err)
     for (int q = 0; q < b; ++q) suffix += std::string(sfx[1]) + delta_suffix;
     for (int j = 0; j < n_cep; ++j) {
       char idx[32];
-      snprintf(idx, sizeof(idx), "[%d]", p.plp ? j : c.first_mfcc + j);
+      snprintf(idx, sizeof(idx), "[%d]", (p.plp || p.audspec) ? j : c.first_mfcc + j);
       p.lld_names.push_back(cep_name + suffix + idx);
     }
     if (c.append_log_energy) p.lld_names.push_back("pcm_LOGenergy" + suffix);
@@ -1415,6 +1451,13 @@ static bool conf_to_plan_inner(const ConfFile &f, ConfPlan &p, std::string &err)
     if (pk) p.parm_kind = atoi(pk->c_str());
   }
   std::ostringstream d;
+  if (p.audspec) {
+    d << "auditory-spectrum chain: " << c.frame_size_sec * 1e3 << " ms / " << c.frame_step_sec * 1e3 << " ms frames, " << c.n_bands << " bands "
+      << c.lofreq << "-" << c.hifreq << " Hz, compression " << c.plp_compression << ", " << c.n_delta << " delta stage(s) of deltawin " << c.delta_win
+      << "; lpOrder, firstCC, lastCC, nCeps and cepLifter of [" << pl->name << ":cPlp] are accepted and ignored (no effect on the auditory spectrum)";
+    p.describe = d.str();
+    return true;
+  }
   d << (p.plp ? "PLP" : "MFCC") << " chain: " << c.frame_size_sec * 1e3 << " ms / " << c.frame_step_sec * 1e3 << " ms frames, " << c.n_bands
     << " bands " << c.lofreq << "-" << c.hifreq << " Hz, " << n_cep << " cepstra" << (c.append_log_energy ? " + log energy" : "")
     << (c.cms ? ", mean-normalised" : "") << ", " << c.n_delta << " delta stage(s)";

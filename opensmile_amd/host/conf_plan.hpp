@@ -50,8 +50,9 @@ uint64_t conf_fingerprint_masked2(const ConfFile &f);
 
 struct ConfPlan {
   std::string preset;                    // "is09_emotion", "compare16", "is13_compare", "egemapsv02", or "" = cfg below
-  smilehip_lld_config cfg;               // a cepstral chain (SMILEHIP_CHAIN_MFCC / _PLP) with the file's option values
+  smilehip_lld_config cfg;               // a cepstral chain (SMILEHIP_CHAIN_MFCC / _PLP / _AUDSPEC) with the file's option values
   bool plp = false;
+  bool audspec = false;                  // a cPlp with doIDFT = doLP = doLpToCeps = 0: the auditory spectrum (config/audspec), one column per band
   int parm_kind = 9;                     // of the file's own cHtkSink
   std::vector<std::string> lld_names;    // element names of the output level
   std::string describe;
@@ -76,6 +77,10 @@ void conf_apply_f0_params(const ConfPlan &p, smilehip_lld_config &cfg);
 
 // false + err: the graph (component, option) the fused path cannot express
 bool conf_to_plan(const ConfFile &f, ConfPlan &p, std::string &err);
+// smilextract_hip --set audspec | audspec_compat -C file: the cepstral-chain walk of conf_to_plan with a cPlp cut behind its auditory stage
+// (doIDFT = doLP = doLpToCeps = 0) admitted: preset = "", cfg = SMILEHIP_CHAIN_AUDSPEC with the file's own values, audspec = true.
+// conf_to_plan itself refuses such a file and names this route.
+bool conf_to_audspec(const ConfFile &f, ConfPlan &p, std::string &err);
 // smilextract_hip --set prosody_shs -C file: the file must be the graph of config/prosody/prosodyShs.conf; preset = "prosody_shs", and
 // unless it is the shipped file itself f0_params holds its values of the options the chain takes as parameters (cPitchShs minPitch,
 // maxPitch, voicingCutoff, nHarmonics, compressionFactor, nCandidates; cSpecScale minF; cContourSmoother smaWin: pitch_min, pitch_max,

@@ -44,6 +44,18 @@ std::vector<std::string> lld_names_chroma_fft(int octave_size) {
   for (int i = 0; i < octave_size; ++i) n.push_back("chroma[" + std::to_string(i) + "]");
   return n;
 }
+// config/audspec/audspec.conf and audspec_compat.conf, level lld: cPlp with doIDFT = doLP = doLpToCeps = 0 names its one array field
+// audSpec (plp.cpp:259-271), each cDeltaRegression appends _de (nameAppend's default); the binary's CSV header prints
+// audSpec[0]; .. ;audSpec[25];audSpec_de[0]; .. ;audSpec_de_de[25]
+std::vector<std::string> lld_names_audspec(int n_bands, int n_delta, const std::string &delta_suffix) {
+  std::vector<std::string> n;
+  std::string suffix;
+  for (int b = 0; b <= n_delta; ++b) {
+    for (int i = 0; i < n_bands; ++i) n.push_back("audSpec" + suffix + "[" + std::to_string(i) + "]");
+    suffix += "_" + delta_suffix;
+  }
+  return n;
+}
 std::vector<std::string> lld_names_prosody_shs() { return {"F0final_sma", "voicingFinalUnclipped_sma", "pcm_loudness_sma"}; }
 
 std::vector<std::string> lld_names_is09() {

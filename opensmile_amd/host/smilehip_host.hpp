@@ -43,6 +43,7 @@ std::vector<std::string> lld_names_htk_variant(bool plp, bool energy);   // MFCC
 std::vector<std::string> lld_names_is09();
 std::vector<std::string> lld_names_prosody_shs();   // prosodyShs.conf: F0final_sma, voicingFinalUnclipped_sma, pcm_loudness_sma
 std::vector<std::string> lld_names_prosody_acf();   // prosodyAcf.conf: voiceProb_sma, F0_sma, pcm_loudness_sma
+std::vector<std::string> lld_names_audspec(int n_bands = 26, int n_delta = 2, const std::string &delta_suffix = "de");   // audspec.conf: audSpec[i], audSpec_de[i], audSpec_de_de[i]
 std::vector<std::string> lld_names_chroma_fft(int octave_size = 12);   // chroma_fft.conf and chroma_filt.conf: chroma[0] .. chroma[octaveSize - 1]
 std::vector<std::string> lld_names_compare16();
 std::vector<std::string> func_names_is09();     // 384: <lld>_<functional>

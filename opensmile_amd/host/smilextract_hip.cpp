@@ -32,6 +32,10 @@
 //   smilextract_hip --set chroma_filt   config/chroma/chroma_filt.conf: 12 chroma values per block of 10 ms from cTonefilt's sine filter bank;
 //                   [-C chroma_filt.conf] -O and -csvoutput as for chroma_fft. With -C: that file's (edited) nNotes, firstNote, decayF0,
 //                                       decayFN, outputPeriod, octaveSize and silThresh; anything else is refused by name
+//   smilextract_hip --set audspec | audspec_compat   config/audspec/audspec.conf / audspec_compat.conf (zeroPadSymmetric = 0): the 26-band
+//                                       auditory spectrum with delta and acceleration, 78 columns (-O out.htk with parmKind 9, -csvoutput
+//                                       out.csv)
+//                   [-C audspec.conf]   with that file's (edited) values through the cepstral-chain walker (plain -C names this route)
 //   smilextract_hip --set gemapsv01a | egemapsv01a   the v01a files: the same columns, zeroPadSymmetric = 0, useBrokenJitterThresh = 1, maxF = 5500
 //   smilextract_hip --set gemapsv01b | egemapsv01b   config/gemaps/v01b/GeMAPSv01b.conf (18 LLDs, 62 functionals) / config/egemaps/v01b/
 //                                       eGeMAPSv01b.conf (23, 88): sub-graphs of eGeMAPSv02.conf, written as column subsets of its levels
@@ -169,9 +173,10 @@ static int run_main(int argc, char **argv, Persist *ps) {
     const bool set_acf = opt.count("--set") && opt["--set"] == "prosody_acf";
     const bool set_chroma = opt.count("--set") && opt["--set"] == "chroma_fft";
     const bool set_filt = opt.count("--set") && opt["--set"] == "chroma_filt";
-    const bool set_with_conf = opt.count("--set") && (opt["--set"] == "prosody_shs" || set_acf || set_chroma || set_filt);
+    const bool set_aud = opt.count("--set") && (opt["--set"] == "audspec" || opt["--set"] == "audspec_compat");
+    const bool set_with_conf = opt.count("--set") && (opt["--set"] == "prosody_shs" || set_acf || set_chroma || set_filt || set_aud);
     if (opt.count("--set") && !set_with_conf)
-      die("-C and --set exclude each other (except --set prosody_shs -C prosodyShs.conf, --set prosody_acf -C prosodyAcf.conf, --set chroma_fft -C chroma_fft.conf and --set chroma_filt -C chroma_filt.conf)");
+      die("-C and --set exclude each other (except --set prosody_shs -C prosodyShs.conf, --set prosody_acf -C prosodyAcf.conf, --set chroma_fft -C chroma_fft.conf, --set chroma_filt -C chroma_filt.conf and --set audspec -C audspec.conf)");
     ConfFile cf;
     std::string cerr_;
     if (!conf_parse(opt["-C"], conf_cmdline, cf, cerr_)) die("-C " + opt["-C"] + ": " + cerr_);
@@ -213,7 +218,8 @@ static int run_main(int argc, char **argv, Persist *ps) {
           opt[o.second] = dflt->second;
       }
     }
-    if (!(set_filt   ? conf_to_chroma_filt(cf, conf_plan, cerr_)
+    if (!(set_aud    ? conf_to_audspec(cf, conf_plan, cerr_)
+          : set_filt ? conf_to_chroma_filt(cf, conf_plan, cerr_)
           : set_chroma ? conf_to_chroma_fft(cf, conf_plan, cerr_)
           : set_acf  ? conf_to_prosody_acf(cf, conf_plan, cerr_)
                      : (set_with_conf ? conf_to_prosody_shs(cf, conf_plan, cerr_) : conf_to_plan(cf, conf_plan, cerr_)))) {
@@ -230,6 +236,7 @@ static int run_main(int argc, char **argv, Persist *ps) {
     }
     fprintf(stderr, "smilextract_hip: %s -> %s\n", opt["-C"].c_str(), conf_plan.describe.c_str());
     if (!conf_plan.preset.empty()) opt["--set"] = conf_plan.preset;
+    else if (set_aud) opt.erase("--set");                  // (the file's own values, zeroPadSymmetric among them: the free chain below)
     if (describe_only) {                                   // what the file maps to, without touching a device
       const smilehip_lld_config &c = conf_plan.cfg;
       printf("preset=%s\n", conf_plan.preset.c_str());
@@ -314,10 +321,13 @@ static int run_main(int argc, char **argv, Persist *ps) {
     if (with_conf) conf_apply_f0_params(conf_plan, vcfg);   // (the names follow the file's octaveSize)
   } else if (prosody_acf) smilehip_config_prosody_acf(&vcfg);
   else if (prosody) smilehip_config_prosody_shs(&vcfg);
-  const bool htk_variant = free_chain || prosody || (!is09 && !cmp16 && !egm && smilehip_config_htk_variant(&vcfg, variant.c_str()) == SMILEHIP_OK);
+  // config/audspec/audspec.conf and audspec_compat.conf: LLD-only sets through standard_data_output_lldonly, like the cepstral files
+  const bool audspec = set == "audspec" || set == "audspec_compat";
+  if (audspec) { if (set == "audspec") smilehip_config_audspec(&vcfg); else smilehip_config_audspec_compat(&vcfg); }
+  const bool htk_variant = free_chain || prosody || audspec || (!is09 && !cmp16 && !egm && smilehip_config_htk_variant(&vcfg, variant.c_str()) == SMILEHIP_OK);
   const bool plp = htk_variant && vcfg.chain_kind == SMILEHIP_CHAIN_PLP;
   if (!is09 && !cmp16 && !egm && !htk_variant)
-    die("--set must be mfcc12_{0,e}_d_a[_z], plp_{0,e}_d_a[_z], is09_emotion, compare16, compare16_lld, is13_compare, egemapsv02, gemapsv01b, egemapsv01b, gemapsv01a, egemapsv01a, prosody_shs, prosody_acf, chroma_fft or chroma_filt (or use -C file.conf)");
+    die("--set must be mfcc12_{0,e}_d_a[_z], plp_{0,e}_d_a[_z], is09_emotion, compare16, compare16_lld, is13_compare, egemapsv02, gemapsv01b, egemapsv01b, gemapsv01a, egemapsv01a, prosody_shs, prosody_acf, chroma_fft, chroma_filt, audspec or audspec_compat (or use -C file.conf)");
   // parmKind of the files' own cHtkSink sections (the _Z files); the others write through standard_data_output_lldonly (9)
   int parm_kind = 9;
   if (variant == "MFCC12_0_D_A_Z") parm_kind = 11014;
@@ -493,6 +503,7 @@ static int run_main(int argc, char **argv, Persist *ps) {
                  : chroma ? lld_names_chroma_fft(vcfg.chroma_octave_size)
                  : prosody_acf ? lld_names_prosody_acf()
                  : prosody ? lld_names_prosody_shs()
+                 : audspec ? lld_names_audspec(vcfg.n_bands, vcfg.n_delta)
                  : (is09 ? lld_names_is09() : (cmp16 ? (cmp_subset ? select_names(lld_names_compare16(), sel_lld) : lld_names_compare16())
                     : (egm ? (egm_subset ? select_names(lld_names_egemaps(), sel_lld) : lld_names_egemaps())
                            : lld_names_htk_variant(plp, htk_variant && vcfg.append_log_energy))));
