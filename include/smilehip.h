@@ -295,6 +295,17 @@ typedef struct smilehip_lld_config {
  * One frame kernel (lld_audspec_frame: a wave per frame for transforms of 512 / 1024 points, a workgroup per frame otherwise), then
  * the window chain. The static level is the output's first block: there is no tap. */
 #define SMILEHIP_CHAIN_AUDSPEC 11
+/* SMILEHIP_CHAIN_SPECTROGRAM: the level `lld` of config/spectrum/spectrogram.conf, K = Nfft / 2 + 1 columns, 257 at 16 kHz:
+ *   pcm_fftMag[0..K-1]   (or pcm_fftMag_SpecDens, _PowSpec, _PowSpecDens, _dBsplPSD: smilehip_plan_set_spectrum_form)
+ * on frames of frame_size_sec every frame_step_sec (25 / 10 ms as shipped; the file's -frameSize / -frameStep): cWindower
+ * (windower.cpp:204-218; no pre-emphasis), cTransformFFT zero-padded to a power of two (transformFft.cpp:143-195), cFFTmagphase in
+ * one of its five forms (fftmagphase.cpp:215-255). The output row is wider than the input frame.
+ * Rows per utterance, as measured against the binary at 0, N - 1, N, N + H - 1 and N + H samples: T = (n - N) / H + 1 for n >= N
+ * samples, none below (spectrogram::rows_of, lld_spectrogram_ops.hpp); row t carries the time of its first sample, t * H / sample_rate
+ * (smilehip_row_time): t * frame_step_sec wherever that step is a whole number of samples, 0.009977 t at 11.025 kHz.
+ * One frame kernel (lld_spectrogram_frame: a wave per frame for transforms of 512 / 1024 points, a workgroup per frame otherwise)
+ * writes the rows straight into the caller's matrix: no scratch, no tap, no window chain. The transform length must be 64 .. 8192. */
+#define SMILEHIP_CHAIN_SPECTROGRAM 12
 
 #define SMILEHIP_STAGE_WINDOW 1u
 #define SMILEHIP_STAGE_FFT    2u
@@ -395,6 +406,20 @@ void smilehip_config_chroma_filt(smilehip_lld_config *c, double sample_rate);
 void smilehip_config_audspec(smilehip_lld_config *c);
 /* ... with config/audspec/audspec_compat.conf: the same graph with [fft:cTransformFFT] zeroPadSymmetric = 0 */
 void smilehip_config_audspec_compat(smilehip_lld_config *c);
+/* fills c -- SMILEHIP_LLD_CONFIG_SIZE_V1 bytes, struct_size = that -- with config/spectrum/spectrogram.conf (chain_kind =
+ * SPECTROGRAM); the caller sets sample_rate (and frame_size_sec / frame_step_sec, the file's -frameSize / -frameStep) afterwards:
+ *   [frame:cFramer] 0.025 / 0.010 s, frameMode = fixed, frameCenterSpecial = left; no pre-emphasis; [win:cWindower] ham, gain 1,
+ *   offset 0; [fft:cTransformFFT] sets nothing: zeroPadSymmetric at its default 1; [fftmag:cFFTmagphase] plain magnitude. */
+void smilehip_config_spectrogram(smilehip_lld_config *c);
+/* cFFTmagphase's output form of a SMILEHIP_CHAIN_SPECTROGRAM plan (the config struct has no field for it): flags are the
+ * SMILEHIP_MAGPHASE_* bits below -- MAGNITUDE alone (a fresh plan), or MAGNITUDE with NORMALISE, POWER, NORMALISE | POWER, or DBPSD
+ * (which implies NORMALISE and wins over POWER, as in the component). dbp_norm / min_dbp are the component's dBpnorm / mindBp
+ * (90.302 / -102.0), read by the DBPSD form alone; min_dbp is raised to dbp_norm - 120 where it lies below that
+ * (fftmagphase.cpp:95-97). PHASE, a set without MAGNITUDE and any plan of another chain are refused (SMILEHIP_ERR_INVALID).
+ * Works on host-only plans; runs read the plan's form when they launch. */
+int smilehip_plan_set_spectrum_form(smilehip_plan *plan, int32_t flags, float dbp_norm, float min_dbp);
+/* what the plan holds: flags (MAGNITUDE | the form's bits), dbp_norm, min_dbp behind the clamp; any pointer may be NULL */
+int smilehip_plan_get_spectrum_form(const smilehip_plan *plan, int32_t *flags, float *dbp_norm, float *min_dbp);
 
 /* F0 group, per component, on an F0 chain plan (smilehip_config_compare16_f0; the plan's spectrum geometry -- n_bins and
  * the level's frameSizeSec, force_fft_frame_size_sec -- must be the input level's):

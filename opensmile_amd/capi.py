@@ -235,6 +235,9 @@ SYMBOLS = {
     "smilehip_batch_chroma_taps": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
     "smilehip_config_audspec": (None, [C.POINTER(LldConfig)]),
     "smilehip_config_audspec_compat": (None, [C.POINTER(LldConfig)]),
+    "smilehip_config_spectrogram": (None, [C.POINTER(LldConfig)]),
+    "smilehip_plan_set_spectrum_form": (C.c_int, [_vp, C.c_int32, C.c_float, C.c_float]),
+    "smilehip_plan_get_spectrum_form": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "smilehip_tonespec_op_create": (C.c_int, [_vp, _vp, _i64, _dbl, _vp]),
     "smilehip_tonespec_op_n_out": (C.c_int, [_vp]),
     "smilehip_tonespec_op_frames": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _vp]),
@@ -665,6 +668,21 @@ def audspec_config(sample_rate=16000.0, compat=False):
     return c
 
 
+CHAIN_SPECTROGRAM = 12
+MAGPHASE_MAGNITUDE, MAGPHASE_PHASE, MAGPHASE_NORMALISE, MAGPHASE_POWER, MAGPHASE_DBPSD = 1, 2, 4, 8, 16   # SMILEHIP_MAGPHASE_*
+
+
+def spectrogram_config(sample_rate=16000.0, frame_size=0.025, frame_step=0.010):
+    """config/spectrum/spectrogram.conf (chain_kind = SPECTROGRAM): pcm_fftMag[0..K-1], K = Nfft / 2 + 1; frame_size / frame_step are the
+    file's -frameSize / -frameStep. The preset fills LLD_CONFIG_SIZE_V1 bytes; the form is the plan's (Plan.set_spectrum_form)."""
+    c = LldConfig()
+    load().smilehip_config_spectrogram(C.byref(c))
+    c.sample_rate = float(sample_rate)
+    c.frame_size_sec = float(frame_size)
+    c.frame_step_sec = float(frame_step)
+    return c
+
+
 def tonefilt_tables(opts, sample_rate):
     """smilehip_tonefilt_op_tables: dict of P (samples per block), freq, decay"""
     L = load()
@@ -994,6 +1012,17 @@ class Plan:
     def lifter(self):
         return self._table(load().smilehip_plan_get_lifter, np.float32)
 
+    def set_spectrum_form(self, flags, dbp_norm=90.302, min_dbp=-102.0):
+        """spectrogram chain plans: cFFTmagphase's form as MAGPHASE_* bits (MAGNITUDE alone, or with NORMALISE, POWER, both, or DBPSD)
+        and the dB form's dBpnorm / mindBp; later runs read it."""
+        _check(load().smilehip_plan_set_spectrum_form(self._h, int(flags), float(dbp_norm), float(min_dbp)))
+
+    def spectrum_form(self):
+        """(flags, dbp_norm, min_dbp behind the component's clamp) of a spectrogram chain plan"""
+        f, a, b = C.c_int32(), C.c_float(), C.c_float()
+        _check(load().smilehip_plan_get_spectrum_form(self._h, C.byref(f), C.byref(a), C.byref(b)))
+        return f.value, a.value, b.value
+
     def set_timing(self, on=True):
         _check(load().smilehip_plan_set_timing(self._h, 1 if on else 0))
 
@@ -1163,6 +1192,35 @@ class Batch:
         L = load()
         ctx = self.plan.ctx._h
         assert self.plan.cfg.chain_kind == CHAIN_AUDSPEC, "not an audspec chain plan"
+        ld_out = self.plan.geometry.n_out if ld_out is None else ld_out
+        f32 = np.asarray(pcm).dtype == np.float32
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32 if f32 else np.int16)
+        out = np.full((self.total_rows, ld_out), fill, np.float32)
+        d_pcm, d_out = _vp(), _vp()
+        _check(L.smilehip_alloc(ctx, max(pcm.nbytes, 4), C.byref(d_pcm)))
+        _check(L.smilehip_alloc(ctx, max(out.nbytes, 4), C.byref(d_out)))
+        try:
+            if pcm.nbytes:
+                _check(L.smilehip_copy_to_device(ctx, d_pcm, pcm.ctypes.data, pcm.nbytes, None))
+            if out.nbytes:
+                _check(L.smilehip_copy_to_device(ctx, d_out, out.ctypes.data, out.nbytes, None))
+            for _ in range(runs):
+                _check((L.smilehip_lld_run_f32 if f32 else L.smilehip_lld_run)(self.plan._h, self._h, d_pcm, d_out, ld_out, None))
+            _check(L.smilehip_stream_synchronize(ctx, None))
+            if out.nbytes:
+                _check(L.smilehip_copy_to_host(ctx, out.ctypes.data, d_out, out.nbytes, None))
+        finally:
+            L.smilehip_free(ctx, d_pcm)
+            L.smilehip_free(ctx, d_out)
+        return out
+
+    def spectrogram_run_host(self, pcm, ld_out=None, fill=0.0, runs=1):
+        """spectrogram chain plans (run_host serves them as well): run on host data (int16 samples through smilehip_lld_run, a float32
+        array through smilehip_lld_run_f32) into a matrix [total_rows x ld_out] that held `fill` everywhere before, `runs` times
+        over, in the plan's form as it is now. The rows are K = n_out wide."""
+        L = load()
+        ctx = self.plan.ctx._h
+        assert self.plan.cfg.chain_kind == CHAIN_SPECTROGRAM, "not a spectrogram chain plan"
         ld_out = self.plan.geometry.n_out if ld_out is None else ld_out
         f32 = np.asarray(pcm).dtype == np.float32
         pcm = np.ascontiguousarray(pcm, dtype=np.float32 if f32 else np.int16)

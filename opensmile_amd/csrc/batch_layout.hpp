@@ -41,7 +41,7 @@ struct BatchLayout {
   int32_t run_frames = 8;
   std::vector<FTileRec> ftiles;                        // MFCC / PLP: non-empty when the batch runs the delta-fused fast kernel
   std::vector<int32_t> jit_utt, jit_t0;                // F0 group
-  std::vector<int32_t> frame_utt;                      // IS09, prosodyAcf, chroma_fft, audspec: the utterance of every frame
+  std::vector<int32_t> frame_utt;                      // IS09, prosodyAcf, chroma_fft, audspec, spectrogram: the utterance of every frame
 };
 
 constexpr int kRunFramesMin = 8;   // frames per 20 ms run when the caller names none (lld_compare.hip / lld_gemaps.hip)
@@ -69,7 +69,7 @@ inline int64_t layout_rows(const BatchLayoutSpec &s, int64_t len, int64_t T) {
   // prosodyShs: cPitchSmoother's level holds T - 1 frames (no output for its first call), the smoother adds its end-of-input rows
   if (s.chain_kind == SMILEHIP_CHAIN_PROSODY_SHS) return T >= 2 ? T - 1 + s.row_extra : 0;
   // (IS09 and prosodyAcf: T + smaWin / 2 rows, prosody_acf::rows_of; chroma_fft and chroma_filt: T rows, chroma::rows_of / tonefilt::rows_of;
-  //  audspec: T rows, audspec::rows_of)
+  //  audspec: T rows, audspec::rows_of; spectrogram: T rows, spectrogram::rows_of)
   if (!compare && s.chain_kind != SMILEHIP_CHAIN_EGEMAPS) return T > 0 ? T + s.row_extra : 0;
   const int64_t T60 = layout_num_frames(len, samples_60ms(s.period), s.H);
   return T60 >= (compare ? 4 : 1) ? T60 + 1 : 0;
@@ -166,7 +166,7 @@ inline int batch_layout(const BatchLayoutSpec &s, const int64_t *h_off, int32_t 
   out.total_frames = out.frame_off[n_utt];
   out.total_rows = out.row_off[n_utt];
   if ((s.chain_kind == SMILEHIP_CHAIN_IS09 || s.chain_kind == SMILEHIP_CHAIN_PROSODY_ACF || s.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT ||
-       s.chain_kind == SMILEHIP_CHAIN_AUDSPEC) &&
+       s.chain_kind == SMILEHIP_CHAIN_AUDSPEC || s.chain_kind == SMILEHIP_CHAIN_SPECTROGRAM) &&
       out.total_frames > 0) {
     out.frame_utt.resize((size_t)out.total_frames);
     for (int32_t u = 0; u < n_utt; ++u) std::fill(out.frame_utt.begin() + out.frame_off[u], out.frame_utt.begin() + out.frame_off[u + 1], u);

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "lld_params.hpp"
+#include "lld_spectrogram_ops.hpp"
 #include "tables.hpp"
 
 namespace smilehip {
@@ -81,6 +82,9 @@ int64_t chroma_wave_grid_cap(int n_cu, int64_t lds_bytes);   // workgroups of th
 hipError_t launch_audspec(const LldParams &P, hipStream_t s);
 int64_t audspec_wave_grid_cap(int n_cu, int64_t lds_bytes);  // workgroups of the wave form a device of n_cu CUs gets at most
 int audspec_wave_frames();                                   // frames in flight per workgroup of the wave form
+// spectrogram.conf: lld_spectrogram_frame (wave per frame for Nfft 512 / 1024, workgroup per frame otherwise) writes the spectrum rows
+// P.out, K wide, in the form F (lld_spectrogram.hip). P.frame_utt is required; the wave form's grid is audspec_wave_grid_cap's.
+hipError_t launch_spectrogram(const LldParams &P, const spectrogram::FormConsts &F, hipStream_t s);
 // cTonespec / cChroma per component (smilehip_tonespec_op_frames / smilehip_chroma_op_frames): strided rows
 hipError_t stage_tonespec(const float *fmap, const chroma::NoteRec *rec, int n_src, int n_notes, int use_power, const float *src, int64_t ld_src,
                           float *dst, int64_t ld_dst, int64_t n_frames, hipStream_t s);

@@ -71,6 +71,11 @@ static int alloc_audspec_scratch(const smilehip_plan *plan, smilehip_batch *b, c
   return SMILEHIP_OK;
 }
 
+// spectrogram: the utterance of every frame; the rows go straight to the caller's matrix
+static int alloc_spectrogram_scratch(smilehip_batch *b, const BatchLayout &L) {
+  return b->total_frames > 0 ? b->d_frame_utt.upload(L.frame_utt) : SMILEHIP_OK;
+}
+
 // chroma_filt: the level tonespec; inputs that would carry the recursion's argument out of sincos_d's domain are refused here
 static int alloc_chroma_filt_scratch(smilehip_plan *plan, smilehip_batch *b) {
   int64_t longest = 0;
@@ -206,6 +211,7 @@ extern "C" int smilehip_batch_create(smilehip_plan *plan, const int64_t *h_off, 
     case SMILEHIP_CHAIN_CHROMA_FFT: rc = alloc_chroma_scratch(plan, b.get(), L); break;
     case SMILEHIP_CHAIN_CHROMA_FILT: rc = alloc_chroma_filt_scratch(plan, b.get()); break;
     case SMILEHIP_CHAIN_AUDSPEC: rc = alloc_audspec_scratch(plan, b.get(), L); break;
+    case SMILEHIP_CHAIN_SPECTROGRAM: rc = alloc_spectrogram_scratch(b.get(), L); break;
     case SMILEHIP_CHAIN_COMPARE: rc = alloc_compare_scratch(plan, b.get(), L); break;
     case SMILEHIP_CHAIN_EGEMAPS: rc = alloc_egemaps_scratch(plan, b.get(), L); break;
     case SMILEHIP_CHAIN_MFCC:
@@ -584,6 +590,23 @@ static int audspec_run(smilehip_plan *plan, smilehip_batch *b, const int16_t *d_
     const int rc = delta_chain_from(plan, b, b->d_static.p, n_static, 0, d_out, ld_out, n_static, plan->cfg.delta_win, plan->cfg.n_delta, stream);
     if (rc) return rc;
   }
+  return timing_mark(plan, 2, s);
+}
+
+// SMILEHIP_CHAIN_SPECTROGRAM: one launch of lld_spectrogram_frame writes the K-wide rows into d_out in the plan's form as it is now
+static int spectrogram_run(smilehip_plan *plan, smilehip_batch *b, const int16_t *d_pcm, float *d_out, int64_t ld_out, void *stream) {
+  const int n_out = plan_n_out(plan);
+  if (ld_out < n_out) return fail(SMILEHIP_ERR_INVALID, "ld_out %lld < n_out %d", (long long)ld_out, n_out);
+  if (b->total_frames == 0) return SMILEHIP_OK;
+  if (!d_pcm || !d_out) return fail(SMILEHIP_ERR_INVALID, "smilehip_lld_run: null device pointer");
+  hipStream_t s = (hipStream_t)stream;
+  LldParams P;
+  fill_params(plan, b, d_pcm, d_out, ld_out, P);
+  int trc;
+  if ((trc = timing_mark(plan, 0, s))) return trc;
+  hipError_t e = launch_spectrogram(P, plan->spg_form, s);
+  if (e != hipSuccess) return fail(SMILEHIP_ERR_HIP, "spectrogram kernel launch failed: %s", hipGetErrorString(e));
+  if ((trc = timing_mark(plan, 1, s))) return trc;
   return timing_mark(plan, 2, s);
 }
 
@@ -1043,6 +1066,7 @@ extern "C" int smilehip_lld_run(smilehip_plan *plan, smilehip_batch *b, const in
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT) return chroma_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FILT) return chroma_filt_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_AUDSPEC) return audspec_run(plan, b, d_pcm, d_out, ld_out, stream);
+  if (plan->cfg.chain_kind == SMILEHIP_CHAIN_SPECTROGRAM) return spectrogram_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE) return compare_full_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_EGEMAPS) return egemaps_run(plan, b, d_pcm, d_out, ld_out, stream);
   return is09_run(plan, b, d_pcm, d_out, ld_out, stream);

@@ -19,6 +19,7 @@
 #include "chroma_tables.hpp"
 #include "tonefilt_tables.hpp"
 #include "lld_audspec_ops.hpp"
+#include "lld_spectrogram_ops.hpp"
 #include "lld_launch.hpp"
 #include "lld_ooura.hpp"
 #include "lld_params.hpp"
@@ -175,6 +176,8 @@ struct smilehip_plan {
   // chroma_filt chain: cTonefilt's per-note table (tonefilt_tables.hpp)
   TonefiltHost tonefilt;
   DevBuf<tonefilt::NoteTab> d_tf_tab;
+  // spectrogram chain: cFFTmagphase's form and its constants (smilehip_plan_set_spectrum_form; plain magnitude on a fresh plan)
+  spectrogram::FormConsts spg_form{};
   // eGeMAPS chain: cSpecResample's tables (transposed), cSpectral's band-slope edges and frequency range
   DevBuf<float> d_rs_cos, d_rs_sin;
   DevBuf<uint64_t> d_fm_flags;              // smilehip_formantlpc_rows: GemapsParams::fm_flags of the largest call so far

@@ -246,6 +246,15 @@ extern "C" void smilehip_config_audspec_compat(smilehip_lld_config *c) {
   c->zero_pad_symmetric = 0;         // [fft:cTransformFFT] zeroPadSymmetric = 0: "for compatibility with 2.2.0 and older versions"
 }
 
+// config/spectrum/spectrogram.conf: framer, Hamming window, transform, cFFTmagphase; every field lies in V1
+extern "C" void smilehip_config_spectrogram(smilehip_lld_config *c) {
+  smilehip_config_mfcc12_0_d_a(c);   // 25 ms / 10 ms, ham, gain 1, offset 0 (the mel / DCT fields are not read by this chain)
+  c->chain_kind = SMILEHIP_CHAIN_SPECTROGRAM;
+  c->preemph = 0;                    // the file has no cVectorPreemphasis
+  c->zero_pad_symmetric = 1;         // [fft:cTransformFFT] sets nothing: the component's default
+  c->n_delta = 0;
+}
+
 static inline bool is_compare_ab_like(const smilehip_lld_config &c) {
   return c.chain_kind == SMILEHIP_CHAIN_COMPARE_AB || c.chain_kind == SMILEHIP_CHAIN_COMPARE;
 }
@@ -267,7 +276,8 @@ static int build_tables(smilehip_plan *p, bool upload = true) {
   const uint32_t mask = p->cfg.stage_mask ? p->cfg.stage_mask : SMILEHIP_STAGE_ALL;
   // the tables built: the prosodyAcf chain has no mel bank and no DCT (its frames may be shorter than a bank has bands)
   const bool no_mel = p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_ACF || p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT ||
-                      p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FILT;   // (chroma_fft and chroma_filt likewise)
+                      p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FILT ||   // (chroma_fft and chroma_filt likewise,
+                      p->cfg.chain_kind == SMILEHIP_CHAIN_SPECTROGRAM;     //  and the spectrogram chain)
   const bool is_aud = p->cfg.chain_kind == SMILEHIP_CHAIN_AUDSPEC;   // (a mel bank and no DCT: first_mfcc / last_mfcc are not read)
   const uint32_t tmask = no_mel ? (mask & ~(SMILEHIP_STAGE_MEL | SMILEHIP_STAGE_MFCC)) : (is_aud ? (mask & ~SMILEHIP_STAGE_MFCC) : mask);
   p->h_window.assign(size_t(p->geo.N), 1.0f);
@@ -386,6 +396,18 @@ static int build_tables(smilehip_plan *p, bool upload = true) {
       return fail(SMILEHIP_ERR_INVALID, "chroma_filt chain: tonefilt_n_notes = %d notes are no multiple of chroma_octave_size %d (cChroma writes no values then)",
                   p->tonefilt.n_notes, c.chroma_octave_size);
     if (!(c.chroma_sil_thresh == c.chroma_sil_thresh)) return fail(SMILEHIP_ERR_INVALID, "chroma_filt chain: chroma_sil_thresh is not a number");
+  } else if (p->cfg.chain_kind == SMILEHIP_CHAIN_SPECTROGRAM) {
+    // everything the chain cannot express is refused with the parameter named
+    const smilehip_lld_config &c = p->cfg;
+    if (mask != SMILEHIP_STAGE_ALL) return fail(SMILEHIP_ERR_INVALID, "spectrogram chain: stage_mask must be all stages");
+    if (c.n_delta != 0) return fail(SMILEHIP_ERR_INVALID, "spectrogram chain: n_delta must be 0 (the file has no cDeltaRegression); got %d", c.n_delta);
+    if (c.preemph) return fail(SMILEHIP_ERR_INVALID, "spectrogram chain: preemph must be 0 (the file has no cVectorPreemphasis)");
+    if (c.append_log_energy) return fail(SMILEHIP_ERR_INVALID, "spectrogram chain: append_log_energy must be 0 (the file has no cEnergy)");
+    if (c.cms) return fail(SMILEHIP_ERR_INVALID, "spectrogram chain: cms must be 0 (the file has no cFullinputMean)");
+    if (p->geo.Nfft < 64 || p->geo.Nfft > 8192)
+      return fail(SMILEHIP_ERR_INVALID, "spectrogram chain: the transform length must be 64 .. 8192 points; frame_size_sec at this sample_rate gives %lld",
+                  (long long)p->geo.Nfft);
+    p->spg_form = spectrogram::form_consts(spectrogram::kMagnitude, p->geo.Nfft, (float)90.302, (float)-102.0);
   } else if (is_aud) {
     // everything the chain cannot express is refused with the parameter named
     const smilehip_lld_config &c = p->cfg;
@@ -742,11 +764,42 @@ extern "C" int smilehip_plan_create_host_only(const smilehip_lld_config *cfg, sm
 
 extern "C" void smilehip_plan_destroy(smilehip_plan *plan) { delete plan; }
 
+// cFFTmagphase's form of a spectrogram plan: the flag bits as the component orders its branches, the mindBp clamp as it applies it
+static const int32_t kSpgFormFlags[5] = {SMILEHIP_MAGPHASE_MAGNITUDE, SMILEHIP_MAGPHASE_MAGNITUDE | SMILEHIP_MAGPHASE_NORMALISE,
+                                         SMILEHIP_MAGPHASE_MAGNITUDE | SMILEHIP_MAGPHASE_POWER,
+                                         SMILEHIP_MAGPHASE_MAGNITUDE | SMILEHIP_MAGPHASE_NORMALISE | SMILEHIP_MAGPHASE_POWER,
+                                         SMILEHIP_MAGPHASE_MAGNITUDE | SMILEHIP_MAGPHASE_NORMALISE | SMILEHIP_MAGPHASE_DBPSD};
+extern "C" int smilehip_plan_set_spectrum_form(smilehip_plan *plan, int32_t flags, float dbp_norm, float min_dbp) {
+  if (!plan) return fail(SMILEHIP_ERR_INVALID, "smilehip_plan_set_spectrum_form: null plan");
+  if (plan->cfg.chain_kind != SMILEHIP_CHAIN_SPECTROGRAM)
+    return fail(SMILEHIP_ERR_INVALID, "smilehip_plan_set_spectrum_form: not a spectrogram plan (chain_kind %d)", plan->cfg.chain_kind);
+  if (flags & SMILEHIP_MAGPHASE_PHASE)
+    return fail(SMILEHIP_ERR_INVALID, "smilehip_plan_set_spectrum_form: SMILEHIP_MAGPHASE_PHASE (cFFTmagphase phase) is not built for the spectrogram chain");
+  if (!(flags & SMILEHIP_MAGPHASE_MAGNITUDE))
+    return fail(SMILEHIP_ERR_INVALID, "smilehip_plan_set_spectrum_form: SMILEHIP_MAGPHASE_MAGNITUDE must be set (cFFTmagphase magnitude = 0 is not built)");
+  const int form = spectrogram::form_of_flags(flags);
+  if (form < 0) return fail(SMILEHIP_ERR_INVALID, "smilehip_plan_set_spectrum_form: unknown flag bits 0x%x", (unsigned)flags);
+  if (form == spectrogram::kDbPsd && (!(dbp_norm == dbp_norm) || !(min_dbp == min_dbp)))
+    return fail(SMILEHIP_ERR_INVALID, "smilehip_plan_set_spectrum_form: dbp_norm / min_dbp is not a number");
+  plan->spg_form = spectrogram::form_consts(form, plan->geo.Nfft, dbp_norm, min_dbp);
+  return SMILEHIP_OK;
+}
+extern "C" int smilehip_plan_get_spectrum_form(const smilehip_plan *plan, int32_t *flags, float *dbp_norm, float *min_dbp) {
+  if (!plan) return fail(SMILEHIP_ERR_INVALID, "smilehip_plan_get_spectrum_form: null plan");
+  if (plan->cfg.chain_kind != SMILEHIP_CHAIN_SPECTROGRAM)
+    return fail(SMILEHIP_ERR_INVALID, "smilehip_plan_get_spectrum_form: not a spectrogram plan (chain_kind %d)", plan->cfg.chain_kind);
+  if (flags) *flags = kSpgFormFlags[plan->spg_form.form];
+  if (dbp_norm) *dbp_norm = plan->spg_form.dbp_norm;
+  if (min_dbp) *min_dbp = plan->spg_form.min_dbp;
+  return SMILEHIP_OK;
+}
+
 int plan_n_static(const smilehip_plan *p) {
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE_F0) return 2;
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_SHS || p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_ACF) return 3;
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT || p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FILT) return p->cfg.chroma_octave_size;
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_AUDSPEC) return p->mel.n_bands;
+  if (p->cfg.chain_kind == SMILEHIP_CHAIN_SPECTROGRAM) return (int)p->geo.K;
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE) return 65;
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_EGEMAPS) return 25;
   return p->cfg.chain_kind == SMILEHIP_CHAIN_IS09 ? 16
@@ -789,6 +842,9 @@ extern "C" double smilehip_row_time(const smilehip_plan *plan, int64_t n_frames,
   // prosodyShs: the rows carry the time stamps of cPitchSmoother's level, whose frame j has that of input frame j + 1
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_SHS)
     return smilehip_frame_time(plan, n_frames >= 2 ? (row < n_frames - 2 ? row : n_frames - 2) + 1 : 0);
+  // spectrogram: as measured on the binary's CSV sink, row t carries the time of its first sample, t * H / sample_rate -- t * frameStep
+  // where frameStep is a whole number of samples, 0.009977 t at 11.025 kHz and 0.010023 t at 22.05 kHz (the HTK header keeps frameStep)
+  if (plan->cfg.chain_kind == SMILEHIP_CHAIN_SPECTROGRAM) return double(row * plan->geo.H) / plan->cfg.sample_rate;
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_MFCC || plan->cfg.chain_kind == SMILEHIP_CHAIN_PLP || plan->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT ||
       plan->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FILT || plan->cfg.chain_kind == SMILEHIP_CHAIN_AUDSPEC ||
       plan->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE_F0 || plan->cfg.chain_kind == SMILEHIP_CHAIN_EGEMAPS || n_frames <= 1)

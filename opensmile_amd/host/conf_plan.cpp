@@ -942,6 +942,107 @@ bool conf_to_chroma_fft(const ConfFile &f, ConfPlan &p, std::string &err) {
   return true;
 }
 
+// ---- smilextract_hip --set spectrogram -C file: config/spectrum/spectrogram.conf with the file's own values. Walked like chroma_fft.conf
+// above; the chain takes the framer's sizes, the window, zeroPadSymmetric and cFFTmagphase's form as parameters. (Plain -C does not
+// map the file: tests/test_conf_plan.py fixes the set of files it maps.)
+std::string spectrum_field_name(int flags) {
+  if (flags & SMILEHIP_MAGPHASE_DBPSD) return "pcm_fftMag_dBsplPSD";
+  const bool n = flags & SMILEHIP_MAGPHASE_NORMALISE, pw = flags & SMILEHIP_MAGPHASE_POWER;
+  return pw ? (n ? "pcm_fftMag_PowSpecDens" : "pcm_fftMag_PowSpec") : (n ? "pcm_fftMag_SpecDens" : "pcm_fftMag");
+}
+bool conf_to_spectrogram(const ConfFile &f, ConfPlan &p, std::string &err) {
+  p = ConfPlan();
+  static const std::vector<std::string> types = {"cFramer", "cWindower", "cTransformFFT", "cFFTmagphase"};
+  std::map<std::string, const ConfInstance *> one;
+  for (const ConfInstance &i : f.inst) {
+    if (is_io_type(i.type)) continue;
+    if (std::find(types.begin(), types.end(), i.type) == types.end()) {
+      err = "component [" + i.name + ":" + i.type + "] is not part of the graph of spectrogram.conf";
+      return false;
+    }
+    if (one.count(i.type)) { err = "more than one " + i.type + " ([" + i.name + "]): not the graph of spectrogram.conf"; return false; }
+    one[i.type] = &i;
+  }
+  for (const std::string &t : types)
+    if (!one.count(t)) { err = "the graph has no " + t + ": not the graph of spectrogram.conf"; return false; }
+  auto lvl = [](const ConfInstance *i, const char *k) { const std::string *v = i->find(k); return v ? *v : std::string(); };
+  auto wired = [&](const ConfInstance *i, const std::string &want) {
+    if (lvl(i, "reader.dmLevel") == want) return true;
+    err = "[" + i->name + ":" + i->type + "] reader.dmLevel = '" + lvl(i, "reader.dmLevel") + "', expected '" + want + "' (not the wiring of spectrogram.conf)";
+    return false;
+  };
+  auto must_be = [](OptReader &o, const char *key, const char *want, const char *dflt) {
+    const std::string v = o.str(key, dflt);
+    if (lower(v) != lower(want) && o.err.empty())
+      o.err = "[" + o.ci.name + ":" + o.ci.type + "] " + key + " = " + v + " is not expressible on the fused path (needs " + want + ")";
+  };
+  const ConfInstance *fr = one["cFramer"], *win = one["cWindower"], *fft = one["cTransformFFT"], *mag = one["cFFTmagphase"];
+  smilehip_lld_config &c = p.cfg;
+  smilehip_config_spectrogram(&c);
+  for (const ConfInstance &i : f.inst)
+    if (i.type == "cWaveSource" && !wired(fr, lvl(&i, "writer.dmLevel"))) return false;
+  {                                                       // src/core/winToVecProcessor.cpp:51-83
+    OptReader o(*fr);
+    c.frame_size_sec = o.num("frameSize", 0.025);
+    c.frame_step_sec = o.num("frameStep", 0.0);
+    if (c.frame_step_sec == 0.0) c.frame_step_sec = c.frame_size_sec;
+    if (!(c.frame_size_sec > 0.0) && o.err.empty()) o.err = "[" + fr->name + ":cFramer] frameSize must be positive";
+    must_be(o, "frameMode", "fixed", "fixed"); must_be(o, "frameCenterSpecial", "left", "left");
+    o.require("noPostEOIprocessing", 1, 1); o.require("frameSizeFrames", 0, 0); o.require("frameStepFrames", 0, 0);
+    o.require("frameCenter", 0, 0); o.require("frameCenterFrames", 0, 0); o.require("allowLastFrameIncomplete", 0, 0);
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  std::string wf;
+  {                                                       // src/dspcore/windower.cpp:36-49
+    OptReader o(*win);
+    if (!wired(win, lvl(fr, "writer.dmLevel"))) return false;
+    wf = o.str("winFunc", "Han");
+    c.win_func = win_func_of(wf);
+    if (c.win_func < 0) o.err = "[" + win->name + ":cWindower] winFunc = " + wf + " is not expressible (Hann, Hamming, rectangular, Gauss, sine, triangle, Bartlett, Lanczos are)";
+    c.win_gain = o.num("gain", 1.0);                      // (the plan's window table carries the gain)
+    c.win_offset = o.num("offset", 0.0);
+    c.win_sigma = o.num("sigma", 0.4);
+    o.require("fade", 0, 0); o.require("squareRoot", 0, 0); o.require("xshift", 0, 0); o.require("processArrayFields", 1, 1);
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  {                                                       // src/dspcore/transformFft.cpp:34-35
+    OptReader o(*fft);
+    if (!wired(fft, lvl(win, "writer.dmLevel"))) return false;
+    o.require("inverse", 0, 0);
+    c.zero_pad_symmetric = o.num("zeroPadSymmetric", 1) != 0.0;
+    o.require("processArrayFields", 1, 1);
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  {                                                       // src/dspcore/fftmagphase.cpp:39-49, :72-97
+    OptReader o(*mag);
+    if (!wired(mag, lvl(fft, "writer.dmLevel"))) return false;
+    o.require("inverse", 0, 0); o.require("magnitude", 1, 1); o.require("phase", 0, 0); o.require("joinMagphase", 0, 0);
+    const bool normalise = o.num("normalise", 0) != 0.0, power = o.num("power", 0) != 0.0, db = o.num("dBpsd", 0) != 0.0;
+    p.spectrum_flags = SMILEHIP_MAGPHASE_MAGNITUDE | (normalise || db ? SMILEHIP_MAGPHASE_NORMALISE : 0) | (power ? SMILEHIP_MAGPHASE_POWER : 0) |
+                       (db ? SMILEHIP_MAGPHASE_DBPSD : 0);
+    p.spectrum_dbp_norm = (float)o.num("dBpnorm", 90.302);
+    p.spectrum_min_dbp = (float)o.num("mindBp", -102.0);
+    o.require("processArrayFields", 1, 1);
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  if (!conf_check_io(f, {lvl(mag, "writer.dmLevel")}, err)) return false;
+  for (const ConfInstance &i : f.inst) {
+    if (i.type == "cWaveSource") { const std::string *fn = i.find("filename"); if (fn) p.wave_file = *fn; }
+    if (i.type == "cArffSink") {
+      const std::string *fn = i.find("filename");
+      if (fn && *fn != "?" && !fn->empty()) { err = "[" + i.name + ":cArffSink] is active (-arffoutput " + *fn + "): the ARFF sink is not built for the spectrogram set"; return false; }
+    }
+    if (i.type == "cHtkSink") { const std::string *pk = i.find("parmKind"); if (pk) p.parm_kind = atoi(pk->c_str()); }
+  }
+  p.lld_names = {spectrum_field_name(p.spectrum_flags)};
+  std::ostringstream d;
+  d << "spectrogram chain: " << c.frame_size_sec * 1e3 << " ms / " << c.frame_step_sec * 1e3 << " ms frames, winFunc " << wf << ", gain " << c.win_gain
+    << ", zeroPadSymmetric " << c.zero_pad_symmetric << ", form " << p.lld_names[0];
+  if (p.spectrum_flags & SMILEHIP_MAGPHASE_DBPSD) d << " (dBpnorm " << p.spectrum_dbp_norm << ", mindBp " << p.spectrum_min_dbp << " before the clamp to dBpnorm - 120)";
+  p.describe = d.str();
+  return true;
+}
+
 // ---- smilextract_hip --set chroma_filt -C file: config/chroma/chroma_filt.conf, possibly with other values of the options the chain takes
 // as parameters (cTonefilt nNotes, firstNote, decayF0, decayFN, outputPeriod; cChroma octaveSize, silThresh). Walked like chroma_fft.conf
 // above. An nNotes that is no multiple of octaveSize is refused: the binary then writes rows of zeros (cChroma logs an error per frame,

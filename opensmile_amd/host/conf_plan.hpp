@@ -54,7 +54,9 @@ struct ConfPlan {
   bool plp = false;
   bool audspec = false;                  // a cPlp with doIDFT = doLP = doLpToCeps = 0: the auditory spectrum (config/audspec), one column per band
   int parm_kind = 9;                     // of the file's own cHtkSink
-  std::vector<std::string> lld_names;    // element names of the output level
+  int spectrum_flags = 0;                // a spectrogram chain (conf_to_spectrogram): cFFTmagphase's form as SMILEHIP_MAGPHASE_* bits, 0 otherwise
+  float spectrum_dbp_norm = (float)90.302, spectrum_min_dbp = (float)-102.0;   //   its dBpnorm / mindBp as the file has them (the plan applies the clamp)
+  std::vector<std::string> lld_names;    // element names of the output level (a spectrogram chain: the field's name alone, the bins follow the rate)
   std::string describe;
   // cepstral chains: the levels between the framer and the cepstra (what the per-frame stages write), and the levels that
   // hold plain static columns of the fused static block (cepstrum j -> j, log energy -> number of cepstra)
@@ -81,6 +83,14 @@ bool conf_to_plan(const ConfFile &f, ConfPlan &p, std::string &err);
 // (doIDFT = doLP = doLpToCeps = 0) admitted: preset = "", cfg = SMILEHIP_CHAIN_AUDSPEC with the file's own values, audspec = true.
 // conf_to_plan itself refuses such a file and names this route.
 bool conf_to_audspec(const ConfFile &f, ConfPlan &p, std::string &err);
+// smilextract_hip --set spectrogram -C file: the file must be the graph of config/spectrum/spectrogram.conf (cFramer, cWindower,
+// cTransformFFT, cFFTmagphase); preset = "", cfg = SMILEHIP_CHAIN_SPECTROGRAM with the file's own frameSize, frameStep, window (function,
+// sigma, gain, offset) and zeroPadSymmetric, spectrum_flags / spectrum_dbp_norm / spectrum_min_dbp = cFFTmagphase's normalise, power,
+// dBpsd, dBpnorm, mindBp. magnitude = 0, phase, joinMagphase, inverse, another frameMode or frameCenterSpecial and any other edit are
+// refused by name. conf_to_plan itself refuses the file; smilextract_hip names this route then.
+bool conf_to_spectrogram(const ConfFile &f, ConfPlan &p, std::string &err);
+// the name cFFTmagphase gives its output field for a set of SMILEHIP_MAGPHASE_* bits (fftmagphase.cpp:141-155), input field `pcm`
+std::string spectrum_field_name(int flags);
 // smilextract_hip --set prosody_shs -C file: the file must be the graph of config/prosody/prosodyShs.conf; preset = "prosody_shs", and
 // unless it is the shipped file itself f0_params holds its values of the options the chain takes as parameters (cPitchShs minPitch,
 // maxPitch, voicingCutoff, nHarmonics, compressionFactor, nCandidates; cSpecScale minF; cContourSmoother smaWin: pitch_min, pitch_max,

@@ -56,6 +56,14 @@ std::vector<std::string> lld_names_audspec(int n_bands, int n_delta, const std::
   }
   return n;
 }
+// config/spectrum/spectrogram.conf, level lld: cFFTmagphase names its one array field after the form (fftmagphase.cpp:141-155: fftMag,
+// fftMag_SpecDens, fftMag_PowSpec, fftMag_PowSpecDens, fftMag_dBsplPSD behind the input field's name pcm; spectrum_field_name,
+// conf_plan.cpp); the binary's CSV header prints pcm_fftMag[0]; .. ;pcm_fftMag[K - 1], K = Nfft / 2 + 1 at the file's own rate
+std::vector<std::string> lld_names_spectrogram(const std::string &field, int n_bins) {
+  std::vector<std::string> n;
+  for (int k = 0; k < n_bins; ++k) n.push_back(field + "[" + std::to_string(k) + "]");
+  return n;
+}
 std::vector<std::string> lld_names_prosody_shs() { return {"F0final_sma", "voicingFinalUnclipped_sma", "pcm_loudness_sma"}; }
 
 std::vector<std::string> lld_names_is09() {

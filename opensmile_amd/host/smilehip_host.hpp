@@ -44,6 +44,7 @@ std::vector<std::string> lld_names_is09();
 std::vector<std::string> lld_names_prosody_shs();   // prosodyShs.conf: F0final_sma, voicingFinalUnclipped_sma, pcm_loudness_sma
 std::vector<std::string> lld_names_prosody_acf();   // prosodyAcf.conf: voiceProb_sma, F0_sma, pcm_loudness_sma
 std::vector<std::string> lld_names_audspec(int n_bands = 26, int n_delta = 2, const std::string &delta_suffix = "de");   // audspec.conf: audSpec[i], audSpec_de[i], audSpec_de_de[i]
+std::vector<std::string> lld_names_spectrogram(const std::string &field = "pcm_fftMag", int n_bins = 257);   // spectrogram.conf: <field>[0 .. K - 1], the field named after cFFTmagphase's form
 std::vector<std::string> lld_names_chroma_fft(int octave_size = 12);   // chroma_fft.conf and chroma_filt.conf: chroma[0] .. chroma[octaveSize - 1]
 std::vector<std::string> lld_names_compare16();
 std::vector<std::string> func_names_is09();     // 384: <lld>_<functional>

@@ -36,6 +36,12 @@
 //                                       auditory spectrum with delta and acceleration, 78 columns (-O out.htk with parmKind 9, -csvoutput
 //                                       out.csv)
 //                   [-C audspec.conf]   with that file's (edited) values through the cepstral-chain walker (plain -C names this route)
+//   smilextract_hip --set spectrogram   config/spectrum/spectrogram.conf: the short-time spectrum, K = Nfft / 2 + 1 columns per frame (257 at
+//                   [-frameSize s] [-frameStep s] [-dB 0|1]   16 kHz): linear magnitude pcm_fftMag[k], or with -dB 1 the dB power spectral
+//                   [-C spectrogram.conf] density pcm_fftMag_dBsplPSD[k]; -O out.htk (parmKind 9), -csvoutput out.csv. -frameSize, -frameStep and
+//                                       -dB are the file's own options, i.e. the framer's. With -C: that file's (edited) frameSize, frameStep,
+//                                       window, zeroPadSymmetric and cFFTmagphase normalise / power / dBpsd / dBpnorm / mindBp; magnitude = 0,
+//                                       phase, joinMagphase, inverse and any other edit are refused by name (plain -C names this route)
 //   smilextract_hip --set gemapsv01a | egemapsv01a   the v01a files: the same columns, zeroPadSymmetric = 0, useBrokenJitterThresh = 1, maxF = 5500
 //   smilextract_hip --set gemapsv01b | egemapsv01b   config/gemaps/v01b/GeMAPSv01b.conf (18 LLDs, 62 functionals) / config/egemaps/v01b/
 //                                       eGeMAPSv01b.conf (23, 88): sub-graphs of eGeMAPSv02.conf, written as column subsets of its levels
@@ -140,7 +146,7 @@ static int run_main(int argc, char **argv, Persist *ps) {
   std::map<std::string, std::string> opt, conf_cmdline;
   const char *with_value[] = {"--set", "-C", "-I", "-filelist", "-O", "-csvoutput", "-htkoutput", "-lldcsvoutput", "-lldhtkoutput",
                               "-instname", "-N", "-outdir", "--device", "--rank", "--world", "--chunk-files", "--master-addr", "--master-port",
-                              "-frameMode", "-frameSize", "-frameStep", "-frameCenterSpecial", "-frameList", "-frameListFile"};
+                              "-frameMode", "-frameSize", "-frameStep", "-frameCenterSpecial", "-frameList", "-frameListFile", "-dB"};
   bool with_conf = false, print_fingerprint = false, describe_only = false, gather = false;
   for (int i = 1; i < argc; ++i)
     if (!strcmp(argv[i], "-C")) with_conf = true;
@@ -164,6 +170,7 @@ static int run_main(int argc, char **argv, Persist *ps) {
       continue;
     }
     if (known) { ++i; continue; }
+    if (!strcmp(argv[i], "-arffoutput")) die("-arffoutput: the ARFF sink is not built for this set (-O writes HTK, -csvoutput CSV)");
     die(std::string("unknown option ") + argv[i]);
   }
   // ---- -C file.conf: the plan comes from the configuration file (conf_plan.cpp)
@@ -174,9 +181,10 @@ static int run_main(int argc, char **argv, Persist *ps) {
     const bool set_chroma = opt.count("--set") && opt["--set"] == "chroma_fft";
     const bool set_filt = opt.count("--set") && opt["--set"] == "chroma_filt";
     const bool set_aud = opt.count("--set") && (opt["--set"] == "audspec" || opt["--set"] == "audspec_compat");
-    const bool set_with_conf = opt.count("--set") && (opt["--set"] == "prosody_shs" || set_acf || set_chroma || set_filt || set_aud);
+    const bool set_spg = opt.count("--set") && opt["--set"] == "spectrogram";
+    const bool set_with_conf = opt.count("--set") && (opt["--set"] == "prosody_shs" || set_acf || set_chroma || set_filt || set_aud || set_spg);
     if (opt.count("--set") && !set_with_conf)
-      die("-C and --set exclude each other (except --set prosody_shs -C prosodyShs.conf, --set prosody_acf -C prosodyAcf.conf, --set chroma_fft -C chroma_fft.conf, --set chroma_filt -C chroma_filt.conf and --set audspec -C audspec.conf)");
+      die("-C and --set exclude each other (except --set prosody_shs -C prosodyShs.conf, --set prosody_acf -C prosodyAcf.conf, --set chroma_fft -C chroma_fft.conf, --set chroma_filt -C chroma_filt.conf, --set audspec -C audspec.conf and --set spectrogram -C spectrogram.conf)");
     ConfFile cf;
     std::string cerr_;
     if (!conf_parse(opt["-C"], conf_cmdline, cf, cerr_)) die("-C " + opt["-C"] + ": " + cerr_);
@@ -199,6 +207,9 @@ static int run_main(int argc, char **argv, Persist *ps) {
       bool is_builtin = false, acted_on = false;
       for (const char *b : builtin) is_builtin = is_builtin || kv.first == b;
       for (const char *h : honoured) acted_on = acted_on || kv.first == h || long_name == h;
+      // --set spectrogram: the file's own frameSize, frameStep and dB are the framer's and cFFTmagphase's (conf_parse has put them in)
+      if (set_spg) acted_on = acted_on || long_name == "frameSize" || long_name == "frameStep" || long_name == "dB";
+      if (set_spg && long_name == "arffoutput" && kv.second != "?") die("-arffoutput: the ARFF sink is not built for --set spectrogram (-O writes HTK, -csvoutput CSV)");
       if (!ok && !is_builtin) die("option -" + kv.first + " is not defined by " + opt["-C"]);
       if (is_builtin || acted_on) continue;
       const auto dflt = cf.cm_defaults.find(long_name);
@@ -218,7 +229,8 @@ static int run_main(int argc, char **argv, Persist *ps) {
           opt[o.second] = dflt->second;
       }
     }
-    if (!(set_aud    ? conf_to_audspec(cf, conf_plan, cerr_)
+    if (!(set_spg    ? conf_to_spectrogram(cf, conf_plan, cerr_)
+          : set_aud  ? conf_to_audspec(cf, conf_plan, cerr_)
           : set_filt ? conf_to_chroma_filt(cf, conf_plan, cerr_)
           : set_chroma ? conf_to_chroma_fft(cf, conf_plan, cerr_)
           : set_acf  ? conf_to_prosody_acf(cf, conf_plan, cerr_)
@@ -230,13 +242,15 @@ static int run_main(int argc, char **argv, Persist *ps) {
       const bool hint_chroma = !set_with_conf && !hint && !hint_acf && conf_to_chroma_fft(cf, as_set, e2);
       const bool hint_filt = !set_with_conf && !hint && !hint_acf && !hint_chroma && conf_to_chroma_filt(cf, as_set, e2);
       if (hint_filt) die("-C " + opt["-C"] + " cannot run on the fused path: " + cerr_ + " -- this file runs as --set chroma_filt -C <file>");
+      if (!set_with_conf && !hint && !hint_acf && !hint_chroma && conf_to_spectrogram(cf, as_set, e2))
+        die("-C " + opt["-C"] + " cannot run on the fused path: " + cerr_ + " -- this file runs as --set spectrogram -C <file>");
       die("-C " + opt["-C"] + " cannot run on the fused path: " + cerr_ +
           (hint ? " -- this file runs as --set prosody_shs -C <file>"
                 : (hint_acf ? " -- this file runs as --set prosody_acf -C <file>" : (hint_chroma ? " -- this file runs as --set chroma_fft -C <file>" : ""))));
     }
     fprintf(stderr, "smilextract_hip: %s -> %s\n", opt["-C"].c_str(), conf_plan.describe.c_str());
     if (!conf_plan.preset.empty()) opt["--set"] = conf_plan.preset;
-    else if (set_aud) opt.erase("--set");                  // (the file's own values, zeroPadSymmetric among them: the free chain below)
+    else if (set_aud || set_spg) opt.erase("--set");       // (the file's own values, zeroPadSymmetric among them: the free chain below)
     if (describe_only) {                                   // what the file maps to, without touching a device
       const smilehip_lld_config &c = conf_plan.cfg;
       printf("preset=%s\n", conf_plan.preset.c_str());
@@ -250,6 +264,9 @@ static int run_main(int argc, char **argv, Persist *ps) {
                c.win_gain, c.win_offset, c.zero_pad_symmetric, c.n_bands, (double)c.lofreq, (double)c.hifreq, c.use_power,
                c.mel_htk_compatible, c.first_mfcc, c.last_mfcc, (double)c.cep_lifter, c.mfcc_htk_compatible, (double)c.melfloor, c.n_delta,
                c.delta_win, c.plp_lp_order, (double)c.plp_compression, c.append_log_energy, c.cms, conf_plan.parm_kind);
+        if (conf_plan.spectrum_flags)                      // a spectrogram chain: the form; the names are <field>[0 .. Nfft / 2] at each file's rate
+          printf("spectrum_flags=%d\nspectrum_field=%s\ndbp_norm=%.9g\nmin_dbp=%.9g\n", conf_plan.spectrum_flags,
+                 spectrum_field_name(conf_plan.spectrum_flags).c_str(), (double)conf_plan.spectrum_dbp_norm, (double)conf_plan.spectrum_min_dbp);
         printf("names=");
         for (size_t k = 0; k < conf_plan.lld_names.size(); ++k) printf("%s%s", k ? ";" : "", conf_plan.lld_names[k].c_str());
         printf("\n");
@@ -280,6 +297,12 @@ static int run_main(int argc, char **argv, Persist *ps) {
   const bool out_subset = egm_subset || cmp_subset;
   if (out_subset && gather) die("--gather is not available with a set that writes a column selection (" + set + "): gather the whole vectors and select");
   const bool has_func = is09 || cmp16f || egm;
+  // config/spectrum/spectrogram.conf: an LLD-only set whose -frameSize / -frameStep / -dB are the file's own options (the framer's and
+  // cFFTmagphase's), not the functionals windows of the other sets; with -C it is the free chain with the file's values
+  const bool spectrogram = set == "spectrogram" || (free_chain && conf_plan.cfg.chain_kind == SMILEHIP_CHAIN_SPECTROGRAM);
+  if (opt.count("-dB") && !spectrogram) die("-dB is an option of --set spectrogram (config/spectrum/spectrogram.conf)");
+  if (spectrogram && opt.count("-frameMode") && opt["-frameMode"] != "full")
+    die("-frameMode " + opt["-frameMode"] + ": --set spectrogram has no functionals level (its -frameSize / -frameStep are the framer's); only full is accepted");
   // ---- functionals over fixed windows (cWinToVecProcessor frameMode = fixed): IS09_emotion's one instance
   const std::string frame_mode = opt.count("-frameMode") ? opt["-frameMode"] : "full";
   if (frame_mode != "full" && frame_mode != "fixed" && frame_mode != "list")
@@ -324,10 +347,38 @@ static int run_main(int argc, char **argv, Persist *ps) {
   // config/audspec/audspec.conf and audspec_compat.conf: LLD-only sets through standard_data_output_lldonly, like the cepstral files
   const bool audspec = set == "audspec" || set == "audspec_compat";
   if (audspec) { if (set == "audspec") smilehip_config_audspec(&vcfg); else smilehip_config_audspec_compat(&vcfg); }
-  const bool htk_variant = free_chain || prosody || audspec || (!is09 && !cmp16 && !egm && smilehip_config_htk_variant(&vcfg, variant.c_str()) == SMILEHIP_OK);
+  int spectrum_flags = SMILEHIP_MAGPHASE_MAGNITUDE;
+  float spectrum_dbp_norm = (float)90.302, spectrum_min_dbp = (float)-102.0;
+  if (spectrogram && !free_chain) {
+    smilehip_config_spectrogram(&vcfg);
+    auto seconds = [&](const char *o, double dflt) {
+      if (!opt.count(o)) return dflt;
+      char *end = nullptr;
+      const double v = strtod(opt[o].c_str(), &end);
+      if (end == opt[o].c_str() || *end || !(v > 0.0)) die(std::string(o) + " " + opt[o] + ": a positive number of seconds is needed");
+      return v;
+    };
+    vcfg.frame_size_sec = seconds("-frameSize", 0.025);
+    vcfg.frame_step_sec = seconds("-frameStep", 0.010);
+    if (opt.count("-dB") && opt["-dB"] != "0" && opt["-dB"] != "1") die("-dB " + opt["-dB"] + ": 0 or 1");
+    if (opt.count("-dB") && opt["-dB"] == "1") spectrum_flags |= SMILEHIP_MAGPHASE_NORMALISE | SMILEHIP_MAGPHASE_DBPSD;
+  } else if (spectrogram) {
+    spectrum_flags = conf_plan.spectrum_flags;
+    spectrum_dbp_norm = conf_plan.spectrum_dbp_norm;
+    spectrum_min_dbp = conf_plan.spectrum_min_dbp;
+  }
+  if (spectrogram && describe_only && !free_chain) {       // what the set runs with, without touching a device
+    printf("preset=spectrogram\nchain_kind=%d\nframe_size_sec=%.17g\nframe_step_sec=%.17g\nwin_func=%d\nzero_pad_symmetric=%d\n"
+           "spectrum_flags=%d\nspectrum_field=%s\ndbp_norm=%.9g\nmin_dbp=%.9g\nparm_kind=9\nnames=%s\n",
+           vcfg.chain_kind, vcfg.frame_size_sec, vcfg.frame_step_sec, vcfg.win_func, vcfg.zero_pad_symmetric, spectrum_flags,
+           spectrum_field_name(spectrum_flags).c_str(), (double)spectrum_dbp_norm, (double)spectrum_min_dbp, spectrum_field_name(spectrum_flags).c_str());
+    return 0;
+  }
+  const std::string spectrum_field = spectrum_field_name(spectrum_flags);
+  const bool htk_variant = free_chain || prosody || audspec || spectrogram || (!is09 && !cmp16 && !egm && smilehip_config_htk_variant(&vcfg, variant.c_str()) == SMILEHIP_OK);
   const bool plp = htk_variant && vcfg.chain_kind == SMILEHIP_CHAIN_PLP;
   if (!is09 && !cmp16 && !egm && !htk_variant)
-    die("--set must be mfcc12_{0,e}_d_a[_z], plp_{0,e}_d_a[_z], is09_emotion, compare16, compare16_lld, is13_compare, egemapsv02, gemapsv01b, egemapsv01b, gemapsv01a, egemapsv01a, prosody_shs, prosody_acf, chroma_fft, chroma_filt, audspec or audspec_compat (or use -C file.conf)");
+    die("--set must be mfcc12_{0,e}_d_a[_z], plp_{0,e}_d_a[_z], is09_emotion, compare16, compare16_lld, is13_compare, egemapsv02, gemapsv01b, egemapsv01b, gemapsv01a, egemapsv01a, prosody_shs, prosody_acf, chroma_fft, chroma_filt, spectrogram, audspec or audspec_compat (or use -C file.conf)");
   // parmKind of the files' own cHtkSink sections (the _Z files); the others write through standard_data_output_lldonly (9)
   int parm_kind = 9;
   if (variant == "MFCC12_0_D_A_Z") parm_kind = 11014;
@@ -665,6 +716,7 @@ static int run_main(int argc, char **argv, Persist *ps) {
       if (with_conf) conf_apply_f0_params(conf_plan, cfg);     // an edited big-set file: its own pitch range, harmonics, buffer ...
       cfg.sample_rate = (double)rate;
       check(smilehip_plan_create(ctx, &cfg, &plan), "smilehip_plan_create");
+      if (spectrogram) check(smilehip_plan_set_spectrum_form(plan, spectrum_flags, spectrum_dbp_norm, spectrum_min_dbp), "smilehip_plan_set_spectrum_form");
     }
     return plan;
   };
@@ -894,6 +946,9 @@ static int run_main(int argc, char **argv, Persist *ps) {
           int n_w = n_out;                                  // columns written (a subset preset writes its selection)
           std::vector<float> x_sel;
           if (out_subset) { x_sel = select_columns(x, r, n_out, sel_lld); x = x_sel.data(); n_w = (int)sel_lld.size(); }
+          std::vector<std::string> spg_names;               // the spectrogram set: <field>[0 .. K - 1], K the file's own (its rate's)
+          if (spectrogram && want_lld_csv) spg_names = lld_names_spectrogram(spectrum_field, n_w);
+          const std::vector<std::string> &lld_names_w = spectrogram ? spg_names : lld_names;
           if (want_lld_htk && chroma) {                     // chroma_fft.conf's own sink: values only (printHeader = 0, timestamp = 0, number = 0)
             CsvOptions co;
             co.print_header = co.timestamp = co.name_column = false;
@@ -911,7 +966,7 @@ static int run_main(int argc, char **argv, Persist *ps) {
             const int64_t n_frames = (cmp16 || egm) ? r - 1 : smilehip_num_frames(plan, w->true_off[i + 1] - w->true_off[i]);
             std::vector<double> times((size_t)r);
             for (int64_t t = 0; t < r; ++t) times[(size_t)t] = smilehip_row_time(plan, n_frames, t);
-            if (!write_csv(per_file(job, lld_csv_opt, (lld_opts || chroma) ? ".lld.csv" : ".csv"), lld_names, x, r, n_w, n_w, g.frame_period,
+            if (!write_csv(per_file(job, lld_csv_opt, (lld_opts || chroma) ? ".lld.csv" : ".csv"), lld_names_w, x, r, n_w, n_w, g.frame_period,
                            times.data(), co, err)) {
               die(err);
               return;
