@@ -306,6 +306,23 @@ typedef struct smilehip_lld_config {
  * One frame kernel (lld_spectrogram_frame: a wave per frame for transforms of 512 / 1024 points, a workgroup per frame otherwise)
  * writes the rows straight into the caller's matrix: no scratch, no tap, no window chain. The transform length must be 64 .. 8192. */
 #define SMILEHIP_CHAIN_SPECTROGRAM 12
+/* SMILEHIP_CHAIN_EMOBASE: the levels `lld` and `lld_de` of config/emobase/emobase.conf, what its lldsink / lldhtksink write as
+ * `lld;lld_de`: 2 (18 + p) columns, 52 with the file's cLpc order p = 8 (smilehip_plan_set_lpc_order):
+ *   pcm_intensity, pcm_loudness, mfcc[1..12], lspFreq[0..p-1], pcm_zcr, voiceProb, F0, F0env (each _sma) | the same with _sma_de
+ * from two framers with one step (frameCenterSpecial = left): 25 ms frames (frame_size_sec) -- cIntensity with both outputs
+ * (src/lldcore/intensity.cpp:125-145: MIN(N, outputs) = 2 terms) and cMZcr on the raw frame, cVectorPreemphasis, then cLpc (method
+ * acf, src/lld/lpc.cpp:171-213) and cLsp (src/lld/lsp.cpp:112-312) on the unwindowed frame, and Hamming window, cTransformFFT,
+ * cFFTmagphase, cMelspec, cMfcc 1..12 -- and 40 ms frames: Hamming window, transform, magnitudes, [acf40:cAcf] (usePower, no / K) and
+ * [cepstrum40:cAcf] with oldCompatCepstrum (src/dspcore/acf.cpp:275-286, :321-331), cPitchACF with voiceProb, F0 and F0env
+ * (src/lldcore/pitchACF.cpp:137-243). cContourSmoother (sma_win) reads the five levels side by side, cDeltaRegression (delta_win 2)
+ * follows. Rows per utterance, as measured against the binary: T40 + smaWin / 2 for T40 >= 1 frames of 40 ms, none for T40 = 0,
+ * however many 25 ms frames there are; every column is smoothed over its own level's frames (the pitch columns replicate frame
+ * T40 - 1 where the others still read frames up to T25 - 1); row n carries the time of frame n for n < smaWin / 2 and of frame
+ * min(n, T25 - 1) otherwise (lld_emobase_ops.hpp states the rules and the inputs they were measured on). One frame kernel
+ * (lld_emobase_frame: a wave per step at 8 / 11.025 / 16 kHz, a workgroup per step otherwise), a row kernel for cLpc and cLsp, the
+ * contour per utterance, a row kernel for the smoother and the regression. The functionals level of the file is not built.
+ * smilehip_batch_emobase_taps returns the levels in front of the smoother. */
+#define SMILEHIP_CHAIN_EMOBASE 13
 
 #define SMILEHIP_STAGE_WINDOW 1u
 #define SMILEHIP_STAGE_FFT    2u
@@ -411,6 +428,29 @@ void smilehip_config_audspec_compat(smilehip_lld_config *c);
  *   [frame:cFramer] 0.025 / 0.010 s, frameMode = fixed, frameCenterSpecial = left; no pre-emphasis; [win:cWindower] ham, gain 1,
  *   offset 0; [fft:cTransformFFT] sets nothing: zeroPadSymmetric at its default 1; [fftmag:cFFTmagphase] plain magnitude. */
 void smilehip_config_spectrogram(smilehip_lld_config *c);
+/* fills c -- SMILEHIP_LLD_CONFIG_SIZE_V1 bytes, struct_size = that -- with config/emobase/emobase.conf (chain_kind = EMOBASE); the
+ * caller sets sample_rate afterwards:
+ *   [fr25:cFramer] 0.025 / 0.010 s and [fr40:cFramer] 0.040 / 0.010 s, frameCenterSpecial = left; [pe:cVectorPreemphasis] k = 0.97;
+ *   [win] / [w40] ham, gain 1, offset 0; [fft] / [fft40] zeroPadSymmetric = 0; [mspec:cMelspec] 26 bands 0 .. 8000 Hz, usePower,
+ *   htkcompatible; [mfcc:cMfcc] 1 .. 12, cepLifter 22, htkcompatible; [lpc:cLpc] method = acf, p = 8 (the plan's,
+ *   smilehip_plan_set_lpc_order); [lsp:cLsp]; [intens:cIntensity] intensity and loudness; [mzcr:cMZcr] zcr; [acf40] usePower 1,
+ *   acfCepsNormOutput 0; [cepstrum40] oldCompatCepstrum 1; [pitchACF] maxPitch 500, voicingCutoff 0.55, voiceProb, F0, F0env;
+ *   [lld:cContourSmoother] smaWin 3; [delta1:cDeltaRegression] deltawin 2. The 40 ms framer's length is the chain's, not a field. */
+void smilehip_config_emobase(smilehip_lld_config *c);
+/* cLpc's order p of a SMILEHIP_CHAIN_EMOBASE plan (the config struct has no field for it): even, 2 .. 16; 8 on a fresh plan. The plan
+ * then has 2 (18 + p) output columns. Set it before the plan's batches are created: a batch keeps the order it was laid out for, and
+ * a run on it with another order is refused. Any plan of another chain is refused (SMILEHIP_ERR_INVALID). Works on host-only plans. */
+int smilehip_plan_set_lpc_order(smilehip_plan *plan, int32_t p);
+int smilehip_plan_get_lpc_order(const smilehip_plan *plan, int32_t *p);
+/* the second framer of a SMILEHIP_CHAIN_EMOBASE plan: samples per 40 ms frame and its transform's length (smilehip_plan_geometry
+ * describes the 25 ms framer); either pointer may be NULL */
+int smilehip_plan_emobase_frame40(const smilehip_plan *plan, int64_t *frame_size, int64_t *fft_size);
+/* emobase chain tap (tests / diagnostics; SMILEHIP_CHAIN_EMOBASE batches): device pointers to the per-frame scratch the last
+ * smilehip_lld_run of this batch filled, both with one row per 25 ms frame of the batch (n_frames, the batch's frame offsets):
+ * d_raw25 [n_frames x (15 + p)] = pcm_intensity | pcm_loudness | mfcc[1..12] | lspFreq[0..p-1] | pcm_zcr, the levels intens, mfcc1,
+ * lsp and mzcr; d_raw3 [n_frames x 3] = voiceProb | F0 | F0env, the level pitch, of which an utterance's first T40 rows are written
+ * (T40 = its 40 ms frames; the one or two rows behind them are never read). */
+int smilehip_batch_emobase_taps(smilehip_batch *batch, float **d_raw25, float **d_raw3, int64_t *n_frames, int32_t *n25);
 /* cFFTmagphase's output form of a SMILEHIP_CHAIN_SPECTROGRAM plan (the config struct has no field for it): flags are the
  * SMILEHIP_MAGPHASE_* bits below -- MAGNITUDE alone (a fresh plan), or MAGNITUDE with NORMALISE, POWER, NORMALISE | POWER, or DBPSD
  * (which implies NORMALISE and wins over POWER, as in the component). dbp_norm / min_dbp are the component's dBpnorm / mindBp

@@ -236,6 +236,11 @@ SYMBOLS = {
     "smilehip_config_audspec": (None, [C.POINTER(LldConfig)]),
     "smilehip_config_audspec_compat": (None, [C.POINTER(LldConfig)]),
     "smilehip_config_spectrogram": (None, [C.POINTER(LldConfig)]),
+    "smilehip_config_emobase": (None, [C.POINTER(LldConfig)]),
+    "smilehip_plan_set_lpc_order": (C.c_int, [_vp, C.c_int32]),
+    "smilehip_plan_get_lpc_order": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
+    "smilehip_plan_emobase_frame40": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "smilehip_batch_emobase_taps": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i64), C.POINTER(C.c_int32)]),
     "smilehip_plan_set_spectrum_form": (C.c_int, [_vp, C.c_int32, C.c_float, C.c_float]),
     "smilehip_plan_get_spectrum_form": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "smilehip_tonespec_op_create": (C.c_int, [_vp, _vp, _i64, _dbl, _vp]),
@@ -683,6 +688,18 @@ def spectrogram_config(sample_rate=16000.0, frame_size=0.025, frame_step=0.010):
     return c
 
 
+CHAIN_EMOBASE = 13
+
+
+def emobase_config(sample_rate=16000.0):
+    """config/emobase/emobase.conf, levels lld and lld_de (chain_kind = EMOBASE): 2 (18 + p) columns, 52 with cLpc's p = 8
+    (Plan.set_lpc_order). The preset fills LLD_CONFIG_SIZE_V1 bytes; the sample rate is set here."""
+    c = LldConfig()
+    load().smilehip_config_emobase(C.byref(c))
+    c.sample_rate = float(sample_rate)
+    return c
+
+
 def tonefilt_tables(opts, sample_rate):
     """smilehip_tonefilt_op_tables: dict of P (samples per block), freq, decay"""
     L = load()
@@ -1023,6 +1040,22 @@ class Plan:
         _check(load().smilehip_plan_get_spectrum_form(self._h, C.byref(f), C.byref(a), C.byref(b)))
         return f.value, a.value, b.value
 
+    def set_lpc_order(self, p):
+        """emobase chain plans: cLpc's order (even, 2 .. 16; 8 on a fresh plan); batches created afterwards are laid out for it"""
+        _check(load().smilehip_plan_set_lpc_order(self._h, int(p)))
+        _check(load().smilehip_plan_geometry(self._h, C.byref(self.geometry)))
+
+    def emobase_frame40(self):
+        """(samples per 40 ms frame, its transform's length) of an emobase chain plan; self.geometry describes the 25 ms framer"""
+        n, nfft = _i64(0), _i64(0)
+        _check(load().smilehip_plan_emobase_frame40(self._h, C.byref(n), C.byref(nfft)))
+        return n.value, nfft.value
+
+    def lpc_order(self):
+        p = C.c_int32()
+        _check(load().smilehip_plan_get_lpc_order(self._h, C.byref(p)))
+        return p.value
+
     def set_timing(self, on=True):
         _check(load().smilehip_plan_set_timing(self._h, 1 if on else 0))
 
@@ -1242,6 +1275,44 @@ class Batch:
             L.smilehip_free(ctx, d_pcm)
             L.smilehip_free(ctx, d_out)
         return out
+
+    def emobase_run_host(self, pcm, ld_out=None, fill=0.0, runs=1):
+        """emobase chain plans: run on host data (int16 samples through smilehip_lld_run, a float32 array through
+        smilehip_lld_run_f32) into a matrix [total_rows x ld_out] that held `fill` everywhere before, `runs` times over. Returns it
+        and the taps (smilehip_batch_emobase_taps), both with one row per 25 ms frame of the batch: [total_frames x (15 + p)] =
+        intens | mfcc1 | lsp | mzcr and [total_frames x 3] = the level pitch (an utterance's first T40 rows are written)."""
+        L = load()
+        ctx = self.plan.ctx._h
+        assert self.plan.cfg.chain_kind == CHAIN_EMOBASE, "not an emobase chain plan"
+        ld_out = self.plan.geometry.n_out if ld_out is None else ld_out
+        f32 = np.asarray(pcm).dtype == np.float32
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32 if f32 else np.int16)
+        out = np.full((self.total_rows, ld_out), fill, np.float32)
+        d_pcm, d_out = _vp(), _vp()
+        _check(L.smilehip_alloc(ctx, max(pcm.nbytes, 4), C.byref(d_pcm)))
+        _check(L.smilehip_alloc(ctx, max(out.nbytes, 4), C.byref(d_out)))
+        try:
+            if pcm.nbytes:
+                _check(L.smilehip_copy_to_device(ctx, d_pcm, pcm.ctypes.data, pcm.nbytes, None))
+            if out.nbytes:
+                _check(L.smilehip_copy_to_device(ctx, d_out, out.ctypes.data, out.nbytes, None))
+            for _ in range(runs):
+                _check((L.smilehip_lld_run_f32 if f32 else L.smilehip_lld_run)(self.plan._h, self._h, d_pcm, d_out, ld_out, None))
+            _check(L.smilehip_stream_synchronize(ctx, None))
+            d25, d3, nf, n25 = _vp(), _vp(), _i64(0), C.c_int32(0)
+            _check(L.smilehip_batch_emobase_taps(self._h, C.byref(d25), C.byref(d3), C.byref(nf), C.byref(n25)))
+            assert nf.value == self.total_frames
+            tap25 = np.zeros((self.total_frames, n25.value), np.float32)
+            tap3 = np.zeros((self.total_frames, 3), np.float32)
+            if out.nbytes:
+                _check(L.smilehip_copy_to_host(ctx, out.ctypes.data, d_out, out.nbytes, None))
+            if tap25.nbytes:
+                _check(L.smilehip_copy_to_host(ctx, tap25.ctypes.data, d25, tap25.nbytes, None))
+                _check(L.smilehip_copy_to_host(ctx, tap3.ctypes.data, d3, tap3.nbytes, None))
+        finally:
+            L.smilehip_free(ctx, d_pcm)
+            L.smilehip_free(ctx, d_out)
+        return out, tap25, tap3
 
     def func_rows(self):
         """LLD rows each utterance's functionals summarise (IS09 chain plans)."""

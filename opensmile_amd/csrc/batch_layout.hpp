@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/smilehip.h"
+#include "lld_emobase_ops.hpp"
 #include "lld_tile_rec.hpp"
 #include "lld_tonefilt_ops.hpp"
 
@@ -41,7 +42,7 @@ struct BatchLayout {
   int32_t run_frames = 8;
   std::vector<FTileRec> ftiles;                        // MFCC / PLP: non-empty when the batch runs the delta-fused fast kernel
   std::vector<int32_t> jit_utt, jit_t0;                // F0 group
-  std::vector<int32_t> frame_utt;                      // IS09, prosodyAcf, chroma_fft, audspec, spectrogram: the utterance of every frame
+  std::vector<int32_t> frame_utt;                      // IS09, prosodyAcf, chroma_fft, audspec, spectrogram, emobase: the utterance of every frame
 };
 
 constexpr int kRunFramesMin = 8;   // frames per 20 ms run when the caller names none (lld_compare.hip / lld_gemaps.hip)
@@ -61,6 +62,7 @@ inline int64_t layout_num_frames(const BatchLayoutSpec &s, int64_t len) {
   return s.chain_kind == SMILEHIP_CHAIN_CHROMA_FILT ? tonefilt::rows_of(len, s.H) : layout_num_frames(len, s.N, s.H);
 }
 inline int64_t samples_60ms(double period) { return std::lround(0.060 / period); }
+inline int64_t samples_40ms(double period) { return std::lround(0.040 / period); }   // emobase.conf [fr40:cFramer]
 
 // Output rows of an utterance of `len` samples / T frames. The 20 ms chains hold rows = T60 + 1, T60 = frames of the 60 ms
 // framer ([is13_frame60]; what both egemapsv02_lldsetE_smo and egemapsv02_lldsetF_smo hold): none if T60 < 4 (ComParE) / < 1 (eGeMAPS).
@@ -68,6 +70,8 @@ inline int64_t layout_rows(const BatchLayoutSpec &s, int64_t len, int64_t T) {
   const bool compare = s.chain_kind == SMILEHIP_CHAIN_COMPARE_AB || s.chain_kind == SMILEHIP_CHAIN_COMPARE;
   // prosodyShs: cPitchSmoother's level holds T - 1 frames (no output for its first call), the smoother adds its end-of-input rows
   if (s.chain_kind == SMILEHIP_CHAIN_PROSODY_SHS) return T >= 2 ? T - 1 + s.row_extra : 0;
+  // emobase: the smoother reads four levels of T (25 ms) frames and one of T40 <= T; the shortest decides (emobase::rows_of)
+  if (s.chain_kind == SMILEHIP_CHAIN_EMOBASE) return emobase::rows_of(T, layout_num_frames(len, samples_40ms(s.period), s.H), (int)s.row_extra);
   // (IS09 and prosodyAcf: T + smaWin / 2 rows, prosody_acf::rows_of; chroma_fft and chroma_filt: T rows, chroma::rows_of / tonefilt::rows_of;
   //  audspec: T rows, audspec::rows_of; spectrogram: T rows, spectrogram::rows_of)
   if (!compare && s.chain_kind != SMILEHIP_CHAIN_EGEMAPS) return T > 0 ? T + s.row_extra : 0;
@@ -166,7 +170,7 @@ inline int batch_layout(const BatchLayoutSpec &s, const int64_t *h_off, int32_t 
   out.total_frames = out.frame_off[n_utt];
   out.total_rows = out.row_off[n_utt];
   if ((s.chain_kind == SMILEHIP_CHAIN_IS09 || s.chain_kind == SMILEHIP_CHAIN_PROSODY_ACF || s.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT ||
-       s.chain_kind == SMILEHIP_CHAIN_AUDSPEC || s.chain_kind == SMILEHIP_CHAIN_SPECTROGRAM) &&
+       s.chain_kind == SMILEHIP_CHAIN_AUDSPEC || s.chain_kind == SMILEHIP_CHAIN_SPECTROGRAM || s.chain_kind == SMILEHIP_CHAIN_EMOBASE) &&
       out.total_frames > 0) {
     out.frame_utt.resize((size_t)out.total_frames);
     for (int32_t u = 0; u < n_utt; ++u) std::fill(out.frame_utt.begin() + out.frame_off[u], out.frame_utt.begin() + out.frame_off[u + 1], u);

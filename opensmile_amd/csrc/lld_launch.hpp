@@ -97,6 +97,11 @@ hipError_t stage_tonefilt_blocks(const TonefiltParams &Q, const float *samples, 
                                  float *dst, hipStream_t s);
 // sincos_d (lld_sincos_d.hpp) on n doubles: smilehip_sincos_d_values
 hipError_t stage_sincos_d(const double *x, int64_t n, double *sn, double *cs, hipStream_t s);
+// emobase.conf: lld_emobase_frame (a wave per step for 25 / 40 ms transforms of 256 / 512 points, a workgroup per step otherwise)
+// into E.raw25 / E.raw3, lld_emobase_lsp (a lane per 25 ms frame), cPitchACF's contour with F0env (a lane per utterance), then
+// lld_emobase_tail: the rows of lld | lld_de into P.out (lld_emobase.hip). P.frame_utt is required.
+hipError_t launch_emobase(const LldParams &P, const EmobaseParams &E, hipStream_t s);
+int emobase_wave_steps();           // steps per workgroup of the wave form
 int f0_chunk_tiles();
 int f0_tile_frames();
 // cPitchSmootherViterbi as a stream: one frame (or the flush) per launch, state in global memory

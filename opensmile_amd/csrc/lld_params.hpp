@@ -225,6 +225,28 @@ struct TonefiltParams {
   float *tonespec;                  // [total_frames x n_notes] the level tonespec (smilehip_batch_chroma_taps), packed
 };
 
+// emobase.conf (lld_emobase.hip, lld_emobase_ops.hpp): what lld_emobase_frame and the row kernels behind it need next to LldParams,
+// which describes the 25 ms framer (batch, geometry, pre-emphasis, window, transform tables, mel bank, DCT)
+struct EmobaseParams {
+  // ---- the 40 ms framer ([fr40] .. [pitchACF]) ----
+  int32_t N40, Nfft40;              // samples per frame, transform length (M40 = Nfft40 / 2 lags)
+  const float *window40;            // [N40] Hamming
+  OouraTab oo40;
+  float fsSec40;                    // (float) frameSizeSec of the ACF level (pitchACF.cpp:113-116)
+  double maxPitch;
+  double voicingCutoff;             // clamped to [0, 1] (pitchACF.cpp:96-98)
+  // ---- the 25 ms framer ----
+  double w0, w1, win_sum;           // cIntensity: the Hamming window's first two values and its sum in index order (intensity.cpp:99-104)
+  int32_t p;                        // cLpc's order (even, 2 .. 16)
+  int32_t n25;                      // 15 + p columns of raw25
+  int32_t W;                        // cContourSmoother smaWin / 2
+  // ---- scratch, rows = the batch's 25 ms frames (frame_off) ----
+  float *raw25;                     // [total_frames x n25] intensity | loudness | mfcc 1 .. 12 | lsp (p) | zcr
+  float *raw3;                      // [total_frames x 3] voiceProb | cut-off pitch candidate -> F0 | F0env; an utterance's rows t < T40 are written
+  const int64_t *row_off;           // [n_utt + 1] output rows
+  int64_t total_rows;
+};
+
 // eGeMAPSv02 / GeMAPSv01b LLD level (lld_gemaps.hip): per-frame scratch and constants
 struct GemapsParams {
   // ---- 20 ms chain ----

@@ -53,6 +53,19 @@ static int alloc_prosody_acf_scratch(smilehip_batch *b, const BatchLayout &L) {
   return SMILEHIP_OK;
 }
 
+// emobase: the utterance of every 25 ms frame; 15 + p floats per frame for the 25 ms levels and three for the level pitch (a row per
+// 25 ms frame: an utterance's first T40 are written; the rest stays zero)
+static int alloc_emobase_scratch(const smilehip_plan *plan, smilehip_batch *b, const BatchLayout &L) {
+  int rc;
+  if (b->total_frames > 0 && (rc = b->d_frame_utt.upload(L.frame_utt))) return rc;
+  b->emo_p = plan->emo_lpc_order;
+  const size_t nf = at_least_one(b->total_frames);
+  if (b->d_raw25.alloc(nf * (size_t)emobase::n25_cols(b->emo_p)) || b->d_raw3.alloc(nf * 3))
+    return fail(SMILEHIP_ERR_HIP, "hipMalloc of the emobase scratch matrices failed");
+  HIP_TRY(hipMemset(b->d_raw3.p, 0, nf * 3 * sizeof(float)));
+  return SMILEHIP_OK;
+}
+
 // chroma_fft: the utterance of every frame, and the level tonespec
 static int alloc_chroma_scratch(smilehip_plan *plan, smilehip_batch *b, const BatchLayout &L) {
   int rc;
@@ -212,6 +225,7 @@ extern "C" int smilehip_batch_create(smilehip_plan *plan, const int64_t *h_off, 
     case SMILEHIP_CHAIN_CHROMA_FILT: rc = alloc_chroma_filt_scratch(plan, b.get()); break;
     case SMILEHIP_CHAIN_AUDSPEC: rc = alloc_audspec_scratch(plan, b.get(), L); break;
     case SMILEHIP_CHAIN_SPECTROGRAM: rc = alloc_spectrogram_scratch(b.get(), L); break;
+    case SMILEHIP_CHAIN_EMOBASE: rc = alloc_emobase_scratch(plan, b.get(), L); break;
     case SMILEHIP_CHAIN_COMPARE: rc = alloc_compare_scratch(plan, b.get(), L); break;
     case SMILEHIP_CHAIN_EGEMAPS: rc = alloc_egemaps_scratch(plan, b.get(), L); break;
     case SMILEHIP_CHAIN_MFCC:
@@ -610,6 +624,56 @@ static int spectrogram_run(smilehip_plan *plan, smilehip_batch *b, const int16_t
   return timing_mark(plan, 2, s);
 }
 
+// SMILEHIP_CHAIN_EMOBASE: lld_emobase_frame (both framers' per-frame values) -> lld_emobase_lsp (cLpc, cLsp per 25 ms frame) ->
+// cPitchACF's contour and F0env per utterance -> lld_emobase_tail (cContourSmoother and cDeltaRegression by the measured row rules)
+static int emobase_run(smilehip_plan *plan, smilehip_batch *b, const int16_t *d_pcm, float *d_out, int64_t ld_out, void *stream) {
+  const int n_out = plan_n_out(plan);
+  if (ld_out < n_out) return fail(SMILEHIP_ERR_INVALID, "ld_out %lld < n_out %d", (long long)ld_out, n_out);
+  if (b->emo_p != plan->emo_lpc_order)
+    return fail(SMILEHIP_ERR_INVALID, "emobase chain: the batch was laid out for cLpc p = %d, the plan now has %d (smilehip_plan_set_lpc_order before smilehip_batch_create)",
+                b->emo_p, plan->emo_lpc_order);
+  if (b->total_frames == 0) return SMILEHIP_OK;
+  if (!d_pcm || (!d_out && b->total_rows > 0)) return fail(SMILEHIP_ERR_INVALID, "smilehip_lld_run: null device pointer");
+  hipStream_t s = (hipStream_t)stream;
+  LldParams P;
+  fill_params(plan, b, d_pcm, d_out, ld_out, P);
+  EmobaseParams E;
+  std::memset(&E, 0, sizeof(E));
+  E.N40 = (int32_t)plan->geo40.N;
+  E.Nfft40 = (int32_t)plan->geo40.Nfft;
+  E.window40 = plan->d_window40.p;
+  E.oo40 = plan->oo40.tab();
+  E.fsSec40 = (float)plan->geo40.fft_frame_size_sec;      // the level's frameSizeSec: Tsamp = fsSec / Nfft (pitchACF.cpp:113-116, :151-153)
+  E.maxPitch = plan->cfg.pitch_max;
+  E.voicingCutoff = plan->cfg.voicing_cutoff;
+  if (E.voicingCutoff > 1.0) E.voicingCutoff = 1.0;       // pitchACF.cpp:96-98
+  if (E.voicingCutoff < 0.0) E.voicingCutoff = 0.0;
+  if (E.maxPitch < 0.0) E.maxPitch = 0.0;
+  // cIntensity::setupNamesForField (intensity.cpp:91-112): the Hamming window as doubles (smileUtil.c:1291-1303), summed in index order
+  {
+    const double NN = (double)plan->geo.N;
+    double sum = 0.0;
+    for (double i = 0.0; i < NN; i += 1.0) sum += 0.54 - 0.46 * std::cos((2.0 * M_PI * i) / (NN - 1.0));
+    if (sum <= 0.0) sum = 1.0;
+    E.w0 = 0.54 - 0.46 * std::cos((2.0 * M_PI * 0.0) / (NN - 1.0));
+    E.w1 = 0.54 - 0.46 * std::cos((2.0 * M_PI * 1.0) / (NN - 1.0));
+    E.win_sum = sum;
+  }
+  E.p = b->emo_p;
+  E.n25 = emobase::n25_cols(E.p);
+  E.W = plan->cfg.sma_win / 2;
+  E.raw25 = b->d_raw25.p;
+  E.raw3 = b->d_raw3.p;
+  E.row_off = b->d_row_off.p;
+  E.total_rows = b->total_rows;
+  int trc;
+  if ((trc = timing_mark(plan, 0, s))) return trc;
+  hipError_t e = launch_emobase(P, E, s);
+  if (e != hipSuccess) return fail(SMILEHIP_ERR_HIP, "emobase kernel launch failed: %s", hipGetErrorString(e));
+  if ((trc = timing_mark(plan, 1, s))) return trc;
+  return timing_mark(plan, 2, s);
+}
+
 // ComParE groups A+B: frame kernel -> RASTA scan -> group A (multi-length SMA+delta) + group B chain
 static int compare_run(smilehip_plan *plan, smilehip_batch *b, const int16_t *d_pcm, float *d_out, int64_t ld_out, void *stream,
                        int de_col = 59) {
@@ -984,6 +1048,17 @@ extern "C" int smilehip_batch_chroma_taps(smilehip_batch *b, float **d_tonespec,
   return SMILEHIP_OK;
 }
 
+// emobase chain tap: the per-frame scratch of the last run (a row per 25 ms frame in both)
+extern "C" int smilehip_batch_emobase_taps(smilehip_batch *b, float **d_raw25, float **d_raw3, int64_t *n_frames, int32_t *n25) {
+  if (!b || b->plan->cfg.chain_kind != SMILEHIP_CHAIN_EMOBASE)
+    return fail(SMILEHIP_ERR_INVALID, "smilehip_batch_emobase_taps: not an emobase chain batch");
+  if (d_raw25) *d_raw25 = b->d_raw25.p;
+  if (d_raw3) *d_raw3 = b->d_raw3.p;
+  if (n_frames) *n_frames = b->total_frames;
+  if (n25) *n25 = emobase::n25_cols(b->emo_p);
+  return SMILEHIP_OK;
+}
+
 // Test/diagnostic taps of the F0 chain: device pointers to the per-frame scratch of the LAST run
 // (candidates: total_frames x 21, level is13_pitchShsG60; energy: total_frames, level is13_e60) and an optional
 // destination for the octave-scaled spectra (total_frames x K, level is13_hpsG60; pass NULL to switch it off).
@@ -1063,6 +1138,7 @@ extern "C" int smilehip_lld_run(smilehip_plan *plan, smilehip_batch *b, const in
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE_F0) return f0_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_SHS) return prosody_shs_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_ACF) return prosody_acf_run(plan, b, d_pcm, d_out, ld_out, stream);
+  if (plan->cfg.chain_kind == SMILEHIP_CHAIN_EMOBASE) return emobase_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT) return chroma_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FILT) return chroma_filt_run(plan, b, d_pcm, d_out, ld_out, stream);
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_AUDSPEC) return audspec_run(plan, b, d_pcm, d_out, ld_out, stream);

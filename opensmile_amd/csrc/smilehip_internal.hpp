@@ -19,6 +19,7 @@
 #include "chroma_tables.hpp"
 #include "tonefilt_tables.hpp"
 #include "lld_audspec_ops.hpp"
+#include "lld_emobase_ops.hpp"
 #include "lld_spectrogram_ops.hpp"
 #include "lld_launch.hpp"
 #include "lld_ooura.hpp"
@@ -176,6 +177,12 @@ struct smilehip_plan {
   // chroma_filt chain: cTonefilt's per-note table (tonefilt_tables.hpp)
   TonefiltHost tonefilt;
   DevBuf<tonefilt::NoteTab> d_tf_tab;
+  // emobase chain: the 40 ms framer's geometry, window and transform beside the plan's own (the 25 ms framer), and cLpc's order
+  Geometry geo40;
+  std::vector<float> h_window40;
+  DevBuf<float> d_window40;
+  OouraDev oo40;
+  int32_t emo_lpc_order = 8;                // smilehip_plan_set_lpc_order
   // spectrogram chain: cFFTmagphase's form and its constants (smilehip_plan_set_spectrum_form; plain magnitude on a fresh plan)
   spectrogram::FormConsts spg_form{};
   // eGeMAPS chain: cSpecResample's tables (transposed), cSpectral's band-slope edges and frequency range
@@ -258,6 +265,8 @@ struct smilehip_batch {
   std::vector<int32_t> h_short;
   DevBuf<int64_t> d_samp_off, d_frame_off;
   DevBuf<float> d_tonespec;        // chroma_fft / chroma_filt chain: the level tonespec, [total_frames x n_notes]
+  DevBuf<float> d_raw25;           // emobase chain: [total_frames x (15 + p)] intens | mfcc1 | lsp | mzcr (d_raw3: the level pitch, a row per 25 ms frame)
+  int32_t emo_p = 0;               // emobase chain: cLpc's order the scratch was laid out for
   DevBuf<float> d_raw3;            // prosodyAcf chain: [total_frames x 3] voiceProb | pitch candidate -> contour | loudness
   DevBuf<int32_t> d_frame_utt;     // IS09 / prosodyAcf chain: utterance of every frame (the frame kernel has one frame per wave and would search frame_off for it)
   DevBuf<int32_t> d_tile_utt, d_tile_t0, d_short, d_dtile_utt, d_dtile_t0;

@@ -255,6 +255,19 @@ extern "C" void smilehip_config_spectrogram(smilehip_lld_config *c) {
   c->n_delta = 0;
 }
 
+// config/emobase/emobase.conf, levels lld and lld_de; every field lies in V1 (cLpc's order is the plan's: smilehip_plan_set_lpc_order)
+extern "C" void smilehip_config_emobase(smilehip_lld_config *c) {
+  smilehip_config_mfcc12_0_d_a(c);   // [fr25] 25 ms / 10 ms, [pe] k = 0.97, [win] ham, [fft] zeroPadSymmetric = 0, [mspec] 26 HTK power bands 0 .. 8000 Hz
+  c->chain_kind = SMILEHIP_CHAIN_EMOBASE;
+  c->first_mfcc = 1;                 // [mfcc:cMfcc] firstMfcc = 1, lastMfcc = 12, cepLifter = 22, htkcompatible
+  c->last_mfcc = 12;
+  c->n_delta = 1;                    // [delta1:cDeltaRegression] deltawin = 2
+  c->delta_win = 2;
+  c->pitch_max = 500.0;              // [pitchACF:cPitchACF] maxPitch = 500, voicingCutoff = 0.55
+  c->voicing_cutoff = 0.55;
+  c->sma_win = 3;                    // [lld:cContourSmoother] smaWin = 3
+}
+
 static inline bool is_compare_ab_like(const smilehip_lld_config &c) {
   return c.chain_kind == SMILEHIP_CHAIN_COMPARE_AB || c.chain_kind == SMILEHIP_CHAIN_COMPARE;
 }
@@ -352,6 +365,32 @@ static int build_tables(smilehip_plan *p, bool upload = true) {
     if (p->geo.Nfft < 64 || p->geo.Nfft > 8192)
       return fail(SMILEHIP_ERR_INVALID, "prosodyAcf chain: the transform length must be 64 .. 8192 points; frame_size_sec at this sample_rate gives %lld",
                   (long long)p->geo.Nfft);
+  } else if (p->cfg.chain_kind == SMILEHIP_CHAIN_EMOBASE) {
+    // everything the chain cannot express is refused with the parameter named
+    const smilehip_lld_config &c = p->cfg;
+    if (mask != SMILEHIP_STAGE_ALL) return fail(SMILEHIP_ERR_INVALID, "emobase chain: stage_mask must be all stages");
+    if (c.sma_win < 3 || !(c.sma_win & 1) || c.sma_win > 9)
+      return fail(SMILEHIP_ERR_INVALID, "emobase chain: sma_win (cContourSmoother smaWin) must be odd, 3 .. 9; got %d", c.sma_win);
+    if (c.n_delta != 1 || c.delta_win != emobase::kDeltaWin)
+      return fail(SMILEHIP_ERR_INVALID, "emobase chain: n_delta must be 1 and delta_win %d ([delta1:cDeltaRegression]); got %d / %d", emobase::kDeltaWin, c.n_delta, c.delta_win);
+    if (!c.preemph || c.preemph_de) return fail(SMILEHIP_ERR_INVALID, "emobase chain: preemph must be 1 and preemph_de 0 ([pe:cVectorPreemphasis])");
+    if (c.win_offset != 0.0) return fail(SMILEHIP_ERR_INVALID, "emobase chain: win_offset must be 0");
+    if (c.zero_pad_symmetric) return fail(SMILEHIP_ERR_INVALID, "emobase chain: zero_pad_symmetric must be 0 ([fft:cTransformFFT] zeroPadSymmetric = 0)");
+    if (c.append_log_energy) return fail(SMILEHIP_ERR_INVALID, "emobase chain: append_log_energy must be 0 (the file has no cEnergy)");
+    if (c.cms) return fail(SMILEHIP_ERR_INVALID, "emobase chain: cms must be 0 (the file has no cFullinputMean)");
+    if (p->dct.n_mfcc != 12) return fail(SMILEHIP_ERR_INVALID, "emobase chain: first_mfcc .. last_mfcc must give 12 coefficients; got %d", p->dct.n_mfcc);
+    if (p->mel.n_bands < 1 || p->mel.n_bands > 32) return fail(SMILEHIP_ERR_INVALID, "emobase chain: n_bands must be 1 .. 32; got %d", p->mel.n_bands);
+    if (c.frame_size_sec >= 0.040) return fail(SMILEHIP_ERR_INVALID, "emobase chain: frame_size_sec must lie below the second framer's 0.040 s; got %g", c.frame_size_sec);
+    if (p->geo.Nfft < 64 || p->geo.Nfft > 8192)
+      return fail(SMILEHIP_ERR_INVALID, "emobase chain: the transform length must be 64 .. 8192 points; frame_size_sec at this sample_rate gives %lld",
+                  (long long)p->geo.Nfft);
+    smilehip_lld_config c40 = c;                          // [fr40:cFramer] .. [fft40:cTransformFFT]: the same step, window and padding
+    c40.frame_size_sec = 0.040;
+    if ((rc = make_geometry(c40, p->geo40)) != SMILEHIP_OK) return fail(rc, "emobase chain: invalid framing parameters of the 40 ms framer");
+    if (p->geo40.Nfft < 64 || p->geo40.Nfft > 8192 || p->geo40.H != p->geo.H || p->geo40.N < p->geo.N)
+      return fail(SMILEHIP_ERR_INVALID, "emobase chain: the 40 ms framer gives a transform of %lld points (64 .. 8192 are built)", (long long)p->geo40.Nfft);
+    p->h_window40.assign(size_t(p->geo40.N), 1.0f);
+    if ((rc = make_window(c40, p->geo40.N, p->h_window40)) != SMILEHIP_OK) return fail(rc, "unknown window function %d", c.win_func);
   } else if (p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT) {
     // everything the chain cannot express is refused with the option named
     const smilehip_lld_config &c = p->cfg;
@@ -490,6 +529,7 @@ static int build_tables(smilehip_plan *p, bool upload = true) {
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT && ((rc = p->d_ts_fmap.upload(p->tonespec.filter_map)) || (rc = p->d_ts_rec.upload(p->tonespec.rec))))
     return rc;
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FILT && (rc = p->d_tf_tab.upload(p->tonefilt.tab))) return rc;
+  if (p->cfg.chain_kind == SMILEHIP_CHAIN_EMOBASE && ((rc = p->d_window40.upload(p->h_window40)) || (rc = p->oo40.build((int)p->geo40.Nfft, true)))) return rc;
   if (f0_front_chain(p->cfg.chain_kind) &&
       ((rc = p->d_f0_rec.upload(p->f0.sp_rec)) || (rc = p->d_f0_d1.upload(p->f0.sp_d1)) || (rc = p->d_f0_d2.upload(p->f0.sp_d2)) ||
        (rc = p->d_f0_co.upload(p->f0.ip_co)) || (rc = p->d_f0_audw.upload(p->f0.audw)) || (rc = p->d_f0_k.upload(p->f0.ip_k)) ||
@@ -794,7 +834,32 @@ extern "C" int smilehip_plan_get_spectrum_form(const smilehip_plan *plan, int32_
   return SMILEHIP_OK;
 }
 
+extern "C" int smilehip_plan_set_lpc_order(smilehip_plan *plan, int32_t p) {
+  if (!plan) return fail(SMILEHIP_ERR_INVALID, "smilehip_plan_set_lpc_order: null plan");
+  if (plan->cfg.chain_kind != SMILEHIP_CHAIN_EMOBASE)
+    return fail(SMILEHIP_ERR_INVALID, "smilehip_plan_set_lpc_order: not an emobase plan (chain_kind %d)", plan->cfg.chain_kind);
+  if (p < 2 || p > emobase::kMaxLpcOrder || (p & 1))
+    return fail(SMILEHIP_ERR_INVALID, "smilehip_plan_set_lpc_order: cLpc p must be even, 2 .. %d; got %d", emobase::kMaxLpcOrder, p);
+  plan->emo_lpc_order = p;
+  return SMILEHIP_OK;
+}
+extern "C" int smilehip_plan_get_lpc_order(const smilehip_plan *plan, int32_t *p) {
+  if (!plan || plan->cfg.chain_kind != SMILEHIP_CHAIN_EMOBASE)
+    return fail(SMILEHIP_ERR_INVALID, "smilehip_plan_get_lpc_order: not an emobase plan");
+  if (p) *p = plan->emo_lpc_order;
+  return SMILEHIP_OK;
+}
+
+extern "C" int smilehip_plan_emobase_frame40(const smilehip_plan *plan, int64_t *frame_size, int64_t *fft_size) {
+  if (!plan || plan->cfg.chain_kind != SMILEHIP_CHAIN_EMOBASE)
+    return fail(SMILEHIP_ERR_INVALID, "smilehip_plan_emobase_frame40: not an emobase plan");
+  if (frame_size) *frame_size = plan->geo40.N;
+  if (fft_size) *fft_size = plan->geo40.Nfft;
+  return SMILEHIP_OK;
+}
+
 int plan_n_static(const smilehip_plan *p) {
+  if (p->cfg.chain_kind == SMILEHIP_CHAIN_EMOBASE) return emobase::n_lld(p->emo_lpc_order);
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE_F0) return 2;
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_SHS || p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_ACF) return 3;
   if (p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT || p->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FILT) return p->cfg.chroma_octave_size;
@@ -808,7 +873,7 @@ int plan_n_static(const smilehip_plan *p) {
 int plan_n_out(const smilehip_plan *p) { return plan_n_static(p) * (1 + p->cfg.n_delta); }
 int plan_row_extra(const smilehip_plan *p) {
   return (p->cfg.chain_kind == SMILEHIP_CHAIN_IS09 || p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_SHS ||
-          p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_ACF) ? p->cfg.sma_win / 2 : 0;
+          p->cfg.chain_kind == SMILEHIP_CHAIN_PROSODY_ACF || p->cfg.chain_kind == SMILEHIP_CHAIN_EMOBASE) ? p->cfg.sma_win / 2 : 0;
 }
 
 extern "C" int smilehip_plan_geometry(const smilehip_plan *p, smilehip_geometry *g) {
@@ -845,6 +910,8 @@ extern "C" double smilehip_row_time(const smilehip_plan *plan, int64_t n_frames,
   // spectrogram: as measured on the binary's CSV sink, row t carries the time of its first sample, t * H / sample_rate -- t * frameStep
   // where frameStep is a whole number of samples, 0.009977 t at 11.025 kHz and 0.010023 t at 22.05 kHz (the HTK header keeps frameStep)
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_SPECTROGRAM) return double(row * plan->geo.H) / plan->cfg.sample_rate;
+  // emobase (lld_emobase_ops.hpp: row_time_frame; n_frames = the utterance's 25 ms frames): the left-padding rows carry their own index
+  if (plan->cfg.chain_kind == SMILEHIP_CHAIN_EMOBASE) return smilehip_frame_time(plan, emobase::row_time_frame(n_frames, 0, plan->cfg.sma_win / 2, row));
   if (plan->cfg.chain_kind == SMILEHIP_CHAIN_MFCC || plan->cfg.chain_kind == SMILEHIP_CHAIN_PLP || plan->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FFT ||
       plan->cfg.chain_kind == SMILEHIP_CHAIN_CHROMA_FILT || plan->cfg.chain_kind == SMILEHIP_CHAIN_AUDSPEC ||
       plan->cfg.chain_kind == SMILEHIP_CHAIN_COMPARE_F0 || plan->cfg.chain_kind == SMILEHIP_CHAIN_EGEMAPS || n_frames <= 1)

@@ -1135,6 +1135,260 @@ bool conf_to_chroma_filt(const ConfFile &f, ConfPlan &p, std::string &err) {
   return true;
 }
 
+// ---- smilextract_hip --set emobase -C file: config/emobase/emobase.conf, levels lld and lld_de, possibly with other values of the
+// options the chain takes as parameters (cPitchACF maxPitch, voicingCutoff; cContourSmoother smaWin; cLpc p). Walked like
+// prosodyAcf.conf above: every other option has the one value SMILEHIP_CHAIN_EMOBASE implements or is refused by name. The
+// cFunctionals instance behind the two levels is passed over (its level is not built: a sink on it is refused by conf_check_io).
+// fingerprint of the reference's own file with its includes and every command-line option at its default (--fingerprint prints it)
+static const uint64_t kEmobaseFingerprint = 0xbb4eb6d6855829baull;
+bool conf_to_emobase(const ConfFile &f, ConfPlan &p, std::string &err) {
+  p = ConfPlan();
+  const char *graph = "not the graph of emobase.conf";
+  static const std::map<std::string, int> count_of = {{"cFramer", 2}, {"cWindower", 2}, {"cTransformFFT", 2}, {"cFFTmagphase", 2}, {"cAcf", 2},
+      {"cPitchACF", 1}, {"cVectorPreemphasis", 1}, {"cMelspec", 1}, {"cMfcc", 1}, {"cLpc", 1}, {"cLsp", 1}, {"cMZcr", 1}, {"cIntensity", 1},
+      {"cContourSmoother", 1}, {"cDeltaRegression", 1}, {"cFunctionals", 1}};
+  std::map<std::string, std::vector<const ConfInstance *>> by_type;
+  for (const ConfInstance &i : f.inst) {
+    if (is_io_type(i.type)) continue;
+    if (!count_of.count(i.type)) { err = "component [" + i.name + ":" + i.type + "] is not part of the graph of emobase.conf"; return false; }
+    by_type[i.type].push_back(&i);
+  }
+  for (const auto &kv : count_of) {
+    const size_t n = by_type.count(kv.first) ? by_type[kv.first].size() : 0;
+    if (kv.first == "cFunctionals" ? n > 1 : n != (size_t)kv.second) {
+      err = "the graph has " + std::to_string(n) + " " + kv.first + " instance(s), emobase.conf has " + std::to_string(kv.second) + ": " + graph;
+      return false;
+    }
+  }
+  auto lvl = [](const ConfInstance *i, const char *k) { const std::string *v = i->find(k); return v ? *v : std::string(); };
+  auto wired = [&](const ConfInstance *i, const std::string &want) {
+    if (lvl(i, "reader.dmLevel") == want) return true;
+    err = "[" + i->name + ":" + i->type + "] reader.dmLevel = '" + lvl(i, "reader.dmLevel") + "', expected '" + want + "' (not the wiring of emobase.conf)";
+    return false;
+  };
+  auto must_be = [](OptReader &o, const char *key, const char *want, const char *dflt) {
+    const std::string v = o.str(key, dflt);
+    if (lower(v) != lower(want) && o.err.empty())
+      o.err = "[" + o.ci.name + ":" + o.ci.type + "] " + key + " = " + v + " is not expressible on the fused path (needs " + want + ")";
+  };
+  auto reads = [&](const char *type, const std::string &level) -> const ConfInstance * {   // the instance of `type` that reads `level`
+    for (const ConfInstance *i : by_type[type]) if (lvl(i, "reader.dmLevel") == level) return i;
+    return nullptr;
+  };
+  auto missing = [&](const char *type, const std::string &level) {
+    err = std::string("no ") + type + " reads level '" + level + "' (not the wiring of emobase.conf)";
+    return false;
+  };
+  // the two framers on `wave`, told apart by their frame size
+  const ConfInstance *fr25 = nullptr, *fr40 = nullptr;
+  for (const ConfInstance *fr : by_type["cFramer"]) {    // src/core/winToVecProcessor.cpp:51-83
+    OptReader o(*fr);
+    if (!wired(fr, "wave")) return false;
+    const double fsz = o.num("frameSize", 0.025);
+    if (fsz == 0.025 && !fr25) fr25 = fr;
+    else if (fsz == 0.04 && !fr40) fr40 = fr;
+    else if (o.err.empty())
+      o.err = "[" + fr->name + ":cFramer] frameSize = " + canonical_value(std::to_string(fsz)) + " is not expressible on the fused path (needs 0.025 and 0.04, one framer each)";
+    o.require("frameStep", 0.01, 0.0);
+    must_be(o, "frameMode", "fixed", "fixed"); must_be(o, "frameCenterSpecial", "left", "left");
+    o.require("noPostEOIprocessing", 1, 1); o.require("frameSizeFrames", 0, 0); o.require("frameStepFrames", 0, 0);
+    o.require("frameCenter", 0, 0); o.require("frameCenterFrames", 0, 0); o.require("allowLastFrameIncomplete", 0, 0);
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  const std::string frames25 = lvl(fr25, "writer.dmLevel"), frames40 = lvl(fr40, "writer.dmLevel");
+  auto window_chain = [&](const std::string &in, const ConfInstance *&mag_out) {   // cWindower -> cTransformFFT -> cFFTmagphase behind level `in`
+    const ConfInstance *win = reads("cWindower", in);
+    if (!win) return missing("cWindower", in);
+    {                                                     // src/dspcore/windower.cpp:36-49
+      OptReader o(*win);
+      const std::string wf = o.str("winFunc", "Han");
+      if (win_func_of(wf) != SMILEHIP_WIN_HAMM) o.err = "[" + win->name + ":cWindower] winFunc = " + wf + " is not expressible on the fused path (needs ham)";
+      o.require("gain", 1, 1); o.require("offset", 0, 0); o.require("fade", 0, 0); o.require("squareRoot", 0, 0); o.require("xshift", 0, 0);
+      o.require("processArrayFields", 1, 1);
+      o.num("sigma", 0.4); o.num("alpha", 0.16); o.num("alpha0", 0); o.num("alpha1", 0); o.num("alpha2", 0); o.num("alpha3", 0);   // (not read by ham)
+      if (!o.finish(kBenign)) { err = o.err; return false; }
+    }
+    const ConfInstance *fft = reads("cTransformFFT", lvl(win, "writer.dmLevel"));
+    if (!fft) return missing("cTransformFFT", lvl(win, "writer.dmLevel"));
+    {                                                     // src/dspcore/transformFft.cpp:34-35
+      OptReader o(*fft);
+      o.require("inverse", 0, 0); o.require("zeroPadSymmetric", 0, 1); o.require("processArrayFields", 1, 1);
+      if (!o.finish(kBenign)) { err = o.err; return false; }
+    }
+    const ConfInstance *mag = reads("cFFTmagphase", lvl(fft, "writer.dmLevel"));
+    if (!mag) return missing("cFFTmagphase", lvl(fft, "writer.dmLevel"));
+    {                                                     // src/dspcore/fftmagphase.cpp:39-49
+      OptReader o(*mag);
+      o.require("inverse", 0, 0); o.require("magnitude", 1, 1); o.require("phase", 0, 0); o.require("joinMagphase", 0, 0);
+      o.require("normalise", 0, 0); o.require("power", 0, 0); o.require("dBpsd", 0, 0); o.require("processArrayFields", 1, 1);
+      if (!o.finish(kBenign)) { err = o.err; return false; }
+    }
+    mag_out = mag;
+    return true;
+  };
+  // ---- 40 ms: window, transform, magnitudes, two cAcf, cPitchACF
+  const ConfInstance *mag40 = nullptr;
+  if (!window_chain(frames40, mag40)) return false;
+  const ConfInstance *pit = by_type["cPitchACF"][0];
+  const std::vector<std::string> pin = split_levels(lvl(pit, "reader.dmLevel"));
+  const ConfInstance *acf = nullptr, *cep = nullptr;
+  if (pin.size() == 2)
+    for (const ConfInstance *a : by_type["cAcf"]) {
+      if (lvl(a, "writer.dmLevel") == pin[0] && !acf) acf = a;
+      else if (lvl(a, "writer.dmLevel") == pin[1] && !cep) cep = a;
+    }
+  if (!acf || !cep) {
+    err = "[" + pit->name + ":cPitchACF] reader.dmLevel = '" + lvl(pit, "reader.dmLevel") + "', expected the levels of the two cAcf instances, ACF first (not the wiring of emobase.conf)";
+    return false;
+  }
+  for (const ConfInstance *a : {acf, cep}) {              // src/dspcore/acf.cpp:46-55, :91-108
+    const bool c = a == cep;
+    OptReader o(*a);
+    if (!wired(a, lvl(mag40, "writer.dmLevel"))) return false;
+    o.require("cepstrum", c ? 1 : 0, 0); o.require("usePower", 1, c ? 0 : 1); o.require("inverse", 0, 0);
+    o.require("cosLifterCepstrum", 0, 0); o.require("expBeforeAbs", 1, 1); o.require("symmetricData", 1, 1);
+    o.require("oldCompatCepstrum", c ? 1 : 0, 0);
+    if (c) { o.num("acfCepsNormOutput", 0); o.num("absCepstrum", 1); }   // (oldCompatCepstrum forces absCepstrum = 1 and acfCepsNormOutput = 0, acf.cpp:103-108)
+    else { o.require("acfCepsNormOutput", 0, 1); o.num("absCepstrum", 0); }   // (absCepstrum: not read without cepstrum)
+    o.require("processArrayFields", 1, 1);
+    o.str("nameAppend", "acf");                           // (cPitchACF names its outputs itself)
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  {                                                       // src/lldcore/pitchACF.cpp:38-49, :96-103
+    OptReader o(*pit);
+    double mp = o.num("maxPitch", 500.0), vc = o.num("voicingCutoff", 0.55);
+    if (vc > 1.0) vc = 1.0;
+    if (vc < 0.0) vc = 0.0;
+    if (mp < 0.0) mp = 0.0;
+    p.f0_params["pitch_max"] = mp;
+    p.f0_params["voicing_cutoff"] = vc;
+    o.require("voiceProb", 1, 1); o.require("F0", 1, 0); o.require("F0raw", 0, 0); o.require("F0env", 1, 0); o.require("voiceQual", 0, 0);
+    o.require("HNR", 0, 0); o.require("HNRdB", 0, 0); o.require("linHNR", 0, 0); o.require("processArrayFields", 0, 0);
+    if (o.has("nameAppend") && !o.str("nameAppend", "").empty()) o.err = "[" + pit->name + ":cPitchACF] nameAppend is not expressible on the fused path (needs none)";
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  // ---- 25 ms: cIntensity and cMZcr on the frames, cVectorPreemphasis, then cLpc -> cLsp and window .. cMelspec -> cMfcc
+  const ConfInstance *in = by_type["cIntensity"][0], *zc = by_type["cMZcr"][0], *pe = by_type["cVectorPreemphasis"][0], *lpc = by_type["cLpc"][0],
+                     *lsp = by_type["cLsp"][0], *mel = by_type["cMelspec"][0], *mfcc = by_type["cMfcc"][0], *smo = by_type["cContourSmoother"][0],
+                     *del = by_type["cDeltaRegression"][0];
+  {                                                       // src/lldcore/intensity.cpp:36-38
+    OptReader o(*in);
+    if (!wired(in, frames25)) return false;
+    o.require("intensity", 1, 1); o.require("loudness", 1, 0); o.require("processArrayFields", 1, 1);
+    if (o.has("nameAppend") && !o.str("nameAppend", "").empty()) o.err = "[" + in->name + ":cIntensity] nameAppend is not expressible on the fused path (needs none)";
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  {                                                       // src/lldcore/mzcr.cpp:36-42
+    OptReader o(*zc);
+    if (!wired(zc, frames25)) return false;
+    o.require("zcr", 1, 1); o.require("mcr", 0, 1); o.require("amax", 0, 1); o.require("maxmin", 0, 1); o.require("dc", 0, 0); o.require("processArrayFields", 1, 1);
+    if (o.has("nameAppend") && !o.str("nameAppend", "").empty()) o.err = "[" + zc->name + ":cMZcr] nameAppend is not expressible on the fused path (needs none)";
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  {                                                       // src/dspcore/vectorPreemphasis.cpp:38-41
+    OptReader o(*pe);
+    if (!wired(pe, frames25)) return false;
+    const double k = o.num("k", 0.97);
+    if ((float)k != 0.97f && o.err.empty()) o.err = "[" + pe->name + ":cVectorPreemphasis] k = " + canonical_value(std::to_string(k)) + " is not expressible on the fused path (needs 0.97)";
+    o.require("de", 0, 0); o.require("f", 0, 0); o.require("processArrayFields", 1, 1);
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  const std::string framespe = lvl(pe, "writer.dmLevel");
+  {                                                       // src/lld/lpc.cpp:45-58
+    OptReader o(*lpc);
+    if (!wired(lpc, framespe)) return false;
+    must_be(o, "method", "acf", "acf");
+    const double order = o.num("p", 8);
+    if ((order < 2 || order > 16 || order != std::floor(order) || ((int)order & 1)) && o.err.empty())
+      o.err = "[" + lpc->name + ":cLpc] p = " + canonical_value(std::to_string(order)) + " is not expressible on the fused path (needs an even number, 2 .. 16)";
+    p.f0_params["lpc_order"] = order;
+    o.require("saveLPCoeff", 1, 1); o.require("lpGain", 0, 0); o.require("saveRefCoeff", 0, 0); o.require("residual", 0, 0);
+    o.require("residualGainScale", 0, 0); o.require("forwardFilter", 0, 0); o.require("lpSpectrum", 0, 0); o.require("forwardLPspec", 1, 1);
+    o.require("processArrayFields", 1, 1);
+    o.num("lpSpecDeltaF", 10); o.num("lpSpecBins", 100);  // (read with lpSpectrum alone)
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  {                                                       // src/lld/lsp.cpp:43-47
+    OptReader o(*lsp);
+    if (!wired(lsp, lvl(lpc, "writer.dmLevel"))) return false;
+    o.require("processArrayFields", 0, 0);
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  const ConfInstance *mag25 = nullptr;
+  if (!window_chain(framespe, mag25)) return false;
+  {                                                       // src/lldcore/melspec.cpp:40-53
+    OptReader o(*mel);
+    if (!wired(mel, lvl(mag25, "writer.dmLevel"))) return false;
+    o.require("nBands", 26, 26); o.require("lofreq", 0, 20); o.require("hifreq", 8000, 8000); o.require("usePower", 1, 0);
+    o.require("htkcompatible", 1, 1); o.require("inverse", 0, 0); o.require("showFbank", 0, 0); o.require("processArrayFields", 1, 1);
+    must_be(o, "specScale", "mel", "mel");
+    o.num("bwMethod", 0); o.num("logScaleBase", 2); o.num("firstNote", 27.5); o.num("halfBwTarg", 0);   // (not read on the mel scale)
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  {                                                       // src/lldcore/mfcc.cpp:40-48
+    OptReader o(*mfcc);
+    if (!wired(mfcc, lvl(mel, "writer.dmLevel"))) return false;
+    o.require("firstMfcc", 1, 1); o.require("lastMfcc", 12, 12); o.require("cepLifter", 22, 22); o.require("htkcompatible", 1, 1);
+    o.require("nMfcc", 12, 12); o.require("melfloor", 1e-8, 1e-8); o.require("doLog", 1, 1); o.require("inverse", 0, 0);
+    o.require("processArrayFields", 1, 1);
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  {                                                       // src/dspcore/contourSmoother.cpp:33-36, src/core/windowProcessor.cpp:39
+    OptReader o(*smo);
+    if (!wired(smo, lvl(in, "writer.dmLevel") + ";" + lvl(mfcc, "writer.dmLevel") + ";" + lvl(lsp, "writer.dmLevel") + ";" + lvl(zc, "writer.dmLevel") + ";" +
+                        lvl(pit, "writer.dmLevel")))
+      return false;
+    const double w = o.num("smaWin", 3);
+    if ((w < 3 || w > 9 || w != std::floor(w) || !((int)w & 1)) && o.err.empty())
+      o.err = "[" + smo->name + ":cContourSmoother] smaWin = " + canonical_value(std::to_string(w)) + " is not expressible on the fused path (needs an odd number, 3 .. 9)";
+    p.f0_params["sma_win"] = w;
+    o.require("noZeroSma", 0, 0); o.require("noPostEOIprocessing", 0, 0);
+    must_be(o, "nameAppend", "sma", "sma");
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  if (lvl(smo, "writer.dmLevel") != "lld") {
+    err = "[" + smo->name + ":cContourSmoother] writer.dmLevel = '" + lvl(smo, "writer.dmLevel") + "', expected 'lld' (the level the shared output file's sinks read)";
+    return false;
+  }
+  {                                                       // src/dspcore/deltaRegression.cpp:38-44
+    OptReader o(*del);
+    if (!wired(del, "lld")) return false;
+    o.require("deltawin", 2, 2); o.require("absOutput", 0, 0); o.require("halfWaveRect", 0, 0); o.require("onlyInSegments", 0, 0);
+    o.require("zeroSegBound", 1, 1); o.require("relativeDelta", 0, 0); o.require("noPostEOIprocessing", 0, 0);
+    must_be(o, "nameAppend", "de", "de");
+    if (!o.finish(kBenign)) { err = o.err; return false; }
+  }
+  if (lvl(del, "writer.dmLevel") != "lld_de") {
+    err = "[" + del->name + ":cDeltaRegression] writer.dmLevel = '" + lvl(del, "writer.dmLevel") + "', expected 'lld_de' (the level the shared output file's sinks read)";
+    return false;
+  }
+  for (const ConfInstance &i : f.inst) {                   // an active sink on the functionals level: said by its name
+    const std::string *fn = i.find("filename");
+    const bool sink = i.type.size() > 4 && i.type.compare(i.type.size() - 4, 4, "Sink") == 0;
+    if (sink && fn && *fn != "?" && lvl(&i, "reader.dmLevel") == "func") {
+      err = "[" + i.name + ":" + i.type + "] is active (filename = " + *fn + "): the functionals level of emobase.conf is not built yet (the levels lld and lld_de are: -lldcsvoutput, -lldhtkoutput)";
+      return false;
+    }
+  }
+  if (!conf_check_io(f, {"lld", "lld_de"}, err)) return false;
+  p.preset = "emobase";
+  for (const ConfInstance &i : f.inst)
+    if (i.type == "cWaveSource") { const std::string *fn = i.find("filename"); if (fn) p.wave_file = *fn; }
+  if (conf_fingerprint(f) == kEmobaseFingerprint) {        // the shipped file: the preset as it is
+    p.f0_params.clear();
+    p.describe = "the graph of emobase.conf, levels lld and lld_de (every processing component and option identical)";
+    return true;
+  }
+  std::string what;
+  for (const auto &kv : p.f0_params) {
+    char buf[64];
+    snprintf(buf, sizeof(buf), "%s%s = %.9g", what.empty() ? "" : ", ", kv.first.c_str(), kv.second);
+    what += buf;
+  }
+  p.describe = "the graph of emobase.conf, levels lld and lld_de, with the file's own parameter values (" + what + ")";
+  return true;
+}
+
 static bool conf_to_plan_inner(const ConfFile &f, ConfPlan &p, std::string &err, bool audspec_set);
 static bool conf_to_plan_any(const ConfFile &f, ConfPlan &p, std::string &err, bool audspec_set) {
   const bool ok = conf_to_plan_inner(f, p, err, audspec_set);

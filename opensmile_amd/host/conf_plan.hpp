@@ -100,6 +100,9 @@ bool conf_to_prosody_shs(const ConfFile &f, ConfPlan &p, std::string &err);
 // smilextract_hip --set prosody_acf -C file: the same for config/prosody/prosodyAcf.conf; preset = "prosody_acf", f0_params holds
 // cPitchACF maxPitch and voicingCutoff (clamped as pitchACF.cpp:96-103 does) and cContourSmoother smaWin: pitch_max, voicing_cutoff, sma_win
 bool conf_to_prosody_acf(const ConfFile &f, ConfPlan &p, std::string &err);
+// smilextract_hip --set emobase -C file: the same for config/emobase/emobase.conf, levels lld and lld_de; preset = "emobase", f0_params
+// holds cPitchACF maxPitch and voicingCutoff (clamped), cContourSmoother smaWin and cLpc p: pitch_max, voicing_cutoff, sma_win, lpc_order
+bool conf_to_emobase(const ConfFile &f, ConfPlan &p, std::string &err);
 // smilextract_hip --set chroma_fft -C file: the same for config/chroma/chroma_fft.conf; preset = "chroma_fft", f0_params holds cTonespec
 // nOctaves, firstNote, filterType (as SMILEHIP_TONESPEC_*), usePower, dbA and cChroma octaveSize, silThresh under the config struct's
 // field names (tonespec_n_octaves .. chroma_sil_thresh)

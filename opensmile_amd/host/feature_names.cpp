@@ -64,6 +64,19 @@ std::vector<std::string> lld_names_spectrogram(const std::string &field, int n_b
   for (int k = 0; k < n_bins; ++k) n.push_back(field + "[" + std::to_string(k) + "]");
   return n;
 }
+// config/emobase/emobase.conf, levels lld;lld_de as the binary's CSV header has them (tests/golden/emobase_synth.npz: csv_header): the
+// smoother's five input levels in the order it reads them, each with nameAppend = sma, then the same with cDeltaRegression's _de
+std::vector<std::string> lld_names_emobase(int lpc_order) {
+  // (field name, index suffix): the appended names go between them -- mfcc_sma[1], lspFreq_sma_de[0]
+  std::vector<std::pair<std::string, std::string>> base = {{"pcm_intensity", ""}, {"pcm_loudness", ""}};
+  for (int i = 1; i <= 12; ++i) base.push_back({"mfcc", "[" + std::to_string(i) + "]"});
+  for (int i = 0; i < lpc_order; ++i) base.push_back({"lspFreq", "[" + std::to_string(i) + "]"});
+  for (const char *s : {"pcm_zcr", "voiceProb", "F0", "F0env"}) base.push_back({s, ""});
+  std::vector<std::string> n;
+  for (const auto &b : base) n.push_back(b.first + "_sma" + b.second);
+  for (const auto &b : base) n.push_back(b.first + "_sma_de" + b.second);
+  return n;
+}
 std::vector<std::string> lld_names_prosody_shs() { return {"F0final_sma", "voicingFinalUnclipped_sma", "pcm_loudness_sma"}; }
 
 std::vector<std::string> lld_names_is09() {

@@ -42,6 +42,7 @@ std::vector<std::string> lld_names_plp_0_d_a();
 std::vector<std::string> lld_names_htk_variant(bool plp, bool energy);   // MFCC12_{0,E}_D_A[_Z], PLP_{0,E}_D_A[_Z]
 std::vector<std::string> lld_names_is09();
 std::vector<std::string> lld_names_prosody_shs();   // prosodyShs.conf: F0final_sma, voicingFinalUnclipped_sma, pcm_loudness_sma
+std::vector<std::string> lld_names_emobase(int lpc_order);   // emobase.conf, lld;lld_de: 2 (18 + p) names
 std::vector<std::string> lld_names_prosody_acf();   // prosodyAcf.conf: voiceProb_sma, F0_sma, pcm_loudness_sma
 std::vector<std::string> lld_names_audspec(int n_bands = 26, int n_delta = 2, const std::string &delta_suffix = "de");   // audspec.conf: audSpec[i], audSpec_de[i], audSpec_de_de[i]
 std::vector<std::string> lld_names_spectrogram(const std::string &field = "pcm_fftMag", int n_bins = 257);   // spectrogram.conf: <field>[0 .. K - 1], the field named after cFFTmagphase's form

@@ -42,6 +42,9 @@
 //                                       -dB are the file's own options, i.e. the framer's. With -C: that file's (edited) frameSize, frameStep,
 //                                       window, zeroPadSymmetric and cFFTmagphase normalise / power / dBpsd / dBpnorm / mindBp; magnitude = 0,
 //                                       phase, joinMagphase, inverse and any other edit are refused by name (plain -C names this route)
+//   smilextract_hip --set emobase       config/emobase/emobase.conf, levels lld and lld_de: 52 columns through -lldcsvoutput / -lldhtkoutput
+//                   [-C emobase.conf]   (parmKind 9); the functionals level is not built: -O, -csvoutput and -htkoutput are refused. With -C:
+//                                       that file's (edited) maxPitch, voicingCutoff, smaWin and cLpc p; anything else is refused by name
 //   smilextract_hip --set gemapsv01a | egemapsv01a   the v01a files: the same columns, zeroPadSymmetric = 0, useBrokenJitterThresh = 1, maxF = 5500
 //   smilextract_hip --set gemapsv01b | egemapsv01b   config/gemaps/v01b/GeMAPSv01b.conf (18 LLDs, 62 functionals) / config/egemaps/v01b/
 //                                       eGeMAPSv01b.conf (23, 88): sub-graphs of eGeMAPSv02.conf, written as column subsets of its levels
@@ -182,9 +185,10 @@ static int run_main(int argc, char **argv, Persist *ps) {
     const bool set_filt = opt.count("--set") && opt["--set"] == "chroma_filt";
     const bool set_aud = opt.count("--set") && (opt["--set"] == "audspec" || opt["--set"] == "audspec_compat");
     const bool set_spg = opt.count("--set") && opt["--set"] == "spectrogram";
-    const bool set_with_conf = opt.count("--set") && (opt["--set"] == "prosody_shs" || set_acf || set_chroma || set_filt || set_aud || set_spg);
+    const bool set_emo = opt.count("--set") && opt["--set"] == "emobase";
+    const bool set_with_conf = opt.count("--set") && (opt["--set"] == "prosody_shs" || set_acf || set_chroma || set_filt || set_aud || set_spg || set_emo);
     if (opt.count("--set") && !set_with_conf)
-      die("-C and --set exclude each other (except --set prosody_shs -C prosodyShs.conf, --set prosody_acf -C prosodyAcf.conf, --set chroma_fft -C chroma_fft.conf, --set chroma_filt -C chroma_filt.conf, --set audspec -C audspec.conf and --set spectrogram -C spectrogram.conf)");
+      die("-C and --set exclude each other (except --set prosody_shs -C prosodyShs.conf, --set prosody_acf -C prosodyAcf.conf, --set chroma_fft -C chroma_fft.conf, --set chroma_filt -C chroma_filt.conf, --set audspec -C audspec.conf, --set spectrogram -C spectrogram.conf and --set emobase -C emobase.conf)");
     ConfFile cf;
     std::string cerr_;
     if (!conf_parse(opt["-C"], conf_cmdline, cf, cerr_)) die("-C " + opt["-C"] + ": " + cerr_);
@@ -229,7 +233,8 @@ static int run_main(int argc, char **argv, Persist *ps) {
           opt[o.second] = dflt->second;
       }
     }
-    if (!(set_spg    ? conf_to_spectrogram(cf, conf_plan, cerr_)
+    if (!(set_emo    ? conf_to_emobase(cf, conf_plan, cerr_)
+          : set_spg  ? conf_to_spectrogram(cf, conf_plan, cerr_)
           : set_aud  ? conf_to_audspec(cf, conf_plan, cerr_)
           : set_filt ? conf_to_chroma_filt(cf, conf_plan, cerr_)
           : set_chroma ? conf_to_chroma_fft(cf, conf_plan, cerr_)
@@ -241,6 +246,8 @@ static int run_main(int argc, char **argv, Persist *ps) {
       const bool hint_acf = !set_with_conf && !hint && conf_to_prosody_acf(cf, as_set, e2);
       const bool hint_chroma = !set_with_conf && !hint && !hint_acf && conf_to_chroma_fft(cf, as_set, e2);
       const bool hint_filt = !set_with_conf && !hint && !hint_acf && !hint_chroma && conf_to_chroma_filt(cf, as_set, e2);
+      if (!set_with_conf && !hint && !hint_acf && !hint_chroma && !hint_filt && conf_to_emobase(cf, as_set, e2))
+        die("-C " + opt["-C"] + " cannot run on the fused path: " + cerr_ + " -- the levels lld and lld_de of this file run as --set emobase -C <file>");
       if (hint_filt) die("-C " + opt["-C"] + " cannot run on the fused path: " + cerr_ + " -- this file runs as --set chroma_filt -C <file>");
       if (!set_with_conf && !hint && !hint_acf && !hint_chroma && conf_to_spectrogram(cf, as_set, e2))
         die("-C " + opt["-C"] + " cannot run on the fused path: " + cerr_ + " -- this file runs as --set spectrogram -C <file>");
@@ -346,6 +353,16 @@ static int run_main(int argc, char **argv, Persist *ps) {
   else if (prosody) smilehip_config_prosody_shs(&vcfg);
   // config/audspec/audspec.conf and audspec_compat.conf: LLD-only sets through standard_data_output_lldonly, like the cepstral files
   const bool audspec = set == "audspec" || set == "audspec_compat";
+  // config/emobase/emobase.conf: the levels lld and lld_de through the file's own lldsink / lldhtksink; no functionals level yet
+  const bool emobase = set == "emobase";
+  int emobase_p = 8;                                       // cLpc's order: the plan's (smilehip_plan_set_lpc_order)
+  if (emobase) {
+    smilehip_config_emobase(&vcfg);
+    if (with_conf && conf_plan.f0_params.count("lpc_order")) emobase_p = (int)conf_plan.f0_params.at("lpc_order");
+    for (const char *o : {"-O", "-csvoutput", "-htkoutput"})
+      if (opt.count(o) && opt[o] != "?")
+        die(std::string(o) + ": the functionals level of emobase.conf is not built yet (--set emobase writes the levels lld and lld_de: -lldcsvoutput, -lldhtkoutput)");
+  }
   if (audspec) { if (set == "audspec") smilehip_config_audspec(&vcfg); else smilehip_config_audspec_compat(&vcfg); }
   int spectrum_flags = SMILEHIP_MAGPHASE_MAGNITUDE;
   float spectrum_dbp_norm = (float)90.302, spectrum_min_dbp = (float)-102.0;
@@ -375,10 +392,10 @@ static int run_main(int argc, char **argv, Persist *ps) {
     return 0;
   }
   const std::string spectrum_field = spectrum_field_name(spectrum_flags);
-  const bool htk_variant = free_chain || prosody || audspec || spectrogram || (!is09 && !cmp16 && !egm && smilehip_config_htk_variant(&vcfg, variant.c_str()) == SMILEHIP_OK);
+  const bool htk_variant = free_chain || prosody || audspec || spectrogram || emobase || (!is09 && !cmp16 && !egm && smilehip_config_htk_variant(&vcfg, variant.c_str()) == SMILEHIP_OK);
   const bool plp = htk_variant && vcfg.chain_kind == SMILEHIP_CHAIN_PLP;
   if (!is09 && !cmp16 && !egm && !htk_variant)
-    die("--set must be mfcc12_{0,e}_d_a[_z], plp_{0,e}_d_a[_z], is09_emotion, compare16, compare16_lld, is13_compare, egemapsv02, gemapsv01b, egemapsv01b, gemapsv01a, egemapsv01a, prosody_shs, prosody_acf, chroma_fft, chroma_filt, spectrogram, audspec or audspec_compat (or use -C file.conf)");
+    die("--set must be mfcc12_{0,e}_d_a[_z], plp_{0,e}_d_a[_z], is09_emotion, compare16, compare16_lld, is13_compare, egemapsv02, gemapsv01b, egemapsv01b, gemapsv01a, egemapsv01a, prosody_shs, prosody_acf, chroma_fft, chroma_filt, spectrogram, emobase, audspec or audspec_compat (or use -C file.conf)");
   // parmKind of the files' own cHtkSink sections (the _Z files); the others write through standard_data_output_lldonly (9)
   int parm_kind = 9;
   if (variant == "MFCC12_0_D_A_Z") parm_kind = 11014;
@@ -386,7 +403,7 @@ static int run_main(int argc, char **argv, Persist *ps) {
   else if (variant == "PLP_0_D_A_Z") parm_kind = 11019;
   else if (variant == "PLP_E_D_A_Z") parm_kind = 8971;
   if (free_chain) parm_kind = conf_plan.parm_kind;
-  const bool lld_opts = is09 || cmp16 || egm;           // LLD files through -lldhtkoutput / -lldcsvoutput as in the reference
+  const bool lld_opts = is09 || cmp16 || egm || emobase;   // LLD files through -lldhtkoutput / -lldcsvoutput as in the reference
   std::string instname = opt.count("-instname") ? opt["-instname"] : (opt.count("-N") ? opt["-N"] : "unknown");
 
   std::vector<Job> jobs;
@@ -552,6 +569,7 @@ static int run_main(int argc, char **argv, Persist *ps) {
   const std::vector<std::string> lld_names =
       free_chain ? conf_plan.lld_names
                  : chroma ? lld_names_chroma_fft(vcfg.chroma_octave_size)
+                 : emobase ? lld_names_emobase(emobase_p)
                  : prosody_acf ? lld_names_prosody_acf()
                  : prosody ? lld_names_prosody_shs()
                  : audspec ? lld_names_audspec(vcfg.n_bands, vcfg.n_delta)
@@ -716,6 +734,7 @@ static int run_main(int argc, char **argv, Persist *ps) {
       if (with_conf) conf_apply_f0_params(conf_plan, cfg);     // an edited big-set file: its own pitch range, harmonics, buffer ...
       cfg.sample_rate = (double)rate;
       check(smilehip_plan_create(ctx, &cfg, &plan), "smilehip_plan_create");
+      if (emobase) check(smilehip_plan_set_lpc_order(plan, emobase_p), "smilehip_plan_set_lpc_order");
       if (spectrogram) check(smilehip_plan_set_spectrum_form(plan, spectrum_flags, spectrum_dbp_norm, spectrum_min_dbp), "smilehip_plan_set_spectrum_form");
     }
     return plan;
